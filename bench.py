@@ -18,16 +18,25 @@ work fixed -> strong scaling) and EVERY form of fsw_gnn_amd/dist.py is timed ove
 all-gather of the embedding), 'consumer' (every rank multiplies its slice block by its columns of the first Linear layer inside
 the fused kernel, the n x 128 partial sums are reduce-scattered, finished rows all-gathered) and 'exchange' (one all-to-all of
 slice blocks to the row owners); node-range chunks pipelined; the headline is the fastest form that leaves the full output on
-every rank.  Each form carries compute_ms (the same step with the collectives replaced by local copies), collective_ms /
-collective_GBps (the form's collectives alone on same-size buffers) and
-bytes per rank.  Recipient-row sharding (not the contracted partition) is timed in the same run as `other_partitions` and is
-never the headline; --shard nodes makes it the only thing that runs.
+every rank.  Each form carries bytes per rank and, with --full, compute_ms (the same step with the collectives replaced by
+local copies) and collective_ms / collective_GBps (the form's collectives alone on same-size buffers).  With --full,
+recipient-row sharding (not the contracted partition) is timed in the same run as `other_partitions` and is never the
+headline; --shard nodes makes it the only thing that runs.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  With --full the
+line also carries what takes runs of its own:
   roofline     the dominant kernel (k_conv_fused_unit; k_embed_reg_unit with --no-fuse) timed alone, HIP events on the launch stream:
-               achieved = its algorithmic bytes per launch / mean duration, against the 8 TB/s HBM peak;
+               achieved = its algorithmic bytes per launch / mean duration, against the 8 TB/s HBM peak; stage_ms at N = 1;
+  weak_scaling, segcumsum, other_partitions, and per form at N > 1 compute_ms / collective_ms (see above);
   cpu_baseline the C oracle (a port of the reference algorithm, oracle/fsw_oracle.c) on this box's host cores,
                rank 0 at N = 1 only, on a bounded sample of the same workload.
+--no-cpu-baseline, --no-segcumsum, --no-weak, --no-other-partitions and --kernel-reps shape those legs.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step returned (rank 0): a fixed, seeded sample of the
+output rows (y_rows.npy, float32, with their indices in y_row_index.npy) and the float64 sum of every output row (y_row_sum.npy),
+at most 64 MB in all.  An output too tall for every row sum to fit (above ~3.2M rows) sums a seeded sample of its rows instead,
+with their indices in y_row_sum_index.npy.  Inputs and weights are seeded, so two builds run with the same arguments can be
+compared file by file.
 """
 import argparse
 import ctypes
@@ -66,6 +75,11 @@ def parse(argv=None):
     ap.add_argument("--slices", type=int, default=N_SLICES,
                     help="slices of the layer (embed_dim = slices + 1).  256 = BASELINE config 3 (the metric's configuration); "
                          "1024 = config 4 (128 slices per GPU at 8 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: dominant-kernel roofline / stage_ms, weak scaling, segmented "
+                         "cumsum, CPU baseline, per-form compute / collective split and the recipient-row partition at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's output as DIR/<name>.npy (rank 0, <= 64 MB)")
     ap.add_argument("--kernel-reps", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-segcumsum", action="store_true", help="skip the stand-alone segmented-cumsum throughput leg")
@@ -91,6 +105,8 @@ def parse(argv=None):
     ap.add_argument("--output", choices=("replicated", "sharded"), default="replicated",
                     help="with --mode consumer: 'sharded' stops after the reduce-scatter (every rank keeps its finished rows)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.mode is not None:
         base = "consumer" if args.mode == "auto" else args.mode
         args.forms = base + ("_sharded" if args.output == "sharded" and base != "gather" else "")
@@ -428,6 +444,50 @@ def all_ranks_ok(ok, dev, world):
     return int(t) == 0
 
 
+DUMP_SEED = 20240607
+DUMP_MAX_ROWS = 65536               # sampled output rows: 32 MB at 128 float32 columns
+DUMP_ROW_BYTES = 32 << 20
+DUMP_TOTAL_BYTES = 60_000_000       # arrays written (< 64 MB with the .npy headers); the row sums get what the rows leave
+
+
+def sample_index(rows, k, seed):
+    """Sorted row indices: all rows when rows <= k, else a seeded sample of k of them (the same for every run and build)."""
+    if rows <= k:
+        return np.arange(rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(rows, size=k, replace=False)).astype(np.int64)
+
+
+def output_sample(y):
+    """What a caller of the timed step received, bounded to DUMP_TOTAL_BYTES: a seeded sample of the output rows (their own dtype,
+    float32 here) with their indices, and the float64 sum of every row -- or, when those 8 B per row do not fit in what the
+    sampled rows leave, the sums of a seeded sample of rows with their indices (16 B per sampled row).  A (rows, row0) pair from
+    a form that leaves the output sharded is taken as this rank's rows, chunk after chunk."""
+    if isinstance(y, tuple):
+        y = y[0].reshape(-1, y[0].shape[-1])
+    rows, cols = y.shape
+    k = max(1, min(DUMP_MAX_ROWS, DUMP_ROW_BYTES // (y.element_size() * cols)))
+    idx = sample_index(rows, k, DUMP_SEED)
+    left = DUMP_TOTAL_BYTES - idx.size * (8 + y.element_size() * cols)
+    sums_idx = sample_index(rows, left // 8 if rows * 8 <= left else left // 16, DUMP_SEED + 1)
+    dtype = np.float64 if y.dtype == torch.float64 else np.float32
+    with torch.no_grad():
+        sel = y.index_select(0, torch.from_numpy(idx).to(y.device))
+        sums = torch.sum(y.index_select(0, torch.from_numpy(sums_idx).to(y.device)) if sums_idx.size < rows else y,
+                         dim=1, dtype=torch.float64)
+        out = {"y_rows": sel.cpu().numpy().astype(dtype, copy=False), "y_row_index": idx.astype(np.float64),
+               "y_row_sum": sums.cpu().numpy()}
+    if sums_idx.size < rows:
+        out["y_row_sum_index"] = sums_idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_TOTAL_BYTES
+    return out
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 
 
 
@@ -566,19 +626,24 @@ def main():
         with torch.no_grad():
             return conv(x, ei)
 
-    forms, sp_stats = {}, {}
+    forms, sp_stats, dumped = {}, {}, None
+    dump = args.dump_outputs is not None and rank == 0
     node_parallel = world > 1 and args.shard == "nodes" and not args.no_fuse
     if world == 1:
         elapsed, y = timed_steps(step, args.warmup, args.steps, dev, world)
         assert torch.isfinite(y).all()
         headline = None
+        dumped = output_sample(y) if dump else None
     elif node_parallel:
         conv.enable_node_parallel(None)
         elapsed, y = timed_steps(step, args.warmup, args.steps, dev, world)
         assert torch.isfinite(y).all()
         headline = None
+        dumped = output_sample(y) if dump else None
     else:
         # every form over the same W + K steps; the headline is the fastest one that leaves the full output on every rank
+        full = [f for f in args.forms if FORM_ARGS[f][1] == "replicated"] or list(args.forms)
+        best = None
         for form in args.forms:
             mode, output = FORM_ARGS[form]
             st = {}
@@ -589,10 +654,15 @@ def main():
                            "form_taken": st.get("mode"), "collective": st.get("collective"), "output": output,
                            "bytes_sent_per_rank": st.get("bytes_sent_per_rank"),
                            "bytes_received_per_rank": st.get("bytes_received_per_rank"), "_elapsed": el, "_stats": st}
+            if form in full and (best is None or el < best):
+                best = el                       # the fastest headline candidate so far: its output is the one written
+                dumped = output_sample(y) if dump else None
             del y
-        full = [f for f in args.forms if FORM_ARGS[f][1] == "replicated"] or list(args.forms)
         headline = min(full, key=lambda f: forms[f]["_elapsed"])
         elapsed, sp_stats = forms[headline]["_elapsed"], forms[headline]["_stats"]
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
+        del dumped
 
     ms_per_step = elapsed / args.steps * 1e3
     value = float(e_coalesced) * S * args.steps / elapsed
@@ -613,13 +683,13 @@ def main():
         "path_roofline_frac": value * 5.13 / (HBM_PEAK_GBS * 1e9),
         "world": wrec,
     }
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         roof, ms = dominant_kernel_roofline(conv, x, ei, n, e_coalesced, args.kernel_reps, dev)
         result["roofline"] = roof
         result["stage_ms"] = ms
     if world > 1 and not node_parallel:
-        # the legs below only decorate the line (roofline of the sharded kernel, compute / collective split per form).  Local
-        # work sits in try blocks; before anything with a collective in it the ranks agree that all of them got there.
+        # the legs below only decorate the line (roofline of the sharded kernel, compute / collective split per form; --full).
+        # Local work sits in try blocks; before anything with a collective in it the ranks agree that all of them got there.
         H = conv.mlp[0].out_features
         width = 1 + max(b - a for a, b in D.slice_partition(S, world))
         reps = max(3, args.kernel_reps // 4)
@@ -627,6 +697,8 @@ def main():
             f = forms[form]
             st = f.pop("_stats")
             f.pop("_elapsed")
+            if not args.full:
+                continue
             mode, output = FORM_ARGS[form]
             conv.enable_slice_parallel(None, mode=mode, chunks=args.chunks or None, output=output, stats={})
             cms, err = 0.0, None
@@ -656,27 +728,28 @@ def main():
                 result[k] = forms[headline][k]
         result["slice_parallel"] = {"mode": forms[headline].get("form_taken"), "collective": forms[headline].get("collective"),
                                     "output": forms[headline]["output"]}
-        try:
-            roof = sharded_kernel_roofline(conv, x, ei, n, max(3, args.kernel_reps // 2), dev, rank, world,
-                                           forms[headline].get("form_taken") == "consumer")   # every rank runs it; no collective
-            if rank == 0:
-                result["roofline"] = roof
-        except Exception as e:   # noqa: BLE001 -- reported in the line, the headline number stands
-            result["extras_error"] = "%s: %s" % (type(e).__name__, e)
-    elif world > 1:
+        if args.full:
+            try:
+                roof = sharded_kernel_roofline(conv, x, ei, n, max(3, args.kernel_reps // 2), dev, rank, world,
+                                               forms[headline].get("form_taken") == "consumer")   # every rank runs it; no collective
+                if rank == 0:
+                    result["roofline"] = roof
+            except Exception as e:   # noqa: BLE001 -- reported in the line, the headline number stands
+                result["extras_error"] = "%s: %s" % (type(e).__name__, e)
+    elif world > 1 and args.full:
         try:
             roof = node_sharded_kernel_roofline(conv, x, ei, n, max(3, args.kernel_reps // 2), dev, rank, world)
             if rank == 0:
                 result["roofline"] = roof
         except Exception as e:   # noqa: BLE001
             result["extras_error"] = "%s: %s" % (type(e).__name__, e)
-    if world > 1 and not node_parallel and not args.no_fuse and not args.no_other_partitions:
+    if args.full and world > 1 and not node_parallel and not args.no_fuse and not args.no_other_partitions:
         result["other_partitions"] = {"recipient_rows": recipient_rows_leg(args, x, ei, e_coalesced, S, dev, world, rank)}
-    if not args.no_weak and not node_parallel and args.slices == N_SLICES:
+    if args.full and not args.no_weak and not node_parallel and args.slices == N_SLICES:
         del conv
         torch.cuda.empty_cache()
         result["weak_scaling"] = weak_scaling_leg(args, x, ei, e_coalesced, dev, world, rank)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_segcumsum:
             torch.cuda.empty_cache()
             try:

@@ -61,8 +61,8 @@ def test_embed_args_struct_matches_header_layout():
     assert ctypes.sizeof(_lib.EmbedArgs) == 8 * 6 + 8 * 3 + 8 + 8 * 2 + 8 * 3 + 16 + 8 * 5 + 16 + 8 * 3 + 8 + 8
 
 
-def test_sorting_networks_native():
-    exe = "/tmp/fsw_test_sortnet"
+def test_sorting_networks_native(tmp_path):
+    exe = str(tmp_path / "fsw_test_sortnet")
     src = os.path.join(ROOT, "tests", "native", "test_sortnet.cpp")
     subprocess.run(["g++", "-O1", "-std=c++17", src, "-o", exe], check=True)
     assert subprocess.run([exe], capture_output=True, text=True).stdout.strip().endswith("OK")
@@ -308,6 +308,58 @@ def test_bench_self_launch_command_and_relay(tmp_path, capfd):
         assert bench.self_launch(a2, ["--gpus", "2"], script=str(script)) != 0      # a failing rank fails the run
     finally:
         del os.environ["FAKE_RC"]
+
+
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """A plain bench.py run leaves the side legs to --full; --dump-outputs writes a fixed, bounded sample of the step's output."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    y = torch.randn(100_000, 128, generator=torch.Generator().manual_seed(3))
+    s1, s2 = bench.output_sample(y), bench.output_sample(y.clone())
+    assert set(s1) == {"y_rows", "y_row_index", "y_row_sum"}
+    assert sum(v.nbytes for v in s1.values()) <= 64 << 20
+    idx = s1["y_row_index"].astype(np.int64)
+    assert s1["y_rows"].dtype == np.float32 and s1["y_rows"].shape == (bench.DUMP_MAX_ROWS, 128)
+    assert np.array_equal(s1["y_rows"], y.numpy()[idx]) and np.array_equal(idx, np.unique(idx))
+    assert s1["y_row_sum"].dtype == np.float64 and np.allclose(s1["y_row_sum"], y.double().sum(1).numpy())
+    assert all(np.array_equal(s1[k], s2[k]) for k in s1)                      # the same rows every run
+    bench.write_outputs(str(tmp_path / "out"), s1)
+    assert np.array_equal(np.load(tmp_path / "out" / "y_rows.npy"), s1["y_rows"])
+    small = bench.output_sample(y[:10])                                       # small outputs are written whole
+    assert np.array_equal(small["y_rows"], y[:10].numpy())
+
+
+def test_bench_output_dump_stays_in_budget_above_the_row_sum_cap(monkeypatch):
+    """An output too tall for every row sum: the sums of a seeded sample of rows plus their indices, still inside the budget;
+    and a sharded form's (R [chunks, rows, H], row0) pair is taken as the rank's rows, chunk after chunk."""
+    import bench
+    cols = 8
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 64)
+    monkeypatch.setattr(bench, "DUMP_TOTAL_BYTES", 64 * (8 + 4 * cols) + 8000)   # 8000 B left: 1000 sums, or 500 with indices
+    g = torch.Generator().manual_seed(5)
+    whole = bench.output_sample(torch.randn(1000, cols, generator=g))
+    assert set(whole) == {"y_rows", "y_row_index", "y_row_sum"} and whole["y_row_sum"].shape == (1000,)
+    for rows in (1001, 50_000):
+        y = torch.randn(rows, cols, generator=g)
+        s = bench.output_sample(y)
+        assert set(s) == {"y_rows", "y_row_index", "y_row_sum", "y_row_sum_index"}
+        assert sum(v.nbytes for v in s.values()) <= bench.DUMP_TOTAL_BYTES
+        sidx = s["y_row_sum_index"].astype(np.int64)
+        assert sidx.shape == (500,) and np.array_equal(sidx, np.unique(sidx)) and sidx[-1] < rows
+        assert np.allclose(s["y_row_sum"], y.double().sum(1).numpy()[sidx])
+        assert np.array_equal(sidx, bench.output_sample(y.clone())["y_row_sum_index"].astype(np.int64))
+    # the real budget: the sampled branch fits below 64 MB, the headline output (1M x 128) keeps every row sum
+    monkeypatch.undo()
+    assert bench.DUMP_TOTAL_BYTES + 4 * 128 <= 64_000_000                     # + four .npy headers
+    assert bench.DUMP_TOTAL_BYTES - bench.DUMP_MAX_ROWS * (8 + 4 * 128) >= 8 * bench.N_NODES
+    R = torch.randn(3, 40, cols, generator=g)
+    s = bench.output_sample((R, torch.tensor([0, 40, 80])))
+    assert np.array_equal(s["y_rows"], R.reshape(-1, cols).numpy()) and np.allclose(s["y_row_sum"], R.double().sum(2).reshape(-1).numpy())
 
 
 def test_build_hint_is_per_owner_and_never_risks_an_unknown_graph():

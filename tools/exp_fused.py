@@ -3,7 +3,7 @@ import os, sys, subprocess
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for dbg in (0, 1, 2, 4, 6, 7):
     env = dict(os.environ, FSW_FUSED_ABL=str(dbg))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True).stdout
     import json
     try:

@@ -29,6 +29,6 @@ echo "== slice shard compute"
 timeout -k 10 300 python tools/exp_slice_shard.py --worlds 4,8 2>/dev/null | tee "$out/slice_shard.log"
 timeout -k 10 300 python tools/exp_slice_shard.py --worlds 4,8 --mode exchange 2>/dev/null | tee "$out/slice_shard_x.log"
 echo "== bench N=1"
-timeout -k 10 400 python bench.py > "$out/bench1.json" 2> "$out/bench1.err"; echo "rc=$?"; tail -c 1800 "$out/bench1.json"
+timeout -k 10 400 python bench.py --full > "$out/bench1.json" 2> "$out/bench1.err"; echo "rc=$?"; tail -c 1800 "$out/bench1.json"
 echo "== bench --gpus 2 (gloo rehearsal)"
-FSW_BENCH_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 2 --steps 2 --warmup 1 --kernel-reps 4 > "$out/bench_g2.json" 2> "$out/bench_g2.err"; echo "rc=$?"; tail -c 2500 "$out/bench_g2.json"; tail -3 "$out/bench_g2.err"
+FSW_BENCH_BACKEND=gloo timeout -k 10 500 python bench.py --full --gpus 2 --steps 2 --warmup 1 --kernel-reps 4 > "$out/bench_g2.json" 2> "$out/bench_g2.err"; echo "rc=$?"; tail -c 2500 "$out/bench_g2.json"; tail -3 "$out/bench_g2.err"

@@ -28,7 +28,7 @@ else
   [ "$1" = run ] && shift
   for lib in "$out"/libfsw_hip_*.so; do
     name=$(basename "$lib" .so); name=${name#libfsw_hip_}
-    FSW_HIP_LIBRARY=$lib python "$root/bench.py" --no-cpu-baseline --steps 10 --warmup 2 "$@" > "$out/$name.json" 2>"$out/$name.err" || { echo "$name FAILED"; tail -3 "$out/$name.err"; continue; }
+    FSW_HIP_LIBRARY=$lib python "$root/bench.py" --full --no-cpu-baseline --steps 10 --warmup 2 "$@" > "$out/$name.json" 2>"$out/$name.err" || { echo "$name FAILED"; tail -3 "$out/$name.err"; continue; }
     python - "$out/$name.json" "$name" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
