@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FSW_HIP_LIBRARY: another build of the same library (kernel tuning experiments, tools/exp_variants.sh)
 LIB_PATH = os.environ.get("FSW_HIP_LIBRARY") or os.path.join(_HERE, "libfsw_hip.so")
 
-FSW_ABI_VERSION = 5
+FSW_ABI_VERSION = 6
 REG_MAX_DEG = 32
 LDS_MAX_DEG = 2048
 MID_SIZES = (40, 48, 64, 80, 96, 128, 160, 192, 256)   # FSW_MID_SIZES: padded register-path networks above REG_MAX_DEG
@@ -55,6 +55,18 @@ class GenericArgs(ctypes.Structure):
     ]
 
 
+class CartArgs(ctypes.Structure):
+    """struct fsw_cart_args of include/fsw_hip.h (field order and types must match)."""
+    _fields_ = [
+        ("value_dtype", c_i32), ("S", c_i32), ("F", c_i32), ("has_mass", c_i32),
+        ("rowptr", c_vp), ("col", c_vp), ("w", c_vp), ("perm", c_vp), ("bin_start", c_vp), ("bin_start_host", c_vp),
+        ("num_rows", c_i64), ("max_degree", c_i64), ("Xp", c_vp), ("ldp", c_i64), ("freqs", c_vp), ("tau", ctypes.c_double),
+        ("unit_table", c_vp), ("ldt", c_i64), ("out", c_vp), ("ldo", c_i64), ("bias", c_vp), ("out_scale", ctypes.c_double),
+        ("mass_fn", c_i32), ("reserved", c_i32), ("mass_scale", ctypes.c_double), ("g", c_vp), ("ldg", c_i64),
+        ("gkey", c_vp), ("ldk", c_i64), ("gfreq", c_vp), ("gw", c_vp), ("scratch", c_vp), ("scratch_bytes", c_sz),
+    ]
+
+
 _SIGNATURES = {
     "fsw_abi_version": (ctypes.c_int, []),
     "fsw_arch": (ctypes.c_char_p, []),
@@ -87,6 +99,9 @@ _SIGNATURES = {
     "fsw_embed_generic_scratch_bytes": (c_sz, [c_i64, c_i64]),
     "fsw_embed_generic": (ctypes.c_int, [ctypes.POINTER(GenericArgs), c_vp]),
     "fsw_project_f64": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_vp, ctypes.c_int, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "fsw_embed_cart_generic_scratch_bytes": (c_sz, [c_i64, c_i64]),
+    "fsw_embed_cart_generic": (ctypes.c_int, [ctypes.POINTER(CartArgs), c_vp]),
+    "fsw_embed_cart_f32": (ctypes.c_int, [ctypes.POINTER(CartArgs), c_vp]),
     "fsw_segcumsum_workspace_bytes": (c_sz, [c_i64]),
     "fsw_segcumsum": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, c_i64, ctypes.c_int, c_vp, c_sz, c_vp]),
     # legacy ABI, exact reference signatures (reference fsw_embedding.py:2952-2977)

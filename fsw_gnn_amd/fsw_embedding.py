@@ -13,7 +13,15 @@ csrc/embed_wsort_bwd.hip) for every weight mode and degree class; gradients flow
 total-mass scale (the weights W are constants).
 Edge features (d_edge > 0) go through the coalescing CSR build and the general-weight kernels.
 dtype=torch.float64 modules and gradients w.r.t. the weights W / sparse edge features run on the generic kernels
-(csrc/embed_generic.hip: any degree, float64 arithmetic).  Not implemented (raise NotImplementedError): Cartesian mode.
+(csrc/embed_generic.hip: any degree, float64 arithmetic).
+
+Cartesian mode, FSW_embedding(d_in, nSlices=S, nFreqs=F, collapse_freqs=...) (reference fsw_embedding.py:153-160, 241-259):
+every slice is sorted once and read out at all F frequencies (csrc/embed_cart.hip); output (<batch>, [nR,] S, F), or
+(<batch>, [nR,] S*F + mass_dim) collapsed, column s*F + f (after the mass column).  no_grad float32 calls run on the tuned
+kernels, autograd calls and float64 modules on the generic Cartesian kernel.  It needs a HIP device at construction (this
+package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
+differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
+bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
 """
 import ctypes
 import numbers
@@ -364,15 +372,37 @@ class _GenericEmbedFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
+        return _GenericEmbedFn.host_backward(ctx, g.contiguous(), _GenericEmbedFn.key_grads)
+
+    @staticmethod
+    def key_grads(ctx, g, gkey, gf, gw):
+        """fsw_embed_generic in backward mode: stores gkey [nnz, S], accumulates gf [S] and gw [nnz] (each nullable)."""
         L = _lib.lib()
+        module, csr = ctx.module, ctx.csr
+        X, V, freqs, efvals = ctx.saved_tensors
+        Xp, ldp, Ke, wv = ctx.aux
+        dev = X.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        has_mass = 1 if module.encode_total_mass else 0
+        scratch = torch.empty(int(L.fsw_embed_generic_scratch_bytes(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8, device=dev)
+        a = _generic_args(module, csr, Xp, ldp, Ke, freqs.detach().contiguous(), wv, ctx.out_scale, has_mass, ctx.mass_scale_value, scratch)
+        a.g, a.ldg = g.data_ptr(), g.stride(0)
+        a.gkey, a.ldk = (gkey.data_ptr(), gkey.shape[1]) if gkey is not None else (None, 0)
+        a.gfreq = gf.data_ptr() if gf is not None else None
+        a.gw = gw.data_ptr() if gw is not None else None
+        _lib.check(L.fsw_embed_generic(ctypes.byref(a), stream), "fsw_embed_generic (backward)")
+
+    @staticmethod
+    def host_backward(ctx, g, key_grads):
+        """Everything of the backward but the kernel call key_grads(ctx, g, gkey, gf, gw): the GEMMs of gX and gprojVecs, the
+        bias, total-mass scale and weight gradients.  Shared with _CartesianEmbedFn (gkey has one column per slice, gf one
+        entry per frequency)."""
         module, csr, out_scale = ctx.module, ctx.csr, ctx.out_scale
         X, V, freqs, efvals = ctx.saved_tensors
         Xp, ldp, Ke, wv = ctx.aux
         dev, dt = X.device, X.dtype
-        stream = torch.cuda.current_stream(dev).cuda_stream
         S, d_in = module.nSlices, module.d_in
         has_mass = 1 if module.encode_total_mass else 0
-        g = g.contiguous()
         need = ctx.needs_input_grad
         gX = gV = gfreqs = gbias = gscale = gW = gEf = None
         nnz = csr.nnz
@@ -380,15 +410,9 @@ class _GenericEmbedFn(torch.autograd.Function):
         want_w = ctx.has_w and need[5]
         if nnz and S and (want_key or need[2] or want_w):
             gkey = torch.zeros((nnz, S), dtype=dt, device=dev) if want_key else None
-            gf = torch.zeros(S, dtype=dt, device=dev) if need[2] else None
+            gf = torch.zeros(freqs.numel(), dtype=dt, device=dev) if need[2] else None
             gw = torch.zeros(nnz, dtype=dt, device=dev) if want_w else None
-            scratch = torch.empty(int(L.fsw_embed_generic_scratch_bytes(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8, device=dev)
-            a = _generic_args(module, csr, Xp, ldp, Ke, freqs.detach().contiguous(), wv, out_scale, has_mass, ctx.mass_scale_value, scratch)
-            a.g, a.ldg = g.data_ptr(), g.stride(0)
-            a.gkey, a.ldk = (gkey.data_ptr(), S) if gkey is not None else (None, 0)
-            a.gfreq = gf.data_ptr() if gf is not None else None
-            a.gw = gw.data_ptr() if gw is not None else None
-            _lib.check(L.fsw_embed_generic(ctypes.byref(a), stream), "fsw_embed_generic (backward)")
+            key_grads(ctx, g, gkey, gf, gw)
             Vd = V.detach()
             if need[0] or need[1]:
                 gXp = torch.zeros((X.shape[0], S), dtype=dt, device=dev).index_add_(0, csr.col.long(), gkey)
@@ -425,6 +449,88 @@ class _GenericEmbedFn(torch.autograd.Function):
         if want_w and gW is None:
             gW = torch.zeros(nnz, dtype=dt, device=dev)
         return gX, gV, gfreqs, gbias, gscale, gW, gEf, None, None, None
+
+
+def _cart_args(module, Xp, ldp, freqs, S, out_scale, has_mass, mass_scale):
+    """struct fsw_cart_args with the fields both Cartesian entry points share."""
+    a = _lib.CartArgs()
+    a.value_dtype = 1 if Xp.dtype == torch.float64 else 0
+    a.S, a.F, a.has_mass = S, module.nFreqs, has_mass
+    a.Xp, a.ldp, a.freqs = Xp.data_ptr(), ldp, freqs.data_ptr()
+    a.tau, a.out_scale = float(module.total_mass_pad_thresh), float(out_scale)
+    a.mass_fn, a.mass_scale = _MASS_FN[module.total_mass_encoding_function], float(mass_scale)
+    return a
+
+
+class _CartesianEmbedFn(torch.autograd.Function):
+    """Cartesian mode through the generic kernel (csrc/embed_cart.hip, fsw_embed_cart_generic: any degree, float32 or float64
+    storage, float64 arithmetic): out [num_rows, has_mass + S F], column has_mass + s F + f = (slice s, frequency f).  Gradients
+    for X, projVecs, freqs, bias (flattened), the total-mass scale and the weights; the host side of the backward is
+    _GenericEmbedFn.host_backward.  Same arguments as _GenericEmbedFn (efvals is always None: no edge features here)."""
+
+    @staticmethod
+    def forward(ctx, X, V, freqs, bias, mass_scale, wvals, efvals, module, csr, out_scale):
+        L = _lib.lib()
+        dev, dt = X.device, X.dtype
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        S, d_in = module.nSlices, module.d_in
+        has_mass = 1 if module.encode_total_mass else 0
+        with torch.no_grad():
+            Xc, Vd, fr = X.detach().contiguous(), V.detach(), freqs.detach().contiguous()
+            ldp = _round_up(S, 32)
+            Xp = torch.empty((Xc.shape[0], ldp), dtype=dt, device=dev)
+            if dt == torch.float64:
+                _lib.check(L.fsw_project_f64(_lib.ptr(Xc), Xc.shape[0], d_in, Xc.stride(0), _lib.ptr(Vd), S, Vd.stride(0), _lib.ptr(Xp), ldp,
+                                             None, stream), "fsw_project_f64")
+            else:
+                _lib.check(L.fsw_project_f32(_lib.ptr(Xc), Xc.shape[0], d_in, Xc.stride(0), _lib.ptr(Vd), S, Vd.stride(0), _lib.ptr(Xp), ldp,
+                                             None, 0, None, stream), "fsw_project_f32")
+            wv = wvals.detach().contiguous() if wvals is not None else None
+            out = torch.empty((csr.num_rows, module.d_out), dtype=dt, device=dev)
+            ms = float(mass_scale.detach()) if mass_scale is not None else 1.0
+            scratch = torch.empty(int(L.fsw_embed_cart_generic_scratch_bytes(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8,
+                                  device=dev)
+            b = bias.detach().contiguous() if bias is not None else None
+            a = _CartesianEmbedFn.args(module, csr, Xp, ldp, fr, wv, out_scale, has_mass, ms, scratch)
+            a.out, a.ldo = out.data_ptr(), out.stride(0)
+            a.bias = b.data_ptr() if b is not None else None
+            _lib.check(L.fsw_embed_cart_generic(ctypes.byref(a), stream), "fsw_embed_cart_generic")
+        ctx.module, ctx.csr, ctx.out_scale, ctx.mass_scale_value = module, csr, float(out_scale), ms
+        ctx.aux = (Xp, ldp, None, wv)
+        ctx.has_ef, ctx.has_w = False, wvals is not None
+        ctx.save_for_backward(X, V, freqs, X.new_zeros(0))
+        return out
+
+    @staticmethod
+    def args(module, csr, Xp, ldp, freqs, wv, out_scale, has_mass, mass_scale, scratch):
+        a = _cart_args(module, Xp, ldp, freqs, module.nSlices, out_scale, has_mass, mass_scale)
+        a.rowptr, a.col = csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None
+        a.w = wv.data_ptr() if wv is not None else None
+        a.num_rows, a.max_degree = csr.num_rows, csr.max_degree
+        a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        return a
+
+    @staticmethod
+    def key_grads(ctx, g, gkey, gf, gw):
+        L = _lib.lib()
+        module, csr = ctx.module, ctx.csr
+        X, V, freqs, _ = ctx.saved_tensors
+        Xp, ldp, _, wv = ctx.aux
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        scratch = torch.empty(int(L.fsw_embed_cart_generic_scratch_bytes(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8,
+                              device=X.device)
+        a = _CartesianEmbedFn.args(module, csr, Xp, ldp, freqs.detach().contiguous(), wv, ctx.out_scale,
+                                   1 if module.encode_total_mass else 0, ctx.mass_scale_value, scratch)
+        a.g, a.ldg = g.data_ptr(), g.stride(0)
+        a.gkey, a.ldk = (gkey.data_ptr(), gkey.shape[1]) if gkey is not None else (None, 0)
+        a.gfreq = gf.data_ptr() if gf is not None else None
+        a.gw = gw.data_ptr() if gw is not None else None
+        _lib.check(L.fsw_embed_cart_generic(ctypes.byref(a), stream), "fsw_embed_cart_generic (backward)")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return _GenericEmbedFn.host_backward(ctx, g.contiguous(), _CartesianEmbedFn.key_grads)
 
 
 class FSW_embedding(nn.Module):
@@ -482,7 +588,12 @@ class FSW_embedding(nn.Module):
             self.nSlices = d_out - self.total_mass_encoding_dim
             self.nFreqs = d_out - self.total_mass_encoding_dim
         elif (d_out is None) and (nSlices is not None) and (nFreqs is not None):
-            raise NotImplementedError("fsw_gnn_amd: Cartesian mode (nSlices x nFreqs) is out of scope (SURVEY.md 2, #14)")
+            assert collapse_freqs or (not encode_total_mass), 'Cartesian mode with collapse_freqs=False is not supported when encode_total_mass=True'
+            self.cartesian_mode = True
+            self.collapse_freqs = bool(collapse_freqs)
+            self.nSlices = nSlices
+            self.nFreqs = nFreqs
+            self.d_out = nSlices * nFreqs + self.total_mass_encoding_dim
         else:
             assert False, "Expected exactly one of (d_out != None) or (nSlices != None and nFreqs != None)"
         assert self.d_out >= 0, 'd_out must be nonnegative'
@@ -495,6 +606,14 @@ class FSW_embedding(nn.Module):
         if device is None:
             device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.device_new = torch.device(device)
+        if self.cartesian_mode:
+            # checked before any parameter exists: a module that cannot run is not built at all
+            if self.device_new.type != 'cuda':
+                raise NotImplementedError("fsw_gnn_amd: Cartesian mode needs a HIP device ('cuda'), got device=%s; this package has "
+                                          "no CPU path in any mode" % self.device_new)
+            if d_edge > 0:
+                raise NotImplementedError("fsw_gnn_amd: Cartesian mode with edge features (d_edge > 0) is not implemented (the "
+                                          "reference lists the combination as untested)")
         assert dtype.is_floating_point and (not dtype.is_complex), \
             'dtype must be real floating-point; instead got dtype=%s' % (dtype)
         if dtype not in (torch.float32, torch.float64):
@@ -504,7 +623,12 @@ class FSW_embedding(nn.Module):
         self.report_on_coherence_minimization = report_on_coherence_minimization
         if report:
             print('Fourier Sliced-Wasserstein Embedding, MI355X-native build %s' % version)
-            print('Using %d (slice, frequency) pairs; device: %s    dtype: %s' % (self.nSlices, self.device_new, dtype))
+            if self.cartesian_mode:
+                print('Cartesian mode: %d slices x %d frequencies -> %s; device: %s    dtype: %s' % (
+                    self.nSlices, self.nFreqs, ('R^%d' % self.d_out) if self.collapse_freqs else ('R^(%dx%d)' % (self.nSlices, self.nFreqs)),
+                    self.device_new, dtype))
+            else:
+                print('Using %d (slice, frequency) pairs; device: %s    dtype: %s' % (self.nSlices, self.device_new, dtype))
         self.reset_parameters()
 
     # ------------------------------------------------------------------------------------------------
@@ -530,7 +654,8 @@ class FSW_embedding(nn.Module):
             d_in=self.d_in + self.d_edge, nSlices=self.nSlices, nFreqs=self.nFreqs,
             total_mass_encoding_dim=self.total_mass_encoding_dim,
             total_mass_encoding_scale_init=self.total_mass_encoding_scale_init, freqs_init=self.freqs_init, device=device,
-            minimize_slice_coherence=self.minimize_slice_coherence, report=self.report_on_coherence_minimization)
+            minimize_slice_coherence=self.minimize_slice_coherence, report=self.report_on_coherence_minimization,
+            cartesian_mode=self.cartesian_mode, collapse_freqs=self.collapse_freqs)
         self.projVecs = nn.Parameter(projVecs.to(dtype=dtype, device=device), requires_grad=self.learnable_slices)
         self.freqs = nn.Parameter(freqs.to(dtype=dtype, device=device), requires_grad=self.learnable_freqs)
         if self.enable_bias:
@@ -541,7 +666,8 @@ class FSW_embedding(nn.Module):
 
     @staticmethod
     def generate_embedding_parameters(d_in, nSlices, nFreqs, total_mass_encoding_dim, total_mass_encoding_scale_init,
-                                      freqs_init, device, minimize_slice_coherence=False, report=False):
+                                      freqs_init, device, minimize_slice_coherence=False, report=False, cartesian_mode=False,
+                                      collapse_freqs=False):
         dt = torch.float64
         # A. random unit projection vectors (reference :448-456), optionally spread out by mutual-coherence
         #    minimisation (:464, :3045-3248 -> coherence.py)
@@ -583,8 +709,16 @@ class FSW_embedding(nn.Module):
         if nFreqs > 0:
             assert not torch.isinf(freqs).any(), "Found infs in freqs"
             assert not torch.isnan(freqs).any(), "Found nans in freqs"
-        # C. zero bias (reference :542-550) and the total-mass scale
-        bias = torch.zeros(size=(nSlices + total_mass_encoding_dim,), dtype=dt, device=device)
+        # C. zero bias (reference :542-550) and the total-mass scale.  Cartesian mode: (nSlices, nFreqs), collapsed
+        #    (nSlices * nFreqs + total_mass_encoding_dim,) -- with the total mass the reference's constructor then fails to
+        #    reshape this to nSlices * nFreqs (:403-404); here the mass column keeps its bias entry
+        if cartesian_mode and not collapse_freqs:
+            bias_shape = (nSlices, nFreqs)
+        elif cartesian_mode:
+            bias_shape = (nSlices * nFreqs + total_mass_encoding_dim,)
+        else:
+            bias_shape = (nSlices + total_mass_encoding_dim,)
+        bias = torch.zeros(size=bias_shape, dtype=dt, device=device)
         scale = torch.tensor(total_mass_encoding_scale_init, device=device, dtype=dt) if total_mass_encoding_dim > 0 else None
         return projVecs, freqs, bias, scale
 
@@ -709,6 +843,10 @@ class FSW_embedding(nn.Module):
             Xf = X.reshape(B * n, d)
             num_rows, out_shape = B * nR, batch_dims + (nR,)
 
+        if self.cartesian_mode:
+            generic = self.get_dtype() == torch.float64 or needs_grad or (torch.is_grad_enabled() and torch.is_tensor(W) and W.requires_grad)
+            out = self._forward_cartesian(Xf, rec, snd, wvals, num_rows, generic, serialize_num_slices)
+            return out.reshape(out_shape + ((self.d_out,) if self.collapse_freqs else (self.nSlices, self.nFreqs)))
         if generic and num_rows > 0 and Xf.shape[0] > 0:
             if self.d_out == 0:
                 return torch.zeros(out_shape + (0,), dtype=X.dtype, device=X.device)
@@ -745,6 +883,91 @@ class FSW_embedding(nn.Module):
         plain = (not self.encode_total_mass) or self.total_mass_encoding_method == 'plain'
         P = _GenericEmbedFn.apply(Xf, self.projVecs, self.freqs, bias if plain else None, scale, wvals, efvals, self, csr, 1.0)
         return P if plain else self._homog_epilogue(P, 1.0, bias)
+
+    def _forward_cartesian(self, Xf, rec, snd, wvals, num_rows, generic, serialize_num_slices):
+        """Cartesian mode: [num_rows, has_mass + S F], column has_mass + s F + f = (slice s, frequency f).  generic: the generic
+        kernel (float64 modules, autograd); otherwise the tuned float32 forward (csrc/embed_cart.hip)."""
+        dev, dt = Xf.device, Xf.dtype
+        S, F = self.nSlices, self.nFreqs
+        if num_rows == 0 or self.d_out == 0:
+            return torch.zeros((num_rows, self.d_out), dtype=dt, device=dev)
+        if S * F == 0:
+            raise NotImplementedError("fsw_gnn_amd: Cartesian mode with nSlices * nFreqs == 0 and encode_total_mass is not supported")
+        bias = self.bias.reshape(-1) if self.enable_bias else None
+        plain = (not self.encode_total_mass) or self.total_mass_encoding_method == 'plain'
+        if Xf.shape[0] == 0:
+            # empty multisets only: the embedding of the pad element alone is 0 and so is f(0) for every mass encoding and method,
+            # which leaves the bias (any dtype; differentiable in the bias)
+            Z = torch.zeros((num_rows, self.d_out), dtype=dt, device=dev)
+            return Z + bias if bias is not None else Z
+        if generic:
+            if fsw_embedding_basic_safety_checks:      # reference fsw_embedding.py:652-703
+                assert bool(torch.isfinite(Xf).all()), "The entries of X cannot contain NaNs or infs"
+                if wvals is not None:
+                    assert bool(torch.isfinite(wvals).all()), "All entries of W must be finite"
+                    assert bool((wvals >= 0).all()), "All entries of W must be nonnegative"
+            csr = SimpleCSR(rec, snd, num_rows, Xf.shape[0])
+            scale = self.total_mass_encoding_scale if self.encode_total_mass else None
+            P = _CartesianEmbedFn.apply(Xf.contiguous(), self.projVecs, self.freqs, bias if plain else None, scale, wvals, None, self,
+                                        csr, 1.0)
+            return P if plain else self._homog_epilogue(P, 1.0, bias)
+        graph = build_csr(rec, snd, wvals.contiguous() if wvals is not None else None, num_rows, Xf.shape[0])
+        with torch.no_grad():
+            out = torch.empty((num_rows, self.d_out), dtype=dt, device=dev)
+            self.embed_cartesian_into(Xf.contiguous(), graph, out, bias.detach() if (bias is not None and plain) else None,
+                                      serialize_num_slices)
+            return out if plain else self._homog_epilogue(out, 1.0, bias.detach() if bias is not None else None)
+
+    def embed_cartesian_into(self, X, graph: CSRGraph, out, bias=None, serialize_num_slices=None, out_scale=1.0):
+        """Tuned float32 Cartesian forward (fsw_embed_cart_f32) of a CSR graph into out [num_rows, d_out] (unit inner stride): the
+        'plain' embedding, plus bias [has_mass + S F] when given.  serialize_num_slices chunks the slices; every chunk covers all
+        frequencies (reference fsw_embedding.py:848)."""
+        L = _lib.lib()
+        dev = X.device
+        S, F = self.nSlices, self.nFreqs
+        has_mass = 1 if self.encode_total_mass else 0
+        assert X.is_contiguous() and X.dtype == torch.float32 and out.stride(1) == 1 and out.shape[0] == graph.num_rows
+        assert out.shape[1] >= has_mass + S * F and graph.num_chunks == 1
+        step = S if (serialize_num_slices is None or serialize_num_slices >= S) else int(serialize_num_slices)
+        assert step >= 1, 'serialize_num_slices must be None or a positive integer'
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ldp = _round_up(step, 32)      # fsw_project_f32 takes its wavefront-per-tile kernel for <= 64 columns at this stride
+        Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=dev)
+        fr = self.freqs.detach().contiguous()
+        V = self.projVecs.detach()
+        table = None
+        if graph.w is None and self.total_mass_pad_thresh <= 1.0:
+            table = torch.empty((int(L.fsw_unit_table_rows(_lib.REG_MAX_DEG)), F), dtype=torch.float32, device=dev)
+            _lib.check(L.fsw_unit_coeff_table(_lib.ptr(fr), F, _lib.REG_MAX_DEG, _lib.ptr(table), F, stream), "fsw_unit_coeff_table")
+        st = None
+        scratch = None
+        for k0 in range(0, S, step):
+            k1 = min(S, k0 + step)
+            Vc = V[k0:k1]
+            _lib.check(L.fsw_project_f32(_lib.ptr(X), X.shape[0], self.d_in, X.stride(0), _lib.ptr(Vc), k1 - k0, Vc.stride(0), _lib.ptr(Xp),
+                                         ldp, None, 0, _lib.ptr(graph.stats_dev) if k0 == 0 else None, stream), "fsw_project_f32")
+            if st is None:
+                st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
+                bsh = graph.bin_start_host[0]
+                if st[_lib.STAT_MAX_DEGREE] >= _lib.LDS_MAX_DEG:
+                    long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[_lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS - 1])
+                    scratch = torch.empty(int(L.fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
+                                          dtype=torch.uint8, device=dev)
+            first = k0 == 0
+            col0 = 0 if first else has_mass + k0 * F
+            ms = struct.unpack('f', struct.pack('i', st[_lib.STAT_USER]))[0] if self.encode_total_mass else 1.0
+            a = _cart_args(self, Xp, ldp, fr, k1 - k0, out_scale, has_mass if first else 0, ms)
+            a.rowptr, a.col = graph.rowptr.data_ptr(), graph.col.data_ptr()
+            a.w = graph.w.data_ptr() if graph.w is not None else None
+            a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), bsh.ctypes.data
+            a.num_rows, a.max_degree = graph.num_rows, st[_lib.STAT_MAX_DEGREE]
+            a.unit_table, a.ldt = (table.data_ptr(), F) if table is not None else (None, 0)
+            a.out, a.ldo = out.data_ptr() + 4 * col0, out.stride(0)
+            a.bias = (bias.data_ptr() + 4 * col0) if bias is not None else None
+            if scratch is not None:
+                a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
+            _lib.check(L.fsw_embed_cart_f32(ctypes.byref(a), stream), "fsw_embed_cart_f32")
+        return out
 
     def _homog_epilogue(self, P, out_scale, bias):
         """'homog' / 'homog_alt' (reference fsw_embedding.py:874-882, 1136-1144) on the 'plain' embedding P = [f(m) scale | emb]

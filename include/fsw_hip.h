@@ -33,7 +33,7 @@ extern "C" {
 
 typedef void* fsw_stream_t; /* a hipStream_t (torch.cuda.current_stream().cuda_stream) */
 
-#define FSW_ABI_VERSION 5
+#define FSW_ABI_VERSION 6
 
 /* Degree classes of the fused neighbourhood kernels.  Rows are binned by in-degree:
  *   bin b, 0 <= b <= FSW_REG_MAX_DEG : rows of degree exactly b (register path, one wave per row and
@@ -346,6 +346,63 @@ int fsw_embed_generic(const fsw_generic_args* args, fsw_stream_t stream);
  * FSW_FLAG_X_NONFINITE in stats[FSW_STAT_FLAGS] (stats nullable) */
 int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double* V, int S, int64_t ldv, double* Xp,
                     int64_t ldp, int32_t* stats, fsw_stream_t stream);
+
+/* ---- Cartesian slice x frequency mode (csrc/embed_cart.hip) -------------------------------------------------------------
+ * FSW_embedding(d_in, nSlices=S, nFreqs=F) (reference fsw_embedding.py:241-259, 1037-1045): every slice s is sorted once and read
+ * out at every frequency f.  Column has_mass + s * F + f of out belongs to (slice s, frequency f) (torch.flatten order, :853-854):
+ *   out[r * ldo + has_mass + s F + f] = out_scale * ((1 + xi_f) sum_t Delta_t(xi_f) p_(t) + bias[has_mass + s F + f])
+ *   out[r * ldo]                      = out_scale * (f(m_r) * mass_scale + bias[0])                     if has_mass
+ * where p_(t) sorts Xp[col[e], s] over the row's entries (+ the pad element) and Delta_t is the readout of fsw_embed_generic.
+ * fsw_embed_cart_f32      tuned float32 forward on a graph of fsw_graph_build: needs perm, bin_start and bin_start_host,
+ *                         unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1, and scratch of
+ *                         fsw_embed_cart_generic_scratch_bytes(max_degree, rows above FSW_LDS_MAX_DEG) bytes when
+ *                         max_degree >= FSW_LDS_MAX_DEG (those rows run on the generic kernel).
+ * fsw_embed_cart_generic  any degree, float32 or float64 storage (value_dtype), float64 arithmetic, on a plain CSR (perm, bin_start
+ *                         ignored); forward (g == NULL) or backward (g != NULL): for the output gradient g [num_rows, ldg]
+ *                           gkey[e * ldk + s]  = sum_f out_scale g[r, has_mass + s F + f] d out / d key_e     (stored; nullable)
+ *                           gfreq[f]          += out_scale sum_{r,s} g[r, has_mass + s F + f] d out / d xi_f  (nullable)
+ *                           gw[e]             += out_scale sum_{s,f} g[r, has_mass + s F + f] d out / d w_e   (nullable; the
+ *                                                total-mass column's dependence on w is NOT included).
+ *                         scratch: fsw_embed_cart_generic_scratch_bytes(max_degree, num_rows) bytes.                         */
+typedef struct {
+  int32_t value_dtype;   /* 0 float32, 1 float64 (fsw_embed_cart_f32: 0) */
+  int32_t S;             /* slices (columns of Xp used) */
+  int32_t F;             /* frequencies */
+  int32_t has_mass;
+  const int32_t* rowptr;
+  const int32_t* col;
+  const void* w;         /* [nnz] raw weights, NULL = unit */
+  const int32_t* perm;
+  const int32_t* bin_start;
+  const int32_t* bin_start_host;   /* HOST copy of the FSW_NUM_BINS + 1 words of bin_start */
+  int64_t num_rows;
+  int64_t max_degree;    /* host value: an upper bound of the longest row */
+  const void* Xp;
+  int64_t ldp;
+  const void* freqs;     /* [F] */
+  double tau;
+  const float* unit_table;
+  int64_t ldt;
+  void* out;
+  int64_t ldo;
+  const void* bias;      /* NULL or [has_mass + S F] */
+  double out_scale;
+  int32_t mass_fn;
+  int32_t reserved;
+  double mass_scale;
+  const void* g;
+  int64_t ldg;
+  void* gkey;
+  int64_t ldk;
+  void* gfreq;
+  void* gw;
+  void* scratch;
+  size_t scratch_bytes;
+} fsw_cart_args;
+
+size_t fsw_embed_cart_generic_scratch_bytes(int64_t max_degree, int64_t num_rows);
+int fsw_embed_cart_generic(const fsw_cart_args* args, fsw_stream_t stream);
+int fsw_embed_cart_f32(const fsw_cart_args* args, fsw_stream_t stream);
 
 /* ---- stand-alone segmented cumulative sum --------------------------------------------------------
  * Replaces segcumsum / segcumsum_cuda (reference fsw_embedding.py:2795-3012): inclusive scan of

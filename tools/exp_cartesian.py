@@ -1,0 +1,76 @@
+"""Cartesian mode against the diagonal-expansion workaround on the BASELINE config-3 graph (1M nodes, 10M edges, d_in = 128), no_grad
+forward on a prebuilt graph:
+  (a) Cartesian S = F = 16 (256 output columns)
+  (b) the workaround: a diagonal module of 256 slices, projVecs repeated F times, freqs tiled S times (same output)
+  (c) the diagonal d_out = 256 headline module (256 distinct slices)
+For each: ms per forward, ms of the projection timed alone, and the rest of the forward (coefficient table, zero-degree rows, the
+one stats read, the neighbourhood kernel) with the neighbourhood kernel's algorithmic bytes as a fraction of 8 TB/s -- an upper-bound
+time, so a lower bound of the fraction.  Byte model of (a)'s kernel: gathers 4 E S + output 4 n S F (+ CSR indices 4 E); (b)/(c):
+gathers 4 E 256 + output 4 n 256 (+ 4 E).  The per-kernel split and the name of the dominant kernel come from a kernel trace of one
+configuration:
+    python tools/exp_cartesian.py [--reps 20] [--only a|b|c]
+    rocprofv3 --kernel-trace --stats -d DIR -o cart -- python tools/exp_cartesian.py --only a   (profiles/r04_cartesian_a_kernel_stats.csv)"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+from fsw_gnn_amd import FSW_embedding, _lib  # noqa: E402
+from fsw_gnn_amd.graph import build_csr  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--slices", type=int, default=16)
+ap.add_argument("--freqs", type=int, default=16)
+ap.add_argument("--only", default="abc", help="subset of the configurations a, b, c to time")
+args = ap.parse_args()
+dev = torch.device("cuda:0")
+n, E, d = bench.N_NODES, bench.N_EDGES, bench.D_FEAT
+S, F = args.slices, args.freqs
+x, ei = bench.make_inputs(n, E, dev)
+graph = build_csr(ei[1].contiguous(), ei[0].contiguous(), None, n, n)
+graph.read_stats()
+torch.manual_seed(7)
+cart = FSW_embedding(d_in=d, nSlices=S, nFreqs=F, collapse_freqs=True, enable_bias=False, device=dev)
+expd = FSW_embedding(d_in=d, d_out=S * F, enable_bias=False, device=dev)
+head = FSW_embedding(d_in=d, d_out=S * F, enable_bias=False, device=dev)
+with torch.no_grad():
+    expd.projVecs.copy_(cart.projVecs.repeat_interleave(F, dim=0))
+    expd.freqs.copy_(cart.freqs.repeat(S))
+out = torch.empty((n, S * F), device=dev)
+ref = torch.empty((n, S * F), device=dev)
+L = _lib.lib()
+stream = torch.cuda.current_stream(dev).cuda_stream
+
+
+def projection_ms(nslices, ldp):
+    Xp = torch.empty((n, ldp), device=dev)
+    V = torch.randn((nslices, d), device=dev)
+    return bench.timed_ms(lambda: _lib.check(L.fsw_project_f32(_lib.ptr(x), n, d, x.stride(0), _lib.ptr(V), nslices, d, _lib.ptr(Xp), ldp,
+                                                               None, 0, None, stream), "fsw_project_f32"), args.reps, dev)
+
+
+with torch.no_grad():
+    cart.embed_cartesian_into(x, graph, out)
+    if "b" in args.only:
+        expd.embed_into(x, graph, ref)
+        print("(a) vs (b): max difference %.2e of max |out|" % float((out - ref).abs().max() / ref.abs().max()))
+    rows = [
+        ("(a) Cartesian S=%d x F=%d" % (S, F), lambda: cart.embed_cartesian_into(x, graph, out), (S, (S + 31) // 32 * 32), S),
+        ("(b) diagonal expansion, %d slices" % (S * F), lambda: expd.embed_into(x, graph, ref), (S * F, (S * F + 63) // 64 * 64), S * F),
+        ("(c) diagonal d_out=%d headline" % (S * F), lambda: head.embed_into(x, graph, ref), (S * F, (S * F + 63) // 64 * 64), S * F),
+    ]
+    print("config 3: n=%d E=%d d_in=%d, max degree %d" % (n, E, d, graph.max_degree))
+    for name, fn, proj_shape, lines in rows:
+        if name[1] not in args.only:
+            continue
+        ms = bench.timed_ms(fn, args.reps, dev)
+        proj = projection_ms(*proj_shape)
+        kern = max(ms - proj, 1e-6)
+        gb = (4.0 * E * lines + 4.0 * n * S * F + 4.0 * E) / 1e9
+        print("%-36s %7.3f ms/forward  projection %6.3f ms  rest (neighbourhood kernel + table + stats read) %7.3f ms  %5.2f GB  "
+              ">= %5.0f GB/s = %.2f of 8 TB/s"
+              % (name, ms, proj, kern, gb, gb / kern * 1e3, gb / kern * 1e3 / bench.HBM_PEAK_GBS), flush=True)
