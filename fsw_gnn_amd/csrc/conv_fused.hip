@@ -91,12 +91,6 @@ struct FusedArgs {
   int Kp;
 };
 
-__device__ __forceinline__ float mass_encode_f(float m, int fn) {
-  if (fn == 1) return 2.f * (m / (sqrtf(m + 1.f) + 1.f));
-  if (fn == 2) return log1pf(m);
-  return m;
-}
-
 // phase 1 for one (degree, 64-slice chunk): embedding values of the block's rows into LDS (row_pipeline.h)
 // RPW = rows per wavefront.  1: lane = slice of one row (col indices wave-uniform, scalar loads).  2: a slice block of at most
 // 32 slices (one rank's share of a slice-sharded layer at 8 ranks x 256 slices, dist.py) -- lanes 0..31 and 32..63 work on two
@@ -211,7 +205,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) k_conv_fused_unit(const F
     for (int c = (r < nrows ? K : 0); c < a.ldh; ++c) H[r * a.ldh + c] = 0.f;
     nodeS[r] = r < nrows ? a.perm[p + r] : -1;
     if (a.has_mass && r < nrows)
-      H[r * a.ldh] = a.out_scale * (mass_encode_f((float)D, a.mass_fn) * a.mass_scale + (a.bias ? a.bias[0] : 0.f));
+      H[r * a.ldh] = mass_column((float)D, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
   }
   FSW_FSTAMP(0);                                           // tile found, H padding / node ids / mass column
   // phase 1: embedding rows

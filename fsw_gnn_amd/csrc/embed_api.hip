@@ -1,17 +1,5 @@
 // C-ABI entry points of the fused neighbourhood embed: argument checks and per-degree-class dispatch.
-#include "fsw_common.h"
-
-namespace fsw {
-int launch_unit_table(const float* freqs, int S, int max_deg, float* table, int64_t ldt, hipStream_t stream);
-int launch_zero_rows(const fsw_embed_args& a, hipStream_t stream);
-int launch_embed_reg(const fsw_embed_args& a, bool unit_fast, int64_t rows_upper, hipStream_t stream);
-int launch_embed_mid(const fsw_embed_args& a, bool unit_fast, int64_t rows_upper, hipStream_t stream);
-int launch_embed_lds(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);
-int launch_embed_hub(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);
-int launch_embed_giant(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);
-int launch_embed_global(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);
-size_t embed_global_scratch_bytes(int64_t max_degree);
-}  // namespace fsw
+#include "embed_launch.h"
 
 using namespace fsw;
 
@@ -48,15 +36,29 @@ extern "C" int fsw_embed_f32(const fsw_embed_args* args, fsw_stream_t stream_) {
   const int64_t nglob = a.num_global_rows < 0 ? a.num_rows : a.num_global_rows;
   int rc;
   if (nz > 0 && (rc = launch_zero_rows(a, stream))) return rc;
-  if (nreg > 0 && (rc = launch_embed_reg(a, unit_fast, nreg, stream))) return rc;
-  // num_lds_rows bounds the rows of FSW_REG_MAX_DEG < degree <= FSW_LDS_MAX_DEG: padded register path first, LDS path for the rest
-  if (nlds > 0 && (rc = launch_embed_mid(a, unit_fast, nlds, stream))) return rc;
-  if (nlds > 0 && (rc = launch_embed_lds(a, nlds, stream))) return rc;
-  if (nglob > 0) {   // rows above FSW_LDS_MAX_DEG: hub kernels (unit weights, up to FSW_HUB_MAX_DEG), scratch-line kernel for the rest
+  if (nreg > 0 && (rc = launch_embed_reg(a, unit_fast, nreg, stream))) return rc;                      // 1 .. FSW_REG_MAX_DEG = 32
+  if (nlds > 0) {   // num_lds_rows bounds the rows of FSW_REG_MAX_DEG < degree <= FSW_LDS_MAX_DEG = 2048
     if (unit_fast) {
-      if ((rc = launch_embed_hub(a, nglob, stream))) return rc;
-      if ((rc = launch_embed_giant(a, nglob, stream))) return rc;
-    } else if ((rc = launch_embed_global(a, nglob, stream))) {
+      if ((rc = launch_embed_mid_unit(a, nlds, stream))) return rc;                                    // 33 .. 256: one lane per slice
+      if ((rc = launch_embed_ws_unit(a, nlds, stream))) return rc;                                     // 257 .. 2048: lines in registers
+    } else {
+      if ((rc = launch_embed_mid_weighted(a, nlds, stream))) return rc;                                // 33 .. 128: one lane per slice
+      if (!a.efeat) {
+        if ((rc = launch_embed_hub_weighted_lds(a, nlds, stream))) return rc;                          // 129 .. 2048: (key, weight) lines in registers
+      } else if ((rc = launch_embed_wsort_lds(a, nlds, stream))) {                                     // 129 .. 2048: lines staged in LDS
+        return rc;
+      }
+    }
+  }
+  if (nglob > 0) {   // num_global_rows bounds the rows above FSW_LDS_MAX_DEG
+    if (unit_fast) {
+      if ((rc = launch_embed_hub(a, nglob, stream))) return rc;                                        // 2049 .. FSW_HUB_MAX_DEG = 32768
+      if ((rc = launch_embed_giant(a, nglob, stream))) return rc;                                      // above: sorted blocks + block sweeps
+    } else if (!a.efeat) {
+      if ((rc = launch_embed_hub_weighted_hub(a, nglob, stream))) return rc;                           // 2049 .. kHubWMaxDeg = 8191
+      // above (of bin FSW_BIN_HUB0 + 1 only its rows of exactly 8192 neighbours are left): sorted blocks + merge-path levels
+      if ((rc = launch_embed_mergepath_w(a, FSW_BIN_HUB0 + 1, FSW_BIN_GLOBAL, kHubWMaxDeg, nglob, stream))) return rc;
+    } else if ((rc = launch_embed_wsort_global(a, nglob, stream))) {                                   // one scratch line per wavefront
       return rc;
     }
   }

@@ -14,12 +14,11 @@
 // no-return global_atomic_add_f32 on 256 contiguous bytes of gXp[col_t] -- the full-rate shape for float atomics
 // on this part (atomics execute at the memory side, ~1.3 TB/s of added bytes chip-wide; this kernel is bound by that).
 // gX = gXp . V and gV = gXp^T . X are two plain GEMMs left to the BLAS.
-#include "fsw_common.h"
+#include "embed_launch.h"
 
 namespace fsw {
 
 constexpr int kBwdRows = 32;
-constexpr double kPiB = 3.14159265358979323846;
 
 // d/dxi [ (1 + xi) Delta_t ] for weights 1/D:  Delta = 2 w sinc(xi w) cos(B),  B = pi xi (2c - w)
 __global__ void __launch_bounds__(256) k_unit_dtable(const float* __restrict__ freqs, int S, int max_deg,
@@ -33,11 +32,11 @@ __global__ void __launch_bounds__(256) k_unit_dtable(const float* __restrict__ f
   const double xi = (double)freqs[k];
   const double w = 1.0 / D, c = (double)(t + 1) / D;
   const double z = xi * w;
-  const double sinc = (z == 0.0) ? 1.0 : sinpi(z) / (kPiB * z);
+  const double sinc = (z == 0.0) ? 1.0 : sinpi(z) / (kPi * z);
   const double dsinc = (z == 0.0) ? 0.0 : (cospi(z) - sinc) / z;
   const double B = xi * (2.0 * c - w);  // in units of pi
   const double delta = 2.0 * w * sinc * cospi(B);
-  const double ddelta = 2.0 * w * (w * dsinc * cospi(B) - sinc * kPiB * (2.0 * c - w) * sinpi(B));
+  const double ddelta = 2.0 * w * (w * dsinc * cospi(B) - sinc * kPi * (2.0 * c - w) * sinpi(B));
   dtable[(int64_t)row * ldt + k] = (float)(delta + (1.0 + xi) * ddelta);
 }
 
@@ -136,18 +135,18 @@ __global__ void __launch_bounds__(256) k_embed_reg_unit_bwd(const int32_t* __res
 // weight, which D(D+1)/2 compares give without sorting (cum[u] += w[t] when t sorts ahead of u).  Coefficient and
 // xi-derivative in float64 (the two terms of dF/dxi cancel from O(c/xi) to O(1)).
 __device__ __forceinline__ void F_dF(double xi, double c, double& F, double& dF) {
-  const double x = 2.0 * kPiB * xi * c;
+  const double x = 2.0 * kPi * xi * c;
   if (x < 1e-4) {
     const double q = 1.0 - x * x * (1.0 / 6.0);
     F = (1.0 + xi) * 2.0 * c * q;
-    dF = 2.0 * c * q - (1.0 + xi) * 2.0 * c * (2.0 * kPiB * c) * (2.0 * kPiB * c) * xi * (1.0 / 3.0);
+    dF = 2.0 * c * q - (1.0 + xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * xi * (1.0 / 3.0);
     return;
   }
   const double ph = xi * c;
   double s, co;
   sincospi(2.0 * (ph - rint(ph)), &s, &co);
-  F = (1.0 + xi) * s / (kPiB * xi);
-  dF = -s / (kPiB * xi * xi) + (1.0 + xi) * 2.0 * c * co / xi;
+  F = (1.0 + xi) * s / (kPi * xi);
+  dF = -s / (kPi * xi * xi) + (1.0 + xi) * 2.0 * c * co / xi;
 }
 
 template <int DEG>
@@ -236,9 +235,6 @@ __global__ void __launch_bounds__(256) k_embed_reg_weighted_bwd(const int32_t* _
       break;
   }
 }
-
-int launch_embed_long_bwd(const fsw_embed_args& a, bool global, int64_t rows_upper, const float* g, int64_t ldg, float* gXp,
-                          int64_t ldgp, float* gfreq, float* gkey, int64_t ldk, hipStream_t stream);
 
 }  // namespace fsw
 

@@ -25,19 +25,16 @@
 // with the per-frequency terms of embed_generic.hip:17-20 summed over f (the weight gradient is linear in H_t, so H is summed
 // over the frequencies first and the reverse cumulative sum runs once per slice).
 #include <algorithm>
-#include "fsw_common.h"
+#include "embed_launch.h"
 #include "sortnet.h"
 #include "wave_sort.h"
 
 namespace fsw {
 
-int launch_zero_rows(const fsw_embed_args& a, hipStream_t stream);   // embed_reg.hip
-
 namespace {
 
 constexpr int kCgThreads = 256;
 constexpr int kCgLdsElems = 2048;
-constexpr double kPiC = 3.14159265358979323846;
 constexpr int kCartScratchBytesPerElem = 8 + 4 + 8 + 8 + 8;   // key, index, cumulative weight, H / reverse sum, key gradient
 constexpr int kCartRows = 64;                                 // rows per workgroup tile of the register path
 constexpr int kCartMaxLine = 2048;                            // longest line of the wavefront path
@@ -71,12 +68,7 @@ struct CartGen {
   int64_t line_elems;
 };
 
-__device__ __forceinline__ double mass_encode_c(double m, int fn) {
-  if (fn == 1) return 2.0 * (m / (sqrt(m + 1.0) + 1.0));
-  if (fn == 2) return log1p(m);
-  return m;
-}
-__device__ __forceinline__ double sinc_c(double z) { return z == 0.0 ? 1.0 : sinpi(z) / (kPiC * z); }
+__device__ __forceinline__ double sinc_c(double z) { return z == 0.0 ? 1.0 : sinpi(z) / (kPi * z); }
 __device__ __forceinline__ double dsinc_c(double z) { return z == 0.0 ? 0.0 : (cospi(z) - sinc_c(z)) / z; }
 
 __device__ __forceinline__ double cg_block_sum(double v, double* red) {
@@ -107,9 +99,6 @@ __device__ __forceinline__ double cg_block_scan(double v, double* red, double* t
   *total = tot;
   return base + inc;
 }
-
-__device__ __forceinline__ void atomic_add_c(float* p, double v) { atomicAdd(p, (float)v); }
-__device__ __forceinline__ void atomic_add_c(double* p, double v) { atomicAdd(p, v); }
 
 // ---- generic kernel: one workgroup per row, slices in turn, frequencies per sorted slice -------------------------------------
 template <class T>
@@ -144,7 +133,7 @@ __global__ void __launch_bounds__(kCgThreads) k_embed_cart_generic(const CartGen
     const double invM = 1.0 / M;
     auto raw_weight = [&](int e) -> double { return e < D ? (a.w ? (double)a.w[start + e] : 1.0) : (e == D ? padw : 0.0); };
     if (!backward && a.has_mass && tid == 0)
-      a.out[row * a.ldo] = (T)(a.out_scale * (mass_encode_c(m, a.mass_fn) * a.mass_scale + (a.bias ? (double)a.bias[0] : 0.0)));
+      a.out[row * a.ldo] = (T)mass_column(m, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
     for (int s = 0; s < a.S; ++s) {
       for (int t = tid; t < Dp; t += kCgThreads) {
         double key = __builtin_inf();
@@ -202,7 +191,7 @@ __global__ void __launch_bounds__(kCgThreads) k_embed_cart_generic(const CartGen
           const double key = keys[t];
           acc += delta * key;
           if (backward) {
-            const double ddelta = 2.0 * wv * (wv * dsinc_c(xi * wv) * cb - sc * kPiC * (2.0 * c - wv) * sinpi(B));
+            const double ddelta = 2.0 * wv * (wv * dsinc_c(xi * wv) * cb - sc * kPi * (2.0 * c - wv) * sinpi(B));
             dacc += (delta + (1.0 + xi) * ddelta) * key;
             gks[t] += gk * (1.0 + xi) * delta;
             if (a.gw) {
@@ -216,7 +205,7 @@ __global__ void __launch_bounds__(kCgThreads) k_embed_cart_generic(const CartGen
           if (tid == 0) a.out[row * a.ldo + oc] = (T)(a.out_scale * ((1.0 + xi) * val + (a.bias ? (double)a.bias[oc] : 0.0)));
         } else if (a.gfreq) {
           const double dv = cg_block_sum(dacc, red);
-          if (tid == 0) atomic_add_c(&a.gfreq[f], gk * dv);
+          if (tid == 0) atomic_add_t(&a.gfreq[f], gk * dv);
         }
       }
       if (backward) {
@@ -250,7 +239,7 @@ __global__ void __launch_bounds__(kCgThreads) k_embed_cart_generic(const CartGen
           for (int t = tid; t < Dtot; t += kCgThreads) {
             const int e = idx[t];
             const double v = (hr[t] - corr) * invM;
-            if (e < D && v != 0.0) atomic_add_c(&a.gw[start + e], v);
+            if (e < D && v != 0.0) atomic_add_t(&a.gw[start + e], v);
           }
         }
       }
@@ -306,18 +295,6 @@ struct CartTuned {
   float mass_scale;
 };
 
-__device__ __forceinline__ float mass_encode_f(float m, int fn) {
-  if (fn == 1) return 2.f * (m / (sqrtf(m + 1.f) + 1.f));
-  if (fn == 2) return log1pf(m);
-  return m;
-}
-
-// sin(2 pi x), x in revolutions: reduced in float64, evaluated in float32 (as embed_reg.hip's weighted readout)
-__device__ __forceinline__ float sin2pi_c(double x) {
-  const double r = x - rint(x);
-  return sinpif(2.f * (float)r);
-}
-
 // Read-only inputs at wave-uniform addresses (coefficient table, frequencies) are read through the constant address space: the
 // compiler then issues scalar loads (s_load_dwordx4).  Through a generic pointer it must assume that the output stores may alias
 // them, and every coefficient becomes a vector-memory load next to the gathers.
@@ -367,7 +344,7 @@ __device__ __forceinline__ void cart_reg_unit(const CartTuned& a, int p, int pe)
       for (int t = 0; t < D; ++t) acc = fmaf(tab[(int64_t)t * a.ldt + f], net.k[t], acc);   // wave-uniform coefficient
       orow[c0 + f] = a.out_scale * acc;
     }
-    if (a.has_mass && s == 0) orow[0] = a.out_scale * (mass_encode_f((float)D, a.mass_fn) * a.mass_scale + (a.bias ? a.bias[0] : 0.f));
+    if (a.has_mass && s == 0) orow[0] = mass_column((float)D, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
   }
 }
 
@@ -414,16 +391,16 @@ __device__ __forceinline__ void cart_reg_weighted(const CartTuned& a, int p, int
         float acc = 0.f, sprev = 0.f;
 #pragma unroll
         for (int t = 0; t <= D; ++t) {
-          const float sn = sin2pi_c(xi * cn[t]);
+          const float sn = sin2pi_rev(xi * cn[t]);
           acc = fmaf(sn - sprev, net.k[t], acc);
           sprev = sn;
         }
-        val = (float)((1.0 + xi) / (kPiC * xi)) * acc;
+        val = (float)((1.0 + xi) / (kPi * xi)) * acc;
       }
       orow[c0 + f] = a.out_scale * (val + (a.bias ? a.bias[c0 + f] : 0.f));
     }
     if (a.has_mass && s == 0)
-      orow[0] = a.out_scale * (mass_encode_f((float)m, a.mass_fn) * a.mass_scale + (a.bias ? a.bias[0] : 0.f));
+      orow[0] = mass_column((float)m, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
   }
 }
 
@@ -525,7 +502,7 @@ __global__ void __launch_bounds__(64) k_cart_wave(const CartTuned a, int p0) {
       for (int t = q; t < L; t += Q) {
         const double c = WEIGHTED ? lc[t] : (double)(t + 1) * invD;
         const float dp = lk[t] - (t + 1 < L ? lk[t + 1] : 0.f);
-        const float term = lin ? (float)(2.0 * c) : sin2pi_c(xi * c);
+        const float term = lin ? (float)(2.0 * c) : sin2pi_rev(xi * c);
         acc = fmaf(term, dp, acc);
       }
     }
@@ -534,13 +511,13 @@ __global__ void __launch_bounds__(64) k_cart_wave(const CartTuned a, int p0) {
     if (lane < NF) {
       float sum = 0.f;
       for (int u = 0; u < Q; ++u) sum += red[lane + u * NF];
-      const float val = lin ? sum : (float)((1.0 + xi) / (kPiC * xi)) * sum;
+      const float val = lin ? sum : (float)((1.0 + xi) / (kPi * xi)) * sum;
       orow[c0 + f] = a.out_scale * (val + (a.bias ? a.bias[c0 + f] : 0.f));
     }
     __syncthreads();
   }
   if (a.has_mass && s == 0 && lane == 0)
-    orow[0] = a.out_scale * (mass_encode_f((float)m, a.mass_fn) * a.mass_scale + (a.bias ? a.bias[0] : 0.f));
+    orow[0] = mass_column((float)m, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
 }
 
 template <int M>

@@ -25,7 +25,6 @@ namespace fsw {
 
 constexpr int kGenThreads = 256;
 constexpr int kGenLdsElems = 2048;   // lines up to this many elements are sorted in LDS
-constexpr double kPiG = 3.14159265358979323846;
 
 template <class T>
 struct GenArgs {
@@ -60,12 +59,7 @@ struct GenArgs {
 };
 constexpr int kGenScratchBytesPerElem = 8 + 4 + 8 + 8;   // key, index, cumulative weight, H / reverse sum
 
-__device__ __forceinline__ double mass_encode_g(double m, int fn) {
-  if (fn == 1) return 2.0 * (m / (sqrt(m + 1.0) + 1.0));
-  if (fn == 2) return log1p(m);
-  return m;
-}
-__device__ __forceinline__ double sinc_g(double z) { return z == 0.0 ? 1.0 : sinpi(z) / (kPiG * z); }
+__device__ __forceinline__ double sinc_g(double z) { return z == 0.0 ? 1.0 : sinpi(z) / (kPi * z); }
 __device__ __forceinline__ double dsinc_g(double z) { return z == 0.0 ? 0.0 : (cospi(z) - sinc_g(z)) / z; }   // reference sp.dsinc :2760-2774
 
 // workgroup-wide sum of a double (all threads get the result)
@@ -99,9 +93,6 @@ __device__ __forceinline__ double block_inclusive_scan(double v, double* red /* 
   return base + inc;
 }
 
-__device__ __forceinline__ void atomic_add_t(float* p, double v) { atomicAdd(p, (float)v); }
-__device__ __forceinline__ void atomic_add_t(double* p, double v) { atomicAdd(p, v); }
-
 template <class T>
 __global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs<T> a) {
   __shared__ double lkey[kGenLdsElems];
@@ -132,7 +123,7 @@ __global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs<T> 
     const double invM = 1.0 / M;
     auto raw_weight = [&](int e) -> double { return e < D ? (a.w ? (double)a.w[start + e] : 1.0) : (e == D ? padw : 0.0); };
     if (!backward && a.has_mass && tid == 0)
-      a.out[row * a.ldo] = (T)(a.out_scale * (mass_encode_g(m, a.mass_fn) * a.mass_scale + (a.bias ? (double)a.bias[0] : 0.0)));
+      a.out[row * a.ldo] = (T)mass_column(m, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
     for (int k = 0; k < a.S; ++k) {
       // A. keys
       for (int t = tid; t < Dp; t += kGenThreads) {
@@ -194,7 +185,7 @@ __global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs<T> 
         const double key = keys[t];
         acc += delta * key;
         if (backward) {
-          const double ddelta = 2.0 * wv * (wv * dsinc_g(xi * wv) * cb - sc * kPiG * (2.0 * c - wv) * sinpi(B));
+          const double ddelta = 2.0 * wv * (wv * dsinc_g(xi * wv) * cb - sc * kPi * (2.0 * c - wv) * sinpi(B));
           dacc += (delta + (1.0 + xi) * ddelta) * key;
           if (e < D && a.gkey) a.gkey[(int64_t)(start + e) * a.ldk + k] = (T)(gk * (1.0 + xi) * delta);
           if (a.gw) {

@@ -17,30 +17,17 @@
 // Replaces, for these rows, the reference's global sort + sparse permutation + segmented cumsum (fsw_embedding.py:917-1032)
 // and the readout (:1047-1109).
 #include <algorithm>
-#include "fsw_common.h"
+#include "embed_launch.h"
 #include "sortnet.h"
 #include "wave_sort.h"
 #include "merge_path.h"
 
 namespace fsw {
 
-constexpr double kPiH = 3.14159265358979323846;
 [[maybe_unused]] constexpr int kHubM = 32;                  // keys per lane
 #ifndef FSW_HUB_ABL
 #define FSW_HUB_ABL 0   // timing experiments (tools/exp_hub.sh): 1 no gather, 2 no wave sort, 4 no cross-wave merge, 8 no readout
 #endif
-
-__device__ __forceinline__ float mass_encode_h(float m, int fn) {
-  if (fn == 1) return 2.f * (m / (sqrtf(m + 1.f) + 1.f));
-  if (fn == 2) return log1pf(m);
-  return m;
-}
-
-__device__ __forceinline__ float wave_sum_h(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // The instantiations are split over three translation units (FSW_HUB_PART = 0: unit weights, 1 / 2: general weights up to 2048 /
 // above; see the Makefile): the (key, weight) networks take minutes to compile.
@@ -149,20 +136,11 @@ __device__ __forceinline__ float hub_line(const int32_t* __restrict__ colrow, in
   gather_chunk<M>(ln, colrow, w * CAP, D, Xp, ldp, k, lane);
   if (!(FSW_HUB_ABL & 2)) ln.sort();
   if constexpr (NW > 1) workgroup_merge_levels<NW, M>(ln, xbuf, w, lane);
-  return wave_sum_h(unit_readout<M>(ln, w * CAP + lane * M, D, xif));
+  return wave_sum(unit_readout<M>(ln, w * CAP + lane * M, D, xif));
 }
 
 #ifndef FSW_HUB_MINWAVES
 #define FSW_HUB_MINWAVES 4   // waves per SIMD the hub kernels are compiled for (128 registers)
-#endif
-#ifndef FSW_ROWLINES_SPLIT
-#define FSW_ROWLINES_SPLIT 0
-#endif
-#ifndef FSW_HUB_ROWLINES
-#define FSW_HUB_ROWLINES 1   // 0: class 257..512 as one 64-lane line of 8 keys per lane (for comparison)
-#endif
-#ifndef FSW_HUB_SPLIT
-#define FSW_HUB_SPLIT 1   // 0: every line on the full class size (for comparison)
 #endif
 
 // NW wavefronts per line, M keys per lane; NW == 1: the workgroup is four independent wavefronts on four lines (adjacent
@@ -202,7 +180,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M > 32 ? 2 : FSW_H
     // second code path costs them registers (20..50 spilled), so they always run the full size.
     constexpr int MS = (M * 3) / 4;
     float tot;
-    if constexpr (FSW_HUB_SPLIT && NW == 1) {
+    if constexpr (NW == 1) {
       if (D <= kWave * MS) tot = hub_line<NW, MS>(col + start, D, Xp, ldp, k, freqs[k], xbuf, w, lane);
       else tot = hub_line<NW, M>(col + start, D, Xp, ldp, k, freqs[k], xbuf, w, lane);
     } else {
@@ -219,7 +197,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M > 32 ? 2 : FSW_H
     if (lane == 0 && w == 0) {
       float* orow = out + (int64_t)node * ldo;
       orow[has_mass + k] = out_scale * (tot + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_h((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      if (has_mass && k == 0) orow[0] = mass_column((float)D, mass_fn, mass_scale, bias, out_scale);
     }
   }
 }
@@ -324,7 +302,7 @@ __global__ void __launch_bounds__(NW* kWave, M > 32 ? 2 : FSW_HUB_MINWAVES) k_em
     }
     if (!(FSW_HUB_ABL & 2)) ln.sort();
     workgroup_merge_levels<NW, M>(ln, xbuf, w, lane);
-    float tot = wave_sum_h(unit_readout<M>(ln, w * CAP + lane * M, D, freqs[k0 + sl]));
+    float tot = wave_sum(unit_readout<M>(ln, w * CAP + lane * M, D, freqs[k0 + sl]));
     if (lane == 0) red[w] = tot;
     __syncthreads();
     tot = 0.f;
@@ -335,7 +313,7 @@ __global__ void __launch_bounds__(NW* kWave, M > 32 ? 2 : FSW_HUB_MINWAVES) k_em
       const int k = k0 + sl;
       float* orow = out + (int64_t)node * ldo;
       orow[has_mass + k] = out_scale * (tot + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_h((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
     }
   }
 }
@@ -352,7 +330,7 @@ __device__ __forceinline__ float hub_quad_line(const float* __restrict__ xline, 
 #pragma unroll
   for (int j = 0; j < M; ++j) ln.k[j] = xline[j * kWave + lane];     // striped: any arrangement will do, the line is sorted next
   if (!(FSW_HUB_ABL & 2)) ln.sort();
-  return wave_sum_h(unit_readout<M>(ln, lane * M, D, xif));
+  return wave_sum(unit_readout<M>(ln, lane * M, D, xif));
 }
 
 template <int M>
@@ -379,7 +357,7 @@ __global__ void __launch_bounds__(256, FSW_HUB_MINWAVES) k_embed_hub_quad(
     if (D < dmin || D > dmax) continue;
     const int32_t* colrow = col + start;
     const float* xr = Xp + k0;
-    const bool small = FSW_HUB_SPLIT && D <= kWave * MS;      // a line of at most 3/4 of the class size: 3/4 of the keys per lane
+    const bool small = D <= kWave * MS;      // a line of at most 3/4 of the class size: 3/4 of the keys per lane
     const int nq = small ? MS / 4 : M / 4;
     static_assert(M % 16 == 0, "3/4 of the keys per lane must still be a multiple of 4");
     int c[M / 4];
@@ -410,7 +388,7 @@ __global__ void __launch_bounds__(256, FSW_HUB_MINWAVES) k_embed_hub_quad(
       const int k = k0 + w;
       float* orow = out + (int64_t)node * ldo;
       orow[has_mass + k] = out_scale * (tot + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_h((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      if (has_mass && k == 0) orow[0] = mass_column((float)D, mass_fn, mass_scale, bias, out_scale);
     }
   }
 }
@@ -525,7 +503,7 @@ __global__ void __launch_bounds__(kGiantNW* kWave, 4) k_embed_giant(const int32_
       }
       sync_scratch();
     }
-    acc = wave_sum_h(acc);
+    acc = wave_sum(acc);
     if (lane == 0) red[w] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -534,20 +512,14 @@ __global__ void __launch_bounds__(kGiantNW* kWave, 4) k_embed_giant(const int32_
       for (int q = 0; q < NW; ++q) tot += red[q];
       float* orow = out + (int64_t)node * ldo;
       orow[has_mass + k] = out_scale * (tot + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_h((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      if (has_mass && k == 0) orow[0] = mass_column((float)D, mass_fn, mass_scale, bias, out_scale);
     }
     __syncthreads();
   }
 }
 
 // unit weights, tau <= 1: the rows above FSW_HUB_MAX_DEG.  scratch: fsw_embed_scratch_bytes(max_degree).
-int launch_embed_mergepath(const fsw_embed_args& a, int bin_lo, int bin_hi, int dlo, int64_t rows_upper, hipStream_t stream);
 int launch_embed_giant(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
-  // FSW_GIANT_MERGEPATH=1: sorted blocks of 8192 + merge-path levels (k_embed_mergepath) instead of the block sweeps below.  Measured
-  // on the 64M-edge RMAT graph's 23 rows above 32768 neighbours: 6.33 ms against 6.07 ms here -- for bare keys the sweeps are cheap
-  // (one v_min / v_max per element) and a merge-path tile is a chain of dependent LDS reads at two wavefronts per SIMD; with a
-  // payload it is the other way round (k_embed_mergepath_w: 11.6 ms against 61.6 ms for the scratch-line kernel)
-  if (getenv("FSW_GIANT_MERGEPATH")) return launch_embed_mergepath(a, FSW_BIN_GLOBAL, FSW_BIN_GLOBAL, FSW_HUB_MAX_DEG, rows_upper, stream);
   rows_upper = bin_rows_or(a, FSW_BIN_GLOBAL, FSW_BIN_GLOBAL, rows_upper);
   if (rows_upper <= 0 || (a.max_degree > 0 && a.max_degree <= FSW_HUB_MAX_DEG)) return 0;
   FSW_REQUIRE(a.max_degree > FSW_HUB_MAX_DEG, "fsw_embed_f32: max_degree (host value) is required for rows above FSW_HUB_MAX_DEG");
@@ -561,102 +533,6 @@ int launch_embed_giant(const fsw_embed_args& a, int64_t rows_upper, hipStream_t 
   k_embed_giant<<<(unsigned)nwg, kGiantNW * kWave, 0, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, a.Xp, a.ldp, a.S, a.freqs, a.out, a.ldo,
                                                                 a.bias, a.out_scale, a.has_mass, a.mass_fn, a.mass_scale,
                                                                 reinterpret_cast<float*>(a.scratch), line_floats);
-  FSW_LAUNCH_CHECK();
-  return 0;
-}
-
-
-// ---- rows above FSW_HUB_MAX_DEG, unit weights: sorted blocks of 8192 keys + merge-path levels (merge_path.h) -------------------
-// Phase A is k_embed_hub<4, 32>'s line (four wavefronts x 32 keys per lane, sorted in registers, two bitonic levels through LDS)
-// for every block of 8192 neighbours, parked in the workgroup's scratch line; the levels above are one merge-path pass each, the
-// last one straight into the readout.  A 150 000-neighbour hub: 19 blocks, 5 passes (k_embed_giant: 10 blocks of 16384, 14 passes).
-struct MpKeys {
-  float k[kMpVT];
-};
-
-__global__ void __launch_bounds__(kMpNT, 2) k_embed_mergepath(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                            const int32_t* __restrict__ perm, const int32_t* __restrict__ bin_start,
-                                                            int bin_lo, int bin_hi, int dlo, const float* __restrict__ Xp, int64_t ldp,
-                                                            int S, const float* __restrict__ freqs, float* __restrict__ out, int64_t ldo,
-                                                            const float* __restrict__ bias, float out_scale, int has_mass, int mass_fn,
-                                                            float mass_scale, float* __restrict__ scratch, int64_t line_cap) {
-  constexpr int NW = 4, M = 32, CAP = M * kWave;
-  static_assert(NW * CAP == kMpBlk, "block = one workgroup's registers");
-  extern __shared__ __attribute__((aligned(16))) float xsm[];   // phase A: exchange buffer [NW][CAP]; levels: tile keys | tile boundaries
-  __shared__ float red[NW];
-  float* tk = xsm;
-  int* part = reinterpret_cast<int*>(xsm + kMpTileLds);
-  const int pbeg = bin_start[bin_lo], nrows = bin_start[bin_hi + 1] - pbeg;
-  const int lane = lane_id(), w = wave_id();
-  const int blk = (gridDim.x & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
-  float* k0 = scratch + (int64_t)blk * 2 * line_cap;
-  float* k1 = k0 + line_cap;
-  const int64_t nlines = (int64_t)nrows * S;
-  for (int64_t line = blk; line < nlines; line += gridDim.x) {
-    const int p = pbeg + (int)(line / S), k = (int)(line % S);
-    const int node = perm[p];
-    const int start = rowptr[node];
-    const int D = rowptr[node + 1] - start;
-    if (D <= dlo) continue;
-    const int nb = (D + kMpBlk - 1) / kMpBlk;
-    const float xif = freqs[k];
-    float acc = 0.f;
-    WaveLine<M, false> ln;
-#pragma unroll 1
-    for (int b = 0; b < nb; ++b) {
-      gather_chunk<M>(ln, col + start, b * kMpBlk + w * CAP, D, Xp, ldp, k, lane);
-      ln.sort();
-      workgroup_merge_levels<NW, M>(ln, xsm, w, lane);
-      if (nb == 1) break;                                  // the whole line is in registers
-      float* dst = k0 + (int64_t)b * kMpBlk + w * CAP + lane * M;
-#pragma unroll
-      for (int j = 0; j < M; j += 4) *reinterpret_cast<float4*>(dst + j) = make_float4(ln.k[j], ln.k[j + 1], ln.k[j + 2], ln.k[j + 3]);
-    }
-    if (nb == 1) {
-      acc = unit_readout<M>(ln, w * CAP + lane * M, D, xif);
-    } else {
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      __syncthreads();
-      MpStamps st{};
-      merge_path_levels<false>(k0, k1, nullptr, nullptr, nb, tk, nullptr, part, [&](int r0, const float* ok, const float*) {
-        MpKeys t;
-#pragma unroll
-        for (int j = 0; j < kMpVT; ++j) t.k[j] = ok[j];
-        acc += unit_readout<kMpVT>(t, r0, D, xif);
-      }, st);
-    }
-    acc = wave_sum_h(acc);
-    if (lane == 0) red[w] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float tot = 0.f;
-#pragma unroll
-      for (int q = 0; q < NW; ++q) tot += red[q];
-      float* orow = out + (int64_t)node * ldo;
-      orow[has_mass + k] = out_scale * (tot + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_h((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
-    }
-    __syncthreads();
-  }
-}
-
-// unit weights, tau <= 1: rows of the bins bin_lo .. bin_hi with more than dlo neighbours.  scratch: fsw_embed_scratch_bytes(max_degree).
-int launch_embed_mergepath(const fsw_embed_args& a, int bin_lo, int bin_hi, int dlo, int64_t rows_upper, hipStream_t stream) {
-  rows_upper = bin_rows_or(a, bin_lo, bin_hi, rows_upper);
-  if (rows_upper <= 0 || (a.max_degree > 0 && a.max_degree <= dlo)) return 0;
-  FSW_REQUIRE(a.max_degree > dlo, "fsw_embed_f32: max_degree (host value) is required for rows above FSW_LDS_MAX_DEG");
-  FSW_REQUIRE(a.scratch, "fsw_embed_f32: these rows need a scratch buffer (fsw_embed_scratch_bytes)");
-  FSW_REQUIRE(((uintptr_t)a.scratch & 15) == 0, "fsw_embed_f32: scratch must be 16-byte aligned");
-  const int64_t line_cap = ceil_div(a.max_degree, kMpBlk) * kMpBlk;
-  int64_t nwg = std::min<int64_t>((int64_t)(a.scratch_bytes / (size_t)(2 * line_cap * 4)), 512);   // two workgroups per CU
-  nwg = std::min<int64_t>(nwg, ceil_div(rows_upper * a.S, 8) * 8);
-  if (nwg >= 8) nwg &= ~(int64_t)7;
-  FSW_REQUIRE(nwg >= 1, "fsw_embed_f32: scratch buffer too small for rows above FSW_HUB_MAX_DEG (need fsw_embed_scratch_bytes(max_degree))");
-  const size_t lds = sizeof(float) * 4 * 32 * kWave;      // phase A's exchange buffer; the tile + boundaries of the levels fit inside
-  static_assert(sizeof(float) * kMpTileLds + sizeof(int) * (kMpParts + 1) <= sizeof(float) * 4 * 32 * kWave, "LDS of the merge levels");
-  k_embed_mergepath<<<(unsigned)nwg, kMpNT, lds, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, bin_lo, bin_hi, dlo, a.Xp, a.ldp, a.S, a.freqs,
-                                                          a.out, a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn, a.mass_scale,
-                                                          reinterpret_cast<float*>(a.scratch), line_cap);
   FSW_LAUNCH_CHECK();
   return 0;
 }
@@ -679,10 +555,7 @@ static int launch_hub(const fsw_embed_args& a, int bin, int64_t rows_upper, hipS
       return 0;
     }
   }
-#ifndef FSW_HUB_Q4_MAXNW
-#define FSW_HUB_Q4_MAXNW 2   // widest line (wavefronts) that takes the 16-byte gather + stash form
-#endif
-  if constexpr (NW >= 2 && NW <= FSW_HUB_Q4_MAXNW) {
+  if constexpr (NW == 2) {
     // 2049..4096 neighbours only: measured on the RMAT graphs 0.41 -> 0.36 ms (scale 20) for two wavefronts per line, but 10.2 -> 12.8 ms
     // (scale 22, 4097..8192) and no change (8193..16384) for four and eight -- there the barrier-separated exchanges between the
     // wavefronts bound the kernel, not the gather, and the stash traffic is pure cost.
@@ -714,20 +587,17 @@ template <int NW>
 static int launch_hub_pair(const fsw_embed_args& a, int bin, int64_t rows_upper, hipStream_t stream) {
   constexpr int kSmall = NW * kWave * 24;
   int rc;
-  if (FSW_HUB_SPLIT && (rc = launch_hub<NW, 24>(a, bin, rows_upper, stream, 0, kSmall))) return rc;
-  return launch_hub<NW, kHubM>(a, bin, rows_upper, stream, FSW_HUB_SPLIT ? kSmall + 1 : 0, 0x7fffffff);
+  if ((rc = launch_hub<NW, 24>(a, bin, rows_upper, stream, 0, kSmall))) return rc;
+  return launch_hub<NW, kHubM>(a, bin, rows_upper, stream, kSmall + 1, 0x7fffffff);
 }
 
-
-// ---- 129..512 neighbours: SEVERAL lines per wavefront, LL lanes x M keys each ---------------------------------------------------
+// ---- 257..512 neighbours: SEVERAL lines per wavefront, LL lanes x M keys each ---------------------------------------------------
 // With LL <= 16 lanes per line every cross-lane exchange of the merge levels is one DPP move inside a row of 16 lanes, and more of
 // the network runs inside a lane (one instruction per key and comparator instead of two).  The 64 / LL lines of a wavefront are
 // adjacent slices of one row, so a gather instruction reads 64 / LL consecutive floats from each of LL rows of Xp.
 //   LL = 16, M = 32  : 257..512 neighbours (four lines per wavefront; a 64-lane line of 8 keys per lane ran 11.5 ms against 9.7)
-//   LL = 4, M = 48/64: 129..256 neighbours (16 lines per wavefront).  These rows used to run lane = slice with the whole row in one
-//                      lane's registers (embed_mid.hip: 160..256 keys -> one wave per SIMD, which can issue a vector instruction
-//                      only every 4 cycles and has nothing to overlap its gather with); split over four lanes the line takes
-//                      48..64 registers per lane and 3..4 waves per SIMD cover each other's gathers.
+// (LL = 4, M = 48 / 64 for 129..256 neighbours, 16 lines per wavefront, measured slower than one lane per slice -- embed_mid.hip --
+// and was removed: DESIGN.md section 5.)
 // 4 x 4 transpose across the four rows of 16 lanes: lane (s, j) holds v[c] = slice c of ITS element and receives v[c] = slice s of
 // the element of lane (c, j).  Two v_permlane32_swap (rows {0,1} <-> {2,3}) and two v_permlane16_swap (even <-> odd rows): one
 // instruction per key, no LDS crossbar.
@@ -836,165 +706,29 @@ __global__ void __launch_bounds__(256, M <= 32 ? 4 : M <= 64 ? 3 : 2) k_embed_ro
     if (sub == 0) {
       float* orow = out + (int64_t)node * ldo;
       orow[has_mass + k] = out_scale * (tot + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_h((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      if (has_mass && k == 0) orow[0] = mass_column((float)D, mass_fn, mass_scale, bias, out_scale);
     }
   }
 }
 
-template <int M, int LL>
-static int launch_rowlines_one(const fsw_embed_args& a, int bin, int64_t rows_upper, hipStream_t stream, int dmin, int dmax) {
-  constexpr int LPB = 4 * (kWave / LL);
+// unit weights, class 257..512: four lines of 16 lanes x 32 keys per wavefront.  (Rows of at most 384 neighbours on 24 keys per lane
+// as a launch of their own were measured and removed: on a graph whose class sits near its upper end -- the 64M-edge RMAT graph, fill
+// 0.93 -- the extra pass over the bin cost 0.8 ms and found nothing.)
+static int launch_rowlines(const fsw_embed_args& a, int bin, int64_t rows_upper, hipStream_t stream) {
+  constexpr int M = 32, LL = 16, LPB = 4 * (kWave / LL);
   rows_upper = bin_rows_or(a, bin, bin, rows_upper);
   if (rows_upper <= 0) return 0;
   const int64_t nvirtual = ceil_div(ceil_div(rows_upper, 8) * a.S, LPB) * 8;
   const int64_t nblocks = std::min<int64_t>(nvirtual, 1ll << 20);
   // 16-byte gathers: the four lines of a wavefront must be four slices of one row starting at a multiple of 4
-  const bool vec4 = LL == 16 && a.S % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)a.Xp & 15) == 0;
-  if constexpr (LL == 16) {
-    if (vec4) {
-      k_embed_rowlines<M, LL, true><<<(unsigned)nblocks, 256, 0, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, bin, a.Xp, a.ldp, a.S,
-                                                                          a.freqs, a.out, a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn,
-                                                                          a.mass_scale, dmin, dmax);
-      FSW_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  k_embed_rowlines<M, LL><<<(unsigned)nblocks, 256, 0, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, bin, a.Xp, a.ldp, a.S, a.freqs, a.out,
-                                                                a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn, a.mass_scale, dmin, dmax);
+  if (a.S % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)a.Xp & 15) == 0)
+    k_embed_rowlines<M, LL, true><<<(unsigned)nblocks, 256, 0, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, bin, a.Xp, a.ldp, a.S, a.freqs,
+                                                                        a.out, a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn, a.mass_scale,
+                                                                        0, 0x7fffffff);
+  else
+    k_embed_rowlines<M, LL><<<(unsigned)nblocks, 256, 0, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, bin, a.Xp, a.ldp, a.S, a.freqs, a.out,
+                                                                  a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn, a.mass_scale, 0, 0x7fffffff);
   FSW_LAUNCH_CHECK();
-  return 0;
-}
-
-static int launch_rowlines(const fsw_embed_args& a, int bin, int64_t rows_upper, hipStream_t stream) {
-  // rows of at most 384 neighbours on 24 keys per lane: off by default -- on a graph whose class sits near its upper end (the 64M-edge
-  // RMAT graph: fill 0.93) the extra pass over the bin costs 0.8 ms and finds nothing
-  constexpr int kSmall = 16 * 24;
-  constexpr bool kSplit = FSW_HUB_SPLIT && FSW_ROWLINES_SPLIT;
-  int rc;
-  if (kSplit && (rc = launch_rowlines_one<24, 16>(a, bin, rows_upper, stream, 0, kSmall))) return rc;
-  return launch_rowlines_one<32, 16>(a, bin, rows_upper, stream, kSplit ? kSmall + 1 : 0, 0x7fffffff);
-}
-
-// ---- 129..256 neighbours, whole-row gathers through LDS ------------------------------------------------------------------------------
-// A workgroup of four wavefronts takes (row, chunk of 64 slices).  The neighbours' 256-byte runs Xp[col, k0 .. k0 + 63] -- the
-// access shape that reads HBM best -- go STRAIGHT into LDS (global_load_lds_dword: no register destination, row t of the tile =
-// neighbour t, 64 slices), and they are issued for the NEXT row of the workgroup before the current row is sorted, so the gather runs
-// under the sort.  The 64 lines of the tile are then read transposed, 4 lanes x DP / 4 keys per line (WaveLine<DP / 4, .., 4>: every
-// exchange of the merge levels a DPP move), 16 lines per wavefront; row stride 72 floats makes both the DMA writes (64 consecutive
-// floats) and the transposed reads (bank = 8 sub + line) conflict-free.  Against one lane per slice with the whole row in its
-// registers (embed_mid.hip: one or two waves per SIMD, nothing to overlap the gather with) the line takes a quarter of the registers.
-constexpr int kMidLdsStride = 72;
-
-template <int DP>   // padded line: 192 or 256 keys
-__global__ void __launch_bounds__(256, 2) k_embed_mid_lds(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                          const int32_t* __restrict__ perm, const int32_t* __restrict__ bin_start, int bin,
-                                                          const float* __restrict__ Xp, int64_t ldp, int S, const float* __restrict__ freqs,
-                                                          float* __restrict__ out, int64_t ldo, const float* __restrict__ bias,
-                                                          float out_scale, int has_mass, int mass_fn, float mass_scale) {
-  constexpr int M = DP / 4, LL = 4;
-  __shared__ float xs[DP * kMidLdsStride];
-  const int lane = lane_id(), w = wave_id();
-  const int sub = lane & (LL - 1), line = lane >> 2;
-  const int k0 = blockIdx.y * kWave;                       // first slice of the chunk
-  const int kl = min(k0 + lane, S - 1);                    // the slice this lane GATHERS (past the end: slice S - 1 again)
-  const int ks = min(k0 + w * 16 + line, S - 1);           // the slice this lane SORTS
-  const bool ks_ok = k0 + w * 16 + line < S;
-  const float xif = freqs[ks];
-  const int pbeg = bin_start[bin], pend = bin_start[bin + 1];
-  // this wavefront gathers neighbours t = w, w + 4, ...: lane i holds the column index of its i-th neighbour (one load per row)
-  auto load_cols = [&](int p, int& D) {
-    int c = 0;
-    D = 0;
-    if (p < pend) {
-      const int node = perm[p];
-      const int start = rowptr[node];
-      D = rowptr[node + 1] - start;
-      const int t = w + 4 * lane;
-      c = col[start + min(t, D - 1)];
-    }
-    return c;
-  };
-  auto issue_gather = [&](int c, int D) {                  // D wave-uniform; neighbours past the end are not loaded (masked at the read)
-    const int mine = (D - w + 3) >> 2;                     // this wavefront's neighbours
-#pragma unroll 8
-    for (int i = 0; i < DP / 4; ++i) {
-      if (i < mine) {                                      // uniform
-        const int ci = __builtin_amdgcn_readlane(c, i);
-        const float* src = Xp + (int64_t)ci * ldp + kl;
-        __builtin_amdgcn_global_load_lds(src, xs + (w + 4 * i) * kMidLdsStride, 4, 0, 0);
-      }
-    }
-  };
-  int p = pbeg + blockIdx.x;
-  int Dn;
-  int cn = load_cols(p, Dn);
-  if (p < pend) issue_gather(cn, Dn);
-  int D = Dn;
-  int node = p < pend ? perm[p] : 0;
-  cn = load_cols(p + gridDim.x, Dn);
-  for (; p < pend; p += gridDim.x) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wavefront's DMAs of row p (and the column indices of the next row)
-    __syncthreads();                                       // ... and everybody else's
-    WaveLine<M, false, false, LL> ln;
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      const int t = i * LL + sub;
-      const float v = xs[t * kMidLdsStride + w * 16 + line];
-      ln.k[i] = t < D ? v : __builtin_inff();
-    }
-    __syncthreads();                                       // the tile has been read: the next row may land in it
-    const int pn = p + gridDim.x;
-    const int Dcur = D, nodecur = node;
-    if (pn < pend) {
-      issue_gather(cn, Dn);
-      D = Dn;
-      node = perm[pn];
-    }
-    cn = load_cols(pn + gridDim.x, Dn);
-    ln.sort();
-    float tot = unit_readout<M>(ln, sub * M, Dcur, xif);
-    tot += xor_lane<2>(tot);
-    tot += xor_lane<1>(tot);
-    if (sub == 0 && ks_ok) {
-      float* orow = out + (int64_t)nodecur * ldo;
-      orow[has_mass + ks] = out_scale * (tot + (bias ? bias[has_mass + ks] : 0.f));
-      if (has_mass && ks == 0) orow[0] = out_scale * (mass_encode_h((float)Dcur, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
-    }
-  }
-}
-
-int launch_embed_mid_lds(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
-  constexpr int sizes[FSW_NUM_MID_BINS] = FSW_MID_SIZES;
-  for (int i = 0; i < FSW_NUM_MID_BINS; ++i) {
-    if (sizes[i] <= 128) continue;
-    const int64_t rows = bin_rows_or(a, FSW_BIN_MID0 + i, FSW_BIN_MID0 + i, rows_upper);
-    if (rows <= 0) continue;
-    dim3 grid((unsigned)std::min<int64_t>(rows, 256), (unsigned)ceil_div(a.S, kWave));
-    if (sizes[i] <= 192)
-      k_embed_mid_lds<192><<<grid, 256, 0, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, FSW_BIN_MID0 + i, a.Xp, a.ldp, a.S, a.freqs, a.out,
-                                                     a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn, a.mass_scale);
-    else
-      k_embed_mid_lds<256><<<grid, 256, 0, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, FSW_BIN_MID0 + i, a.Xp, a.ldp, a.S, a.freqs, a.out,
-                                                     a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn, a.mass_scale);
-    FSW_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// unit weights, mid bins of 129..256 neighbours (FSW_MID_SIZES 160 / 192 / 256): lines of 192 and 256 keys over LL lanes
-#ifndef FSW_MIDSPLIT_LL
-#define FSW_MIDSPLIT_LL 4
-#endif
-int launch_embed_mid_split(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
-  constexpr int LL = FSW_MIDSPLIT_LL;
-  constexpr int sizes[FSW_NUM_MID_BINS] = FSW_MID_SIZES;
-  int rc;
-  for (int i = 0; i < FSW_NUM_MID_BINS; ++i) {
-    if (sizes[i] <= 128) continue;
-    if (sizes[i] <= 192) rc = launch_rowlines_one<192 / LL, LL>(a, FSW_BIN_MID0 + i, rows_upper, stream, 0, 0x7fffffff);
-    else rc = launch_rowlines_one<256 / LL, LL>(a, FSW_BIN_MID0 + i, rows_upper, stream, 0, 0x7fffffff);
-    if (rc) return rc;
-  }
   return 0;
 }
 
@@ -1006,20 +740,6 @@ int launch_embed_mid_split(const fsw_embed_args& a, int64_t rows_upper, hipStrea
 // and the reference's pad element (key 0, weight max(tau - m, 0), fsw_embedding.py:1000-1017), so a class runs one size up from
 // the unit kernels.  Readout as in k_embed_wsort: float64 cumulative weight (lane sum -> wave scan -> wavefront offsets), phase
 // reduced in float64, sine in float32, coefficient = difference of consecutive sines.
-__device__ __forceinline__ double wave_exclusive_scan_f64_h(double v, int lane) {
-  double inc = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const double t = __shfl_up(inc, off);
-    if (lane >= off) inc += t;
-  }
-  return inc - v;
-}
-
-__device__ __forceinline__ float sin2pi_rev_h(double x) {
-  const double r = x - rint(x);
-  return sinpif(2.f * (float)r);
-}
 
 template <int M>
 __device__ __forceinline__ void wave_exchange_w(WaveLine<M, true>& ln, float* __restrict__ xk, float* __restrict__ xw, int w, int lane,
@@ -1131,7 +851,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k
     double lsum = 0.0;
 #pragma unroll
     for (int j = 0; j < M; ++j) lsum += (double)ln.w[j];
-    double cw = wave_exclusive_scan_f64_h(lsum, lane);
+    double cw = wave_exclusive_scan_f64(lsum);
     if constexpr (NW > 1) {
       const double wtot = __shfl(cw + lsum, kWave - 1);      // this wavefront's total
       if (lane == 0) redd[w] = wtot;
@@ -1142,7 +862,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k
       __syncthreads();
     }
     float acc = 0.f;
-    float sprev = lin ? 0.f : sin2pi_rev_h(xi * (cw * inv));
+    float sprev = lin ? 0.f : sin2pi_rev(xi * (cw * inv));
     const int r0 = w * CAP + lane * M;
 #pragma unroll
     for (int j = 0; j < M; ++j) {
@@ -1151,13 +871,13 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k
       if (lin) {
         acc += valid ? ln.w[j] * ln.k[j] : 0.f;
       } else {
-        const float sn = sin2pi_rev_h(xi * (cw * inv));
+        const float sn = sin2pi_rev(xi * (cw * inv));
         acc += valid ? (sn - sprev) * ln.k[j] : 0.f;
         sprev = sn;
       }
     }
-    acc *= lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPiH * xi));
-    float tot = wave_sum_h(acc);
+    acc *= lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPi * xi));
+    float tot = wave_sum(acc);
     if constexpr (NW > 1) {
       if (lane == 0) red[w] = tot;
       __syncthreads();
@@ -1169,7 +889,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k
     if (lane == 0 && w == 0) {
       float* orow = out + (int64_t)node * ldo;
       orow[has_mass + k] = out_scale * (tot + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_h((float)m, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      if (has_mass && k == 0) orow[0] = mass_column((float)m, mass_fn, mass_scale, bias, out_scale);
     }
   }
 }
@@ -1194,7 +914,6 @@ static int launch_hub_w(const fsw_embed_args& a, int bin_lo, int bin_hi, int64_t
   return 0;
 }
 
-
 #if FSW_HUB_PART == 2
 #if FSW_MP_STAMPS
 __device__ unsigned long long g_mp_stamps[512][4][16];   // [workgroup][wavefront][phase]: s_memtime ticks; [..][15]: lines
@@ -1214,7 +933,7 @@ __device__ __forceinline__ float weighted_readout(const float* __restrict__ kk, 
   double lsum = 0.0;
 #pragma unroll
   for (int j = 0; j < N; ++j) lsum += (double)ww[j];
-  double cw = wave_exclusive_scan_f64_h(lsum, lane);
+  double cw = wave_exclusive_scan_f64(lsum);
   const double wtot = __shfl(cw + lsum, kWave - 1);
   if (lane == 0) redd[w] = wtot;
   __syncthreads();
@@ -1228,7 +947,7 @@ __device__ __forceinline__ float weighted_readout(const float* __restrict__ kk, 
   cw += carry;
   carry += tot;
   float acc = 0.f;
-  float sprev = lin ? 0.f : sin2pi_rev_h(xi * (cw * inv));
+  float sprev = lin ? 0.f : sin2pi_rev(xi * (cw * inv));
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     const bool valid = r0 + j < Dtot;
@@ -1236,7 +955,7 @@ __device__ __forceinline__ float weighted_readout(const float* __restrict__ kk, 
     if (lin) {
       acc += valid ? ww[j] * kk[j] : 0.f;
     } else {
-      const float sn = sin2pi_rev_h(xi * (cw * inv));
+      const float sn = sin2pi_rev(xi * (cw * inv));
       acc += valid ? (sn - sprev) * kk[j] : 0.f;
       sprev = sn;
     }
@@ -1350,8 +1069,8 @@ __global__ void __launch_bounds__(kMpNT, 2) k_embed_mergepath_w(
         acc += weighted_readout<kMpVT>(ok, ow, r0, Dtot, xi, inv, lin, carry, redd, w, lane);
       }, st);
     }
-    acc *= lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPiH * xi));
-    acc = wave_sum_h(acc);
+    acc *= lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPi * xi));
+    acc = wave_sum(acc);
     if (lane == 0) red[w] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1360,7 +1079,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_embed_mergepath_w(
       for (int q = 0; q < NW; ++q) tot += red[q];
       float* orow = out + (int64_t)node * ldo;
       orow[has_mass + k] = out_scale * (tot + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_h((float)m, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      if (has_mass && k == 0) orow[0] = mass_column((float)m, mass_fn, mass_scale, bias, out_scale);
     }
     __syncthreads();
     FSW_MP_MARK(st, 10);                                   // workgroup sum + store
@@ -1413,21 +1132,19 @@ namespace fsw {
 #define FSW_HW(NW, M, LO, HI, DLO, DHI) \
   if ((rc = launch_hub_w<NW, M>(a, LO, HI, rows_upper, stream, DLO, DHI))) return rc
 #if FSW_HUB_PART == 1
-// general weights without edge features: rows of FSW_MID_MAX_DEG_WEIGHTED < degree <= 4096 (bins bin_lo .. FSW_BIN_HUB0).
-// bin_lo: the first mid bin above FSW_MID_MAX_DEG_WEIGHTED.  lds_rows / hub_rows bound the rows of the two ranges.
-int launch_embed_hub_weighted_lds(const fsw_embed_args& a, int bin_lo, int64_t rows_upper, hipStream_t stream) {
+// general weights without edge features: rows of FSW_MID_MAX_DEG_WEIGHTED < degree <= FSW_LDS_MAX_DEG (the mid bins ..160, ..192,
+// ..256 and the LDS bins).  Below 129 neighbours the per-lane (key, weight) network of embed_mid.hip is faster (measured with the
+// hand-over at 33 and 65: DESIGN.md).  rows_upper bounds the rows of the range.
+int launch_embed_hub_weighted_lds(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
   // A line holds D + 1 elements, and a bitonic line costs its CAPACITY, not its fill: every bin is split over the capacities
   // 64 * {3, 4, 6, 8, 12, 16, 24} (x 2 wavefronts) by a degree window inside the kernel -- a row of 300 neighbours runs on 384
   // wires instead of 768, the one row of exactly 512 (513 elements) on 768.  Rows outside a launch's window cost two loads.
   int rc;
   constexpr int B160 = FSW_BIN_LDS0 - 3, B192 = FSW_BIN_LDS0 - 2, B256 = FSW_BIN_LDS0 - 1;   // mid bins ..160, ..192, ..256
-  constexpr int B40 = FSW_BIN_MID0, B64 = FSW_BIN_MID0 + 2, B128 = FSW_BIN_MID0 + 5;          // ..40, ..64, ..128
-  if (bin_lo <= B64) FSW_HW(1, 1, std::max(bin_lo, B40), B64, 0, 63);
-  if (bin_lo <= B128) FSW_HW(1, 2, std::max(bin_lo, B64), B128, 63, 127);
-  if (bin_lo <= B128) FSW_HW(1, 3, B128, B128, 127, 191);
-  if (bin_lo <= B160) FSW_HW(1, 3, std::max(bin_lo, B160), B160, 0, 191);
-  if (bin_lo <= B256) FSW_HW(1, 4, std::max(bin_lo, B192), B256, 0, 255);
-  if (bin_lo <= B256) FSW_HW(1, 6, B256, B256, 255, 383);
+  static_assert(FSW_MID_MAX_DEG_WEIGHTED == 128 && B160 == FSW_BIN_MID0 + 6, "the bins above FSW_MID_MAX_DEG_WEIGHTED start at ..160");
+  FSW_HW(1, 3, B160, B160, 0, 191);
+  FSW_HW(1, 4, B192, B256, 0, 255);
+  FSW_HW(1, 6, B256, B256, 255, 383);
   FSW_HW(1, 6, FSW_BIN_LDS0, FSW_BIN_LDS0, 0, 383);               // 257 .. 512
   FSW_HW(1, 8, FSW_BIN_LDS0, FSW_BIN_LDS0, 383, 511);
   FSW_HW(1, 12, FSW_BIN_LDS0, FSW_BIN_LDS0, 511, 767);
@@ -1440,15 +1157,15 @@ int launch_embed_hub_weighted_lds(const fsw_embed_args& a, int bin_lo, int64_t r
   return 0;
 }
 #elif FSW_HUB_PART == 2
-// general weights, 2049 .. kHubWMaxDeg (fsw_common.h) neighbours: two and four wavefronts per line.  Above, the scratch-line kernel of
-// embed_wsort.hip stays: sixteen wavefronts x 12 keys (or eight x 24) per line measured 124 (159) ms on the RMAT graph's class
+// general weights, 2049 .. kHubWMaxDeg (fsw_common.h) neighbours: two and four wavefronts per line.  Wider lines lost even to the scratch-line
+// kernel of embed_wsort.hip: sixteen wavefronts x 12 keys (or eight x 24) per line measured 124 (159) ms on the RMAT graph's class
 // 4097..8192 against its 97 ms -- one workgroup per CU at 96 KB of exchange buffer does not cover the barrier-separated exchanges
 int launch_embed_hub_weighted_hub(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
   int rc;
   FSW_HW(2, 24, FSW_BIN_HUB0, FSW_BIN_HUB0, 0, 3071);             // 2049 .. 4096
   FSW_HW(4, 16, FSW_BIN_HUB0, FSW_BIN_HUB0, 3071, 4095);
   FSW_HW(4, 24, FSW_BIN_HUB0, FSW_BIN_HUB0, 4095, 6143);
-  FSW_HW(4, 24, FSW_BIN_HUB0 + 1, FSW_BIN_HUB0 + 1, 0, 6143);     // 4097 .. 8191 (8192 itself: scratch-line kernel)
+  FSW_HW(4, 24, FSW_BIN_HUB0 + 1, FSW_BIN_HUB0 + 1, 0, 6143);     // 4097 .. 8191 (8192 itself: k_embed_mergepath_w)
   FSW_HW(4, 32, FSW_BIN_HUB0 + 1, FSW_BIN_HUB0 + 1, 6143, kHubWMaxDeg);
   return 0;
 }
@@ -1462,15 +1179,7 @@ int launch_embed_hub(const fsw_embed_args& a, int64_t rows_upper, hipStream_t st
   int rc;
   const int64_t md = a.max_degree;   // host value, <= 0 when unknown
   if ((rc = launch_hub_pair<2>(a, FSW_BIN_HUB0, rows_upper, stream))) return rc;
-#ifndef FSW_HUB_WIDE2
-#define FSW_HUB_WIDE2 0   // 1: 4097..8192 neighbours on TWO wavefronts x 48 / 64 keys per lane (16-byte gathers + stash, one exchange level)
-#endif
-  if (FSW_HUB_WIDE2) {
-    if (md <= 0 || md > 4096) {
-      if ((rc = launch_hub<2, 48>(a, FSW_BIN_HUB0 + 1, rows_upper, stream, 0, 2 * kWave * 48))) return rc;
-      if ((rc = launch_hub<2, 64>(a, FSW_BIN_HUB0 + 1, rows_upper, stream, 2 * kWave * 48 + 1, 0x7fffffff))) return rc;
-    }
-  } else if ((md <= 0 || md > 4096) && (rc = launch_hub_pair<4>(a, FSW_BIN_HUB0 + 1, rows_upper, stream))) return rc;
+  if ((md <= 0 || md > 4096) && (rc = launch_hub_pair<4>(a, FSW_BIN_HUB0 + 1, rows_upper, stream))) return rc;
   if ((md <= 0 || md > 8192) && (rc = launch_hub_pair<8>(a, FSW_BIN_HUB0 + 2, rows_upper, stream))) return rc;
   if ((md <= 0 || md > 16384) && (rc = launch_hub_pair<16>(a, FSW_BIN_HUB0 + 3, rows_upper, stream))) return rc;
   return 0;
@@ -1482,9 +1191,7 @@ int launch_embed_ws_unit(const fsw_embed_args& a, int64_t rows_upper, hipStream_
   if (rows_upper <= 0) return 0;
   int rc;
   const int64_t md = a.max_degree;
-  if ((md <= 0 || md > FSW_MID_MAX_DEG) &&
-      (rc = FSW_HUB_ROWLINES ? launch_rowlines(a, FSW_BIN_LDS0, rows_upper, stream) : launch_hub<1, 8>(a, FSW_BIN_LDS0, rows_upper, stream)))
-    return rc;
+  if ((md <= 0 || md > FSW_MID_MAX_DEG) && (rc = launch_rowlines(a, FSW_BIN_LDS0, rows_upper, stream))) return rc;
   if ((md <= 0 || md > 512) && (rc = launch_hub<1, 16>(a, FSW_BIN_LDS0 + 1, rows_upper, stream))) return rc;
   if ((md <= 0 || md > 1024) && (rc = launch_hub<1, 32>(a, FSW_BIN_LDS0 + 2, rows_upper, stream))) return rc;
   return 0;

@@ -13,7 +13,7 @@
 //     table as on the <= 32 path would not fit -- so there is still no transcendental per element;
 //   * general weights: (key, weight) network, the reference's pad element (fsw_embedding.py:787-821) at wire D,
 //     cumulative weight and phase in float64 as in embed_reg.hip.
-#include "fsw_common.h"
+#include "embed_launch.h"
 #include <algorithm>
 #include <stdlib.h>
 #include "sortnet.h"
@@ -23,20 +23,6 @@
 #endif
 
 namespace fsw {
-
-constexpr double kPiM = 3.14159265358979323846;
-
-__device__ __forceinline__ float mass_encode_m(float m, int fn) {
-  // reference fsw_embedding.py:857-865
-  if (fn == 1) return 2.f * (m / (sqrtf(m + 1.f) + 1.f));
-  if (fn == 2) return log1pf(m);
-  return m;
-}
-
-__device__ __forceinline__ float sin2pi_rev_m(double x) {
-  const double r = x - rint(x);
-  return sinpif(2.f * (float)r);
-}
 
 template <int DP>
 __global__ void __launch_bounds__(256) k_embed_mid_unit(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -98,7 +84,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_unit(const int32_t* __restric
     float* orow = out + (int64_t)node * ldo;
     orow[has_mass + kc] = acc;
     if (has_mass && chunk == 0 && lane_id() == 0)
-      orow[0] = out_scale * (mass_encode_m((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      orow[0] = out_scale * (mass_encode((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
     node = node_n;
     start = start_n;
     end = end_n;
@@ -213,7 +199,7 @@ __global__ void __launch_bounds__(256, 1) k_embed_mid_unit_pf(const int32_t* __r
     float* orow = out + (int64_t)cur.node * ldo;
     orow[has_mass + kc] = acc;
     if (has_mass && chunk == 0 && lane == 0)
-      orow[0] = out_scale * (mass_encode_m((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      orow[0] = out_scale * (mass_encode((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
     cur = nxt;
     nxt = nn;
   }
@@ -237,7 +223,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
   const float xif = freqs[kc];
   const double xi = (double)xif;
   const bool lin = xif < 1e-30f;
-  const float scale = lin ? 2.f : (float)((1.0 + xi) / (kPiM * xi));
+  const float scale = lin ? 2.f : (float)((1.0 + xi) / (kPi * xi));
   const float b = bias ? bias[has_mass + kc] : 0.f;
   const double taud = (double)tau;
   for (int p = pbeg + blockIdx.x; p < pend; p += gridDim.x) {
@@ -278,7 +264,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
     for (int t = 0; t < DP; ++t) {
       if (t <= D) {
         c += (double)net.w[t];
-        const float s = sin2pi_rev_m(xi * (c * inv));
+        const float s = sin2pi_rev(xi * (c * inv));
         acc = fmaf(s - sprev, net.k[t], acc);
         acc0 = fmaf(net.w[t], net.k[t], acc0);
         sprev = s;
@@ -288,7 +274,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
     float* orow = out + (int64_t)node * ldo;
     orow[has_mass + kc] = out_scale * (scale * val + b);
     if (has_mass && chunk == 0 && lane_id() == 0)
-      orow[0] = out_scale * (mass_encode_m((float)m, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      orow[0] = out_scale * (mass_encode((float)m, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
   }
 }
 
@@ -297,18 +283,13 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
 #ifndef FSW_MID_PART
 #error "compile with -DFSW_MID_PART=0|1|2"
 #endif
-int launch_mid_unit_small(const fsw_embed_args& a, dim3 grid, hipStream_t stream);
 int launch_mid_unit_large(const fsw_embed_args& a, dim3 grid, hipStream_t stream);
-int launch_mid_weighted(const fsw_embed_args& a, dim3 grid, hipStream_t stream);
-int launch_embed_mid_split(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);   // embed_hub.hip
-int launch_embed_mid_lds(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);     // embed_hub.hip
+// rows_upper: upper bound of the rows in the mid bins (the per-bin counts stay on the device); surplus workgroups of
+// an instance whose bin is short or empty leave at once.
+static dim3 mid_grid(const fsw_embed_args& a, int64_t rows_upper) {
+  return dim3((unsigned)std::min<int64_t>(rows_upper, 8192), (unsigned)ceil_div(a.S, 4 * kWave));
+}
 
-#define FSW_MID_UNIT(i, DP)                                                                                               \
-  if (bin_rows_or(a, FSW_BIN_MID0 + i, FSW_BIN_MID0 + i, 1) > 0)                                                            \
-  k_embed_mid_unit<DP><<<grid, 256, 0, stream>>>(a.rowptr, a.col, a.perm, a.bin_start, FSW_BIN_MID0 + i, a.Xp, a.ldp, a.S,  \
-                                                 a.freqs, a.out, a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn,       \
-                                                 a.mass_scale);                                                           \
-  FSW_LAUNCH_CHECK()
 #ifndef FSW_MID_PF_MIN
 #define FSW_MID_PF_MIN 192    // networks of at least this many wires prefetch the next row's keys (k_embed_mid_unit_pf<DP, PF > 0>)
 #endif
@@ -336,29 +317,13 @@ int launch_embed_mid_lds(const fsw_embed_args& a, int64_t rows_upper, hipStream_
   FSW_LAUNCH_CHECK()
 
 #if FSW_MID_PART == 0
-int launch_mid_unit_small(const fsw_embed_args& a, dim3 grid, hipStream_t stream) {
+// unit weights, tau <= 1.  (Two re-mappings of the bins of 129..256 neighbours that gave a line to four lanes were measured slower
+// than one lane per slice and removed: DESIGN.md, the embed_hub.hip entry.)
+int launch_embed_mid_unit(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
+  const dim3 grid = mid_grid(a, rows_upper);
   FSW_MID_UNIT_PF(0, 40, 40); FSW_MID_UNIT_PF(1, 48, 48); FSW_MID_UNIT_PF(2, 64, 64); FSW_MID_UNIT_PF(3, 80, 80); FSW_MID_UNIT_PF(4, 96, 96);
   FSW_MID_UNIT_PF(5, 128, 128);
-  return 0;
-}
-
-// rows_upper: upper bound of the rows in the mid bins (the per-bin counts stay on the device); surplus workgroups of
-// an instance whose bin is short or empty leave at once.
-int launch_embed_mid(const fsw_embed_args& a, bool unit_fast, int64_t rows_upper, hipStream_t stream) {
-  if (rows_upper <= 0) return 0;
-  dim3 grid((unsigned)std::min<int64_t>(rows_upper, 8192), (unsigned)ceil_div(a.S, 4 * kWave));
-  int rc;
-  if (unit_fast) {
-    if ((rc = launch_mid_unit_small(a, grid, stream))) return rc;
-    // 129..256 neighbours: FSW_MID_SPLIT=1 in the environment runs the line split over four lanes instead (embed_hub.hip:
-    // k_embed_rowlines<M, 4>, three waves per SIMD).  Measured SLOWER on the populated bin of the RMAT graphs (129..160 neighbours:
-    // 373 against 524 G keys/s; LL = 2 / 8: 379 / 392): four 64-byte pieces per gather instruction instead of one 256-byte run
-    // cost more than the occupancy gains -- kept for comparison (tools/exp_skew.py --fine)
-    static const int split = [] { const char* e = getenv("FSW_MID_SPLIT"); return e ? atoi(e) : 0; }();
-    if (split == 2) return launch_embed_mid_lds(a, rows_upper, stream);   // whole-row gathers through LDS (k_embed_mid_lds)
-    return split ? launch_embed_mid_split(a, rows_upper, stream) : launch_mid_unit_large(a, grid, stream);
-  }
-  return launch_mid_weighted(a, grid, stream);   // bins above FSW_MID_MAX_DEG_WEIGHTED go to the wave-sort path (embed_wsort.hip)
+  return launch_mid_unit_large(a, grid, stream);
 }
 #elif FSW_MID_PART == 1
 int launch_mid_unit_large(const fsw_embed_args& a, dim3 grid, hipStream_t stream) {
@@ -366,19 +331,15 @@ int launch_mid_unit_large(const fsw_embed_args& a, dim3 grid, hipStream_t stream
   return 0;
 }
 #else
-int launch_mid_weighted(const fsw_embed_args& a, dim3 grid, hipStream_t stream) {
-  // without edge features the bins from weighted_hub_first_mid_bin() on run on k_embed_hub_w (embed_wsort.hip: launch_embed_lds)
-  const int end = a.efeat ? 6 : weighted_hub_first_mid_bin();
-  if (end > 0) { FSW_MID_WEIGHTED(0, 40); }
-  if (end > 1) { FSW_MID_WEIGHTED(1, 48); }
-  if (end > 2) { FSW_MID_WEIGHTED(2, 64); }
-  if (end > 3) { FSW_MID_WEIGHTED(3, 80); }
-  if (end > 4) { FSW_MID_WEIGHTED(4, 96); }
-  if (end > 5) { FSW_MID_WEIGHTED(5, 128); }
+// general weights: the bins up to FSW_MID_MAX_DEG_WEIGHTED; the bins above go to (key, weight) lines (embed_hub.hip) or, with edge
+// features, to the wave-sort path (embed_wsort.hip)
+int launch_embed_mid_weighted(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
+  const dim3 grid = mid_grid(a, rows_upper);
+  FSW_MID_WEIGHTED(0, 40); FSW_MID_WEIGHTED(1, 48); FSW_MID_WEIGHTED(2, 64); FSW_MID_WEIGHTED(3, 80); FSW_MID_WEIGHTED(4, 96);
+  FSW_MID_WEIGHTED(5, 128);
   return 0;
 }
 #endif
-#undef FSW_MID_UNIT
 #undef FSW_MID_UNIT_PF
 #undef FSW_MID_WEIGHTED
 

@@ -9,28 +9,27 @@
 // (the full-rate shape), as on the <= 32 path (embed_bwd.hip); gfreq is reduced per lane over the workgroup's rows.
 // F(xi; c) = (1 + xi) sin(2 pi xi c)/(pi xi), see embed_wsort_bwd.hip (which serves the rows above 128).
 #include <algorithm>
-#include "fsw_common.h"
+#include "embed_launch.h"
 #include "sortnet.h"
 
 namespace fsw {
 
-constexpr double kPiMB = 3.14159265358979323846;
 
 struct FCoefM {
   double xi, a1, a2, a3;   // a1 = (1 + xi)/(pi xi), a2 = 1/(pi xi^2), a3 = 2 (1 + xi)/xi: no division left per element
   __device__ __forceinline__ explicit FCoefM(double x) : xi(x) {
     const double r = x > 0.0 ? 1.0 / x : 0.0;
-    a1 = (1.0 + x) * r * (1.0 / kPiMB);
-    a2 = r * r * (1.0 / kPiMB);
+    a1 = (1.0 + x) * r * (1.0 / kPi);
+    a2 = r * r * (1.0 / kPi);
     a3 = 2.0 * (1.0 + x) * r;
   }
 };
 __device__ __forceinline__ void F_dF_sc_m(const FCoefM& f, double c, double s, double co, double& F, double& dF) {
-  const double x = 2.0 * kPiMB * f.xi * c;
+  const double x = 2.0 * kPi * f.xi * c;
   if (x < 1e-4) {   // series: the two terms of dF cancel for tiny phases; xi == 0 gives F = dF = 2 c
     const double q = 1.0 - x * x * (1.0 / 6.0);
     F = (1.0 + f.xi) * 2.0 * c * q;
-    dF = 2.0 * c * q - (1.0 + f.xi) * 2.0 * c * (2.0 * kPiMB * c) * (2.0 * kPiMB * c) * f.xi * (1.0 / 3.0);
+    dF = 2.0 * c * q - (1.0 + f.xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * f.xi * (1.0 / 3.0);
   } else {
     F = f.a1 * s;
     dF = fma(f.a3 * c, co, -(f.a2 * s));

@@ -18,7 +18,7 @@
 //                            and phase in float64 (v_fma_f64 is full rate per instruction class on gfx950),
 //                            Delta_t = [sin(2 pi xi c_t) - sin(2 pi xi c_{t-1})] (1+xi)/(pi xi), which equals
 //                            the reference's 2 w sinc(xi w) cos(pi xi (2c - w)) by sum-to-product.
-#include "fsw_common.h"
+#include "embed_launch.h"
 #include "sortnet.h"
 #include "row_pipeline.h"
 #ifndef FSW_REG_PIPE_BARRIER
@@ -28,14 +28,6 @@
 namespace fsw {
 
 constexpr int kRowsPerBlock = 32;  // perm positions per workgroup
-constexpr double kPi = 3.14159265358979323846;
-
-__device__ __forceinline__ float mass_encode(float m, int fn) {
-  // reference fsw_embedding.py:857-865
-  if (fn == 1) return 2.f * (m / (sqrtf(m + 1.f) + 1.f));
-  if (fn == 2) return log1pf(m);
-  return m;
-}
 
 // ---- unit-weight coefficient table ------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_unit_table(const float* __restrict__ freqs, int S, int max_deg,
@@ -105,7 +97,7 @@ __device__ __forceinline__ void unit_run(int p, int pe, const int32_t* __restric
   const int nodev = perm[p + min(lane, nrows - 1)];   // lane r: node id and CSR offset of the block's row r
   const int startv = rowptr[nodev];
   if (mass_lane_wave && lane < nrows)
-    out[(int64_t)nodev * ldo] = out_scale * (mass_encode((float)D, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+    out[(int64_t)nodev * ldo] = mass_column((float)D, mass_fn, mass_scale, bias, out_scale);
   // lanes past the last slice recompute slice S-1 and store the same value to the same address (row_pipeline.h); with RPW = 2 a
   // step past the last row recomputes the last row in the same way
   float* ok = out + has_mass + kc;
@@ -189,12 +181,6 @@ __global__ void __launch_bounds__(256) k_embed_reg_unit_narrow(const int32_t* __
 }
 
 // ---- general weights ------------------------------------------------------------------------------------
-// sin(2 pi x) for a float64 phase x in revolutions: reduce in float64, evaluate in float32 with
-// relative accuracy (sinpif on |r| <= 1).
-__device__ __forceinline__ float sin2pi_rev(double x) {
-  const double r = x - rint(x);
-  return sinpif(2.f * (float)r);
-}
 
 template <int DEG>
 __device__ __forceinline__ void weighted_run(int p, int pe, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -248,7 +234,7 @@ __device__ __forceinline__ void weighted_run(int p, int pe, const int32_t* __res
     const float val = lin ? acc0 * (float)inv : acc;
     float* orow = out + (int64_t)node * ldo;
     if (kvalid) orow[has_mass + k] = out_scale * (scale * val + b);
-    if (mass_lane) orow[0] = out_scale * (mass_encode((float)m, mass_fn) * mass_scale + b0);
+    if (mass_lane) orow[0] = mass_column((float)m, mass_fn, mass_scale, b0, out_scale);
   }
 }
 

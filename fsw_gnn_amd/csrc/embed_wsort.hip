@@ -17,42 +17,14 @@
 //                cumsum of fsw_embedding.py:1031-1032), phase in float64, the reference's pad element
 //                (fsw_embedding.py:787-821) is element D.
 #include <algorithm>
-#include "fsw_common.h"
+#include "embed_launch.h"
 #include "sortnet.h"
 #include "wave_sort.h"
 
 namespace fsw {
 
-constexpr double kPiW = 3.14159265358979323846;
 constexpr int kWsLdsBytes = 69 * 1024;   // two workgroups per CU
 constexpr int kWsSplitY = 4;             // workgroups sharing one row (disjoint slice groups)
-
-__device__ __forceinline__ float mass_encode_w(float m, int fn) {
-  if (fn == 1) return 2.f * (m / (sqrtf(m + 1.f) + 1.f));
-  if (fn == 2) return log1pf(m);
-  return m;
-}
-
-__device__ __forceinline__ float sin2pi_rev_w(double x) {
-  const double r = x - rint(x);
-  return sinpif(2.f * (float)r);
-}
-
-__device__ __forceinline__ float wave_sum_w(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-__device__ __forceinline__ double wave_exclusive_scan_f64(double v) {
-  double inc = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const double t = __shfl_up(inc, off);
-    if (lane_id() >= off) inc += t;
-  }
-  return inc - v;
-}
 
 template <int M, bool WEIGHTED>
 __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -157,7 +129,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
             sincospi(2.0 * (step - rint(step)), &sd, &cd);
             const double x0 = step * (double)(lane * M);
             sincospi(2.0 * (x0 - rint(x0)), &s, &c);
-            const double scale = (1.0 + xi) / (kPiW * xi);
+            const double scale = (1.0 + xi) / (kPi * xi);
 #pragma unroll
             for (int j = 0; j < M; ++j) {
               const double sn = fma(s, cd, c * sd), cn = fma(c, cd, -(s * sd));
@@ -171,7 +143,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
 #pragma unroll
           for (int j = 0; j < M; ++j) part += (double)ln.w[j];
           double c = wave_exclusive_scan_f64(part);
-          float sprev = lin ? 0.f : sin2pi_rev_w(xi * (c * inv));
+          float sprev = lin ? 0.f : sin2pi_rev(xi * (c * inv));
 #pragma unroll
           for (int j = 0; j < M; ++j) {
             const bool valid = lane * M + j < Dtot;
@@ -179,14 +151,14 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
             if (lin) {
               acc += valid ? ln.w[j] * ln.k[j] : 0.f;
             } else {
-              const float s = sin2pi_rev_w(xi * (c * inv));
+              const float s = sin2pi_rev(xi * (c * inv));
               acc += valid ? (s - sprev) * ln.k[j] : 0.f;
               sprev = s;
             }
           }
-          acc *= lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPiW * xi));
+          acc *= lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPi * xi));
         }
-        acc = wave_sum_w(acc);
+        acc = wave_sum(acc);
         if (lane == 0) res[kk] = out_scale * (acc + (bias ? bias[has_mass + k] : 0.f));
       }
       __syncthreads();
@@ -194,7 +166,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
       __syncthreads();
     }
     if (has_mass && blockIdx.y == 0 && threadIdx.x == 0)
-      out[(int64_t)node * ldo] = out_scale * (mass_encode_w((float)m, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      out[(int64_t)node * ldo] = mass_column((float)m, mass_fn, mass_scale, bias, out_scale);
   }
 }
 
@@ -289,7 +261,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
     const int node = perm[p];
     const int start = rowptr[node];
     const int D = rowptr[node + 1] - start;
-    if (D <= dlo) continue;                             // done by k_embed_hub_w (launch_embed_global)
+    if (D <= dlo) continue;                             // rows another kernel takes (the launcher passes 0: none)
     const int Dtot = WEIGHTED ? D + 1 : D;
     const int Dp = (int)pow2ceil((uint32_t)Dtot);       // >= 2 CAP: D > FSW_LDS_MAX_DEG = CAP; <= wave_bytes / 8 by the bin's bound
     double m = (double)D;
@@ -392,7 +364,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
 #pragma unroll
           for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
           carry += tot;
-          float sprev = lin ? 0.f : sin2pi_rev_w(xi * (c * inv));
+          float sprev = lin ? 0.f : sin2pi_rev(xi * (c * inv));
 #pragma unroll
           for (int j = 0; j < M; ++j) {
             const bool valid = r0 + j < Dtot;
@@ -400,7 +372,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
             if (lin) {
               acc += valid ? ln.w[j] * ln.k[j] : 0.f;
             } else {
-              const float s = sin2pi_rev_w(xi * (c * inv));
+              const float s = sin2pi_rev(xi * (c * inv));
               acc += valid ? (s - sprev) * ln.k[j] : 0.f;
               sprev = s;
             }
@@ -409,43 +381,24 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
       }
       FSW_WSG_FENCE();
     }
-    acc = wave_sum_w(acc) * (lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPiW * xi)));
+    acc = wave_sum(acc) * (lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPi * xi)));
     if (lane == 0) {
       float* orow = out + (int64_t)node * ldo;
       orow[has_mass + k] = out_scale * (acc + (bias ? bias[has_mass + k] : 0.f));
-      if (has_mass && k == 0) orow[0] = out_scale * (mass_encode_w((float)m, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+      if (has_mass && k == 0) orow[0] = mass_column((float)m, mass_fn, mass_scale, bias, out_scale);
     }
   }
 }
 
-int launch_embed_ws_unit(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);   // embed_hub.hip
-int launch_embed_hub_weighted_lds(const fsw_embed_args& a, int bin_lo, int64_t rows_upper, hipStream_t stream);
-int launch_embed_hub_weighted_hub(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);
-int launch_embed_mergepath_w(const fsw_embed_args& a, int bin_lo, int bin_hi, int dlo, int64_t rows_upper, hipStream_t stream);
-#ifndef FSW_WEIGHTED_HUB
-#define FSW_WEIGHTED_HUB 1   // 0: general weights on the LDS-staged / scratch-line kernels of this file only (for comparison)
-#endif
-
-// general weights: every row above FSW_LDS_MAX_DEG (unit weights with tau <= 1 take embed_hub.hip's kernels)
-int launch_embed_global(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
+// general weights with edge features: every row above FSW_LDS_MAX_DEG
+int launch_embed_wsort_global(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
   if (rows_upper <= 0) return 0;
-  // without edge features the rows of up to kHubWMaxDeg neighbours keep their line in registers (embed_hub.hip: k_embed_hub_w)
-  int first_bin = FSW_BIN_HUB0, dlo = 0;
-  if (FSW_WEIGHTED_HUB && !a.efeat) {
-    if (int rc = launch_embed_hub_weighted_hub(a, rows_upper, stream)) return rc;
-    first_bin = FSW_BIN_HUB0 + 1;      // its rows of exactly 8192 neighbours (8193 elements) are all that is left of this bin
-    dlo = kHubWMaxDeg;
-    if (a.max_degree > 0 && a.max_degree <= kHubWMaxDeg) return 0;
-    if (bin_rows_or(a, first_bin, FSW_BIN_GLOBAL, 1) <= 0) return 0;
-    // above: sorted blocks + merge-path levels (embed_hub.hip); FSW_WEIGHTED_SCRATCH=1 keeps the scratch-line kernel below, for comparison
-    if (!getenv("FSW_WEIGHTED_SCRATCH")) return launch_embed_mergepath_w(a, first_bin, FSW_BIN_GLOBAL, dlo, rows_upper, stream);
-  }
   FSW_REQUIRE(a.max_degree > FSW_LDS_MAX_DEG, "fsw_embed_f32: max_degree (host value) is required for rows above FSW_LDS_MAX_DEG");
   FSW_REQUIRE(a.scratch, "fsw_embed_f32: these rows need a scratch buffer (fsw_embed_scratch_bytes)");
   char* scratch = reinterpret_cast<char*>(a.scratch);
   // One launch per degree bin, each with the scratch line its OWN longest row needs: sized by the graph's longest row, a single
   // 150 000-neighbour hub left 680 wavefronts (two thirds of one per SIMD) for every row above 4096 neighbours.
-  for (int bin = first_bin; bin <= FSW_BIN_GLOBAL; ++bin) {
+  for (int bin = FSW_BIN_HUB0; bin <= FSW_BIN_GLOBAL; ++bin) {
     const int64_t rows = bin_rows_or(a, bin, bin, rows_upper);
     if (rows <= 0) continue;
     const int64_t bin_max = bin == FSW_BIN_GLOBAL ? a.max_degree : std::min<int64_t>(a.max_degree, (int64_t)4096 << (bin - FSW_BIN_HUB0));
@@ -457,7 +410,7 @@ int launch_embed_global(const fsw_embed_args& a, int64_t rows_upper, hipStream_t
     FSW_REQUIRE(nwaves >= 4, "fsw_embed_f32: scratch buffer too small for rows above FSW_LDS_MAX_DEG (need fsw_embed_scratch_bytes(max_degree))");
     k_embed_wsort_global<32, true><<<(unsigned)(nwaves / 4), 256, 0, stream>>>(a.rowptr, a.col, a.w, a.perm, a.bin_start, a.Xp, a.ldp, a.S,
         a.freqs, a.tau, a.out, a.ldo, a.bias, a.out_scale, a.has_mass, a.mass_fn, a.mass_scale, a.efeat, a.Ve, a.ldve, a.d_edge, scratch, wave_bytes,
-        bin, bin, dlo);
+        bin, bin, 0);
     FSW_LAUNCH_CHECK();
   }
   return 0;
@@ -474,23 +427,18 @@ static int launch_wsort(const fsw_embed_args& a, int bin_lo, int bin_hi, int64_t
   return 0;
 }
 
-// rows_upper bounds the rows in the mid + LDS bins (the per-bin counts stay on the device)
-int launch_embed_lds(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
+// general weights with edge features: D + 1 elements with the pad element, so a class runs one size up, and the mid bins above
+// FSW_MID_MAX_DEG_WEIGHTED come here too.  rows_upper bounds the rows in the mid + LDS bins (the per-bin counts stay on the device)
+int launch_embed_wsort_lds(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream) {
   if (rows_upper <= 0) return 0;
-  const bool unit_fast = (a.w == nullptr) && (a.tau <= 1.f);
+  constexpr int sizes[FSW_NUM_MID_BINS] = FSW_MID_SIZES;
+  int bin_lo = FSW_BIN_MID0;
+  while (bin_lo < FSW_BIN_LDS0 && sizes[bin_lo - FSW_BIN_MID0] <= FSW_MID_MAX_DEG_WEIGHTED) ++bin_lo;
   int rc;
-  if (unit_fast) {   // one wavefront per line straight from Xp, no LDS staging (embed_hub.hip)
-    return launch_embed_ws_unit(a, rows_upper, stream);
-  } else {           // D + 1 elements with the pad element: one size up; the mid bins above FSW_MID_MAX_DEG_WEIGHTED come here too
-    constexpr int sizes[FSW_NUM_MID_BINS] = FSW_MID_SIZES;
-    int bin_lo = FSW_BIN_MID0;
-    while (bin_lo < FSW_BIN_LDS0 && sizes[bin_lo - FSW_BIN_MID0] <= FSW_MID_MAX_DEG_WEIGHTED) ++bin_lo;
-    if (FSW_WEIGHTED_HUB && !a.efeat) return launch_embed_hub_weighted_lds(a, FSW_BIN_MID0 + weighted_hub_first_mid_bin(), rows_upper, stream);
-    if (bin_lo < FSW_BIN_LDS0 && (rc = launch_wsort<8, true>(a, bin_lo, FSW_BIN_LDS0 - 1, rows_upper, stream))) return rc;
-    if ((rc = launch_wsort<16, true>(a, FSW_BIN_LDS0, FSW_BIN_LDS0, rows_upper, stream))) return rc;
-    if ((rc = launch_wsort<32, true>(a, FSW_BIN_LDS0 + 1, FSW_BIN_LDS0 + 1, rows_upper, stream))) return rc;
-    if ((rc = launch_wsort<64, true>(a, FSW_BIN_LDS0 + 2, FSW_BIN_LDS0 + 2, rows_upper, stream))) return rc;
-  }
+  if (bin_lo < FSW_BIN_LDS0 && (rc = launch_wsort<8, true>(a, bin_lo, FSW_BIN_LDS0 - 1, rows_upper, stream))) return rc;
+  if ((rc = launch_wsort<16, true>(a, FSW_BIN_LDS0, FSW_BIN_LDS0, rows_upper, stream))) return rc;
+  if ((rc = launch_wsort<32, true>(a, FSW_BIN_LDS0 + 1, FSW_BIN_LDS0 + 1, rows_upper, stream))) return rc;
+  if ((rc = launch_wsort<64, true>(a, FSW_BIN_LDS0 + 2, FSW_BIN_LDS0 + 2, rows_upper, stream))) return rc;
   return 0;
 }
 

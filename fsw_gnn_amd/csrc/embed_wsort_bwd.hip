@@ -16,13 +16,12 @@
 // with one 4-byte atomic per neighbour (these rows are few).
 #include <algorithm>
 #include <stdlib.h>
-#include "fsw_common.h"
+#include "embed_launch.h"
 #include "sortnet.h"
 #include "wave_sort.h"
 
 namespace fsw {
 
-constexpr double kPiB = 3.14159265358979323846;
 // LDS per workgroup: two workgroups per CU, except where the registers of a wave (one wave per SIMD) already allow only one
 // workgroup per CU -- those instances take twice the lines per slice group, i.e. twice as long atomic runs per neighbour
 template <int M, bool WEIGHTED>
@@ -32,43 +31,23 @@ constexpr int kWbSplitY = 4;
 #define FSW_WSB_ABL 0   // timing experiments on k_embed_wsort_bwd: 1 no atomics, 2 no sort, 4 no coefficient walk
 #endif
 
-__device__ __forceinline__ float wave_sum_b(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_b64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double wave_exclusive_scan_b64(double v) {
-  double inc = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const double t = __shfl_up(inc, off);
-    if (lane_id() >= off) inc += t;
-  }
-  return inc - v;
-}
-
 // F and dF/dxi at normalised cumulative weight c, given sin and cos of 2 pi xi c; series for tiny phases (the two terms
 // of dF cancel there); xi == 0: F = 2 c, dF = 2 c.  FCoef holds the per-slice factors so that no division is left per element.
 struct FCoef {
   double xi, a1, a2, a3;   // a1 = (1 + xi)/(pi xi), a2 = 1/(pi xi^2), a3 = 2 (1 + xi)/xi
   __device__ __forceinline__ explicit FCoef(double x) : xi(x) {
     const double r = x > 0.0 ? 1.0 / x : 0.0;
-    a1 = (1.0 + x) * r * (1.0 / kPiB);
-    a2 = r * r * (1.0 / kPiB);
+    a1 = (1.0 + x) * r * (1.0 / kPi);
+    a2 = r * r * (1.0 / kPi);
     a3 = 2.0 * (1.0 + x) * r;
   }
 };
 __device__ __forceinline__ void F_dF_sc(const FCoef& f, double c, double s, double co, double& F, double& dF) {
-  const double x = 2.0 * kPiB * f.xi * c;
+  const double x = 2.0 * kPi * f.xi * c;
   if (x < 1e-4) {
     const double q = 1.0 - x * x * (1.0 / 6.0);
     F = (1.0 + f.xi) * 2.0 * c * q;
-    dF = 2.0 * c * q - (1.0 + f.xi) * 2.0 * c * (2.0 * kPiB * c) * (2.0 * kPiB * c) * f.xi * (1.0 / 3.0);
+    dF = 2.0 * c * q - (1.0 + f.xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * f.xi * (1.0 / 3.0);
   } else {
     F = f.a1 * s;
     dF = fma(f.a3 * c, co, -(f.a2 * s));
@@ -168,7 +147,7 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
         wrow[t + t / M] = wt;
         part += (double)wt;
       }
-      part = wave_sum_b64(part);
+      part = wave_sum(part);
       if (lane == 0) msum[wv] = part;
       __syncthreads();
       m = msum[0] + msum[1] + msum[2] + msum[3];
@@ -226,12 +205,12 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
             const int id = ln.index(j);
             part += (lane * M + j < Dtot) ? (double)wrow[id + id / M] : 0.0;
           }
-          cbase = wave_exclusive_scan_b64(part);
+          cbase = wave_exclusive_scan_f64(part);
         }
         float gf = (FSW_WSB_ABL & 4) ? 0.f : walk_line<M, WEIGHTED>(
             ln, lane * M, D, Dtot, xi, inv, gi, cbase, [&](int id) { return wrow[id + id / M]; },
             [&](int id, float v) { line[id + id / M] = v; });   // every lane has read its keys: the line is free
-        gf = wave_sum_b(gf);
+        gf = wave_sum(gf);
         if (lane == 0 && gfreq) atomicAdd(gfreq + k, gf);
       }
       __syncthreads();
@@ -308,7 +287,7 @@ __global__ void __launch_bounds__(256, (M >= 32 ? 2 : (M >= 16 ? 3 : 4))) k_embe
     // every lane of THIS wavefront has read the line (the sort needed all keys): its places may take the results
     float gf = walk_line<M, false>(
         ln, lane * M, D, D, xi, 1.0 / (double)D, gi, 0.0, [](int) { return 0.f; }, [&](int id, float v) { xq[w][id] = v; });
-    gf = wave_sum_b(gf);
+    gf = wave_sum(gf);
     if (lane == 0 && gfreq) atomicAdd(gfreq + k, gf);
     __syncthreads();
     for (int e = threadIdx.x; e < D; e += blockDim.x)
@@ -394,7 +373,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global_bwd(const int32_t* _
     if constexpr (WEIGHTED) {
       double part = 0.0;
       for (int t = lane; t < D; t += kWave) part += (double)(w ? w[start + t] : 1.f);
-      m = wave_sum_b64(part);
+      m = wave_sum(part);
       padw = (float)fmax((double)tau - m, 0.0);
     }
     const double inv = 1.0 / (WEIGHTED ? fmax(m, (double)tau) : m);
@@ -446,14 +425,14 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global_bwd(const int32_t* _
           double part = 0.0;
 #pragma unroll
           for (int j = 0; j < M; ++j) part += (c0 + lane * M + j < Dtot) ? (double)weight_of(ln.index(j)) : 0.0;
-          cbase = carry + wave_exclusive_scan_b64(part);
-          carry += wave_sum_b64(part);
+          cbase = carry + wave_exclusive_scan_f64(part);
+          carry += wave_sum(part);
         }
         gf += walk_line<M, WEIGHTED>(ln, c0 + lane * M, D, Dtot, xi, inv, gi, cbase, weight_of, [&](int id, float v) { sc[id] = v; });
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
-    gf = wave_sum_b(gf);
+    gf = wave_sum(gf);
     if (lane == 0 && gfreq) atomicAdd(gfreq + k, gf);
     for (int t = lane; t < D; t += kWave) {
       const float v = sc[t];
@@ -486,9 +465,6 @@ static int launch_wsort_bwd(const fsw_embed_args& a, int bin_lo, int bin_hi, int
   return 0;
 }
 
-int launch_embed_mid_bwd(const fsw_embed_args& a, int64_t rows_upper, const float* g, int64_t ldg, float* gXp, int64_t ldgp,
-                         float* gfreq, float* gkey, int64_t ldk, hipStream_t stream);
-
 // rows of FSW_REG_MAX_DEG < degree <= FSW_LDS_MAX_DEG (rows_upper bounds their number) or, global == true, above
 int launch_embed_long_bwd(const fsw_embed_args& a, bool global, int64_t rows_upper, const float* g, int64_t ldg, float* gXp,
                           int64_t ldgp, float* gfreq, float* gkey, int64_t ldk, hipStream_t stream) {
@@ -498,7 +474,7 @@ int launch_embed_long_bwd(const fsw_embed_args& a, bool global, int64_t rows_upp
   if (global) {
     FSW_REQUIRE(a.scratch && a.max_degree > FSW_LDS_MAX_DEG, "fsw_embed_backward: rows above FSW_LDS_MAX_DEG need the scratch buffer and max_degree");
     char* scratch = reinterpret_cast<char*>(a.scratch);
-    // one launch per degree bin, the scratch line sized by the bin's own longest row (see launch_embed_global, embed_wsort.hip)
+    // one launch per degree bin, the scratch line sized by the bin's own longest row (see launch_embed_wsort_global, embed_wsort.hip)
     for (int bin = FSW_BIN_HUB0; bin <= FSW_BIN_GLOBAL; ++bin) {
       const int64_t rows = bin_rows_or(a, bin, bin, rows_upper);
       if (rows <= 0) continue;
@@ -527,7 +503,7 @@ int launch_embed_long_bwd(const fsw_embed_args& a, bool global, int64_t rows_upp
   constexpr int kFirst = FSW_BIN_MID0 + 6;                     // first bin above FSW_MID_MAX_DEG_WEIGHTED = 128
   // unit weights with stored key gradients (the store-and-sum backward) and four-slice alignment: the quad kernels
   const bool quad = unit && gkey && !a.efeat && a.S % 4 == 0 && ldk % 4 == 0 && a.ldp % 4 == 0 && ((uintptr_t)gkey & 15) == 0 &&
-                    ((uintptr_t)a.Xp & 15) == 0 && !getenv("FSW_BWD_QUAD_OFF");
+                    ((uintptr_t)a.Xp & 15) == 0;
   if (quad) {
     if ((rc = launch_quad_bwd<4>(a, kFirst, FSW_BIN_LDS0 - 1, rows_upper, g, ldg, gfreq, gkey, ldk, stream))) return rc;   // 129 .. 256
     if ((rc = launch_quad_bwd<8>(a, FSW_BIN_LDS0, FSW_BIN_LDS0, rows_upper, g, ldg, gfreq, gkey, ldk, stream))) return rc;

@@ -69,26 +69,8 @@ __host__ __device__ inline int degree_bin(int deg) {
 }
 
 // general weights without edge features: rows of up to this many neighbours (+ the pad element = 8192 = four wavefronts x 32 keys per
-// lane) keep their (key, weight) line in registers (embed_hub.hip: k_embed_hub_w); above, the scratch-line kernel of embed_wsort.hip
+// lane) keep their (key, weight) line in registers (embed_hub.hip: k_embed_hub_w); above, sorted blocks + merge path (k_embed_mergepath_w)
 constexpr int kHubWMaxDeg = 8191;
-
-// general weights without edge features: index (into FSW_MID_SIZES) of the first mid bin that runs on the (key, weight) lines of
-// embed_hub.hip (k_embed_hub_w) instead of the per-lane (key, weight) network of embed_mid.hip.  FSW_W_HUB_FROM = 33 | 65 | 129 in
-// the environment overrides the default (timing experiments).
-#ifndef FSW_W_HUB_FROM_DEFAULT
-#define FSW_W_HUB_FROM_DEFAULT 129
-#endif
-inline int weighted_hub_first_mid_bin() {
-  static const int idx = [] {
-    const char* e = getenv("FSW_W_HUB_FROM");
-    const int from = e ? atoi(e) : FSW_W_HUB_FROM_DEFAULT;
-    constexpr int sizes[FSW_NUM_MID_BINS] = FSW_MID_SIZES;
-    int i = 0;
-    while (i < FSW_NUM_MID_BINS && sizes[i] < from) ++i;   // first bin whose rows can have `from` neighbours or more
-    return std::min(i, 6);                                  // bins above FSW_MID_MAX_DEG_WEIGHTED never take the per-lane network
-  }();
-  return idx;
-}
 
 // rows of the degree bins lo .. hi when the caller passed the host copy of bin_start, `upper` (a bound) otherwise
 inline int64_t bin_rows_or(const fsw_embed_args& a, int lo, int hi, int64_t upper) {
@@ -100,6 +82,64 @@ __host__ __device__ inline uint32_t pow2ceil(uint32_t v) {
   while (p < v) p <<= 1;
   return p;
 }
+
+constexpr double kPi = 3.14159265358979323846;
+
+// total-mass encoding (reference fsw_embedding.py:857-865): identity | 2 (sqrt(1 + m) - 1), written without cancellation | log(1 + m)
+__device__ __forceinline__ float mass_encode(float m, int fn) {
+  if (fn == 1) return 2.f * (m / (sqrtf(m + 1.f) + 1.f));
+  if (fn == 2) return log1pf(m);
+  return m;
+}
+__device__ __forceinline__ double mass_encode(double m, int fn) {   // the float64 paths of embed_generic.hip / embed_cart.hip
+  if (fn == 1) return 2.0 * (m / (sqrt(m + 1.0) + 1.0));
+  if (fn == 2) return log1p(m);
+  return m;
+}
+// value of the total-mass output column of a row of total mass m; b0: the column's bias (0 without bias).  (k_embed_mid_* and
+// k_embed_hub_q4 write the expression out: with the branches of the encoding and of the bias inlined through this function their
+// sorting networks get another register allocation.)
+__device__ __forceinline__ float mass_column(float m, int mass_fn, float mass_scale, float b0, float out_scale) {
+  return out_scale * (mass_encode(m, mass_fn) * mass_scale + b0);
+}
+__device__ __forceinline__ float mass_column(float m, int mass_fn, float mass_scale, const float* bias, float out_scale) {
+  return out_scale * (mass_encode(m, mass_fn) * mass_scale + (bias ? bias[0] : 0.f));
+}
+template <class T>   // float64 arithmetic, bias in the output's precision
+__device__ __forceinline__ double mass_column(double m, int mass_fn, double mass_scale, const T* bias, double out_scale) {
+  return out_scale * (mass_encode(m, mass_fn) * mass_scale + (bias ? (double)bias[0] : 0.0));
+}
+
+// sin(2 pi x) for a float64 phase x in revolutions: reduced in float64, evaluated in float32 with relative accuracy (sinpif on |r| <= 1)
+__device__ __forceinline__ float sin2pi_rev(double x) {
+  const double r = x - rint(x);
+  return sinpif(2.f * (float)r);
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// sum of v over the lanes below this one
+__device__ __forceinline__ double wave_exclusive_scan_f64(double v) {
+  double inc = v;
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    const double t = __shfl_up(inc, off);
+    if (lane_id() >= off) inc += t;
+  }
+  return inc - v;
+}
+
+// gradient accumulators are float32 or float64 (the generic / Cartesian paths in either precision)
+__device__ __forceinline__ void atomic_add_t(float* p, double v) { atomicAdd(p, (float)v); }
+__device__ __forceinline__ void atomic_add_t(double* p, double v) { atomicAdd(p, v); }
 
 // sin and cos of 2 pi x for x in REVOLUTIONS (|x| < 2^40), absolute error ~1e-15: reduction to [-1/8, 1/8] revolutions around the
 // nearest quarter turn (exact in float64), Taylor polynomials on |angle| <= pi/4, quadrant fix-up.  About a third of the
@@ -148,7 +188,7 @@ struct UnitCoef {
     twoc = 2.0 * cd;
     cur = c0;
     prev = fma(c0, cd, s0 * sd);                 // cos(phi - theta)
-    B = (float)((1.0 + xi) / (3.14159265358979323846 * xi) * 2.0 * sh);
+    B = (float)((1.0 + xi) / (kPi * xi) * 2.0 * sh);
   }
   __device__ __forceinline__ float next() {     // cos(phi_r) of the current rank, then advance
     const float v = (float)cur;

@@ -251,9 +251,6 @@ __global__ void __launch_bounds__(768) k_project_bs(const float* __restrict__ X,
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 // bf16 per LDS row of the A planes: 16 KS + 8 (16-byte pad: row stride = 4 banks mod 64, conflict-free 16-byte fragment reads)
-#ifndef FSW_PROJECT_DIRECT_C
-#define FSW_PROJECT_DIRECT_C 0   // 1: C tile stored straight from the accumulators instead of through the LDS staging tile
-#endif
 #ifndef FSW_PROJECT_STAMPS
 #define FSW_PROJECT_STAMPS 0   // 1: s_memtime stamps at the phase boundaries of k_project_bf3's tile loop, summed per wave role
 #endif                         //    (tools/exp_project_stamps.py reads them through fsw_debug_project_stamps)
@@ -267,9 +264,6 @@ __device__ unsigned long long g_proj_stamps[1024][12][8];   // [workgroup][wave]
   } while (0)
 #else
 #define FSW_STAMP(i) do { } while (0)
-#endif
-#ifndef FSW_PROJECT_STAGGER
-#define FSW_PROJECT_STAGGER 0  // 1: the matrix block first / in the middle / last for the three wavefronts of a SIMD (see the tile loop)
 #endif
 #ifndef FSW_PROJECT_ABL
 #define FSW_PROJECT_ABL 0   // timing experiments (tools/exp_variants.sh): 1 = no MFMA, 2 = no output stores
@@ -291,9 +285,8 @@ __global__ void __launch_bounds__(KS <= 8 ? 768 : 512) k_project_bf3(const float
                                                      const float* __restrict__ b2, float* __restrict__ Y2, int64_t ldy2,
                                                      const int32_t* __restrict__ row_map, int64_t ntiles, int nslab_waves,
                                                      int nsl1, int y2_vec, int cbufs) {
-  // cbufs: buffers of the C staging tile.  2: one barrier per tile orders everything; 1: a second barrier per tile, half the
-  // staging LDS -- with the slabs split over two column groups (6 slab waves each) two workgroups then share a CU and cover
-  // each other's load / matrix / store phases.
+  // cbufs: buffers of the C staging tile.  2 (what the launcher passes): one barrier per tile orders everything; 1: a second barrier
+  // per tile, half the staging LDS.
   // KS <= 8 (d <= 128): up to 12 slab waves keep their whole slab of [V; W2] in registers (24 KS registers each).
   // KS == 16 (d <= 256): the slab takes 192 registers, so a workgroup is 4 slab waves + 4 waves that only move X, two waves
   // per SIMD at up to 256 registers, and the column groups beyond the first re-read X (from L2 / the Infinity Cache mostly).
@@ -443,97 +436,8 @@ __global__ void __launch_bounds__(KS <= 8 ? 768 : 512) k_project_bf3(const float
   unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long stamp_last = clock64();
 #endif
-#if FSW_PROJECT_STAGGER && !FSW_PROJECT_DIRECT_C
-  // the three blocks of an iteration
-  auto move_in = [&](int64_t t) {                        // tile t + 1 from registers into the A planes, loads of tile t + 2 issued
-    const int64_t next = t + gridDim.x, next2 = next + gridDim.x;
-    if (next < ntiles) store_tile(buf ^ 1, rs == 2 ? 0 : rs + 1, next, tr);
-    FSW_STAMP(0);                                        // waited for the tile's loads, split, wrote the A planes
-    if (next2 < ntiles) load_tile(next2, tr);
-    FSW_STAMP(1);                                        // loads of tile t + 2 issued
-  };
-  auto matrix = [&](int64_t t) {
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    if (slab_active && !(FSW_PROJECT_ABL & 1)) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&As[buf][0][fr][16 * s + 8 * fh]);
-        const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(&As[buf][1][fr][16 * s + 8 * fh]);
-        const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(&As[buf][2][fr][16 * s + 8 * fh]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, bw[0][s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bw[1][s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[2][s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bw[0][s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[1][s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[0][s], acc, 0, 0, 0);
-      }
-      FSW_STAMP(2);                                      // matrix instructions issued
-#if FSW_PROJECT_DIRECT_C
-      // straight from the accumulators: every store instruction covers two rows x 32 columns = two whole 128-byte lines
-      if (col_ok && !(FSW_PROJECT_ABL & 2)) {
-        const int64_t row0 = t * BS_ROWS;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int R = (r & 3) + 8 * (r >> 2) + 4 * fh;   // C/D map of the 32x32 MFMA
-          if (row0 + R < n) {
-            if (second) Y2[(int64_t)rmap[rs * BS_ROWS + R] * ldy2 + c] = acc[r] + add;
-            else Xp[(row0 + R) * ldp + c] = acc[r] + add;
-          }
-        }
-      }
-#else
-      if (cbufs == 1) __syncthreads();   // uniform: the previous tile has left the single staging buffer
-      float* cs = Cs + (cbufs == 2 ? buf : 0) * BS_ROWS * ldc + wv * 32 + fr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) cs[((r & 3) + 8 * (r >> 2) + 4 * fh) * ldc] = acc[r] + add;   // C/D map of the 32x32 MFMA
-      FSW_STAMP(3);                                      // accumulators drained into the staging tile
-#endif
-    } else if (cbufs == 1) {
-      __syncthreads();                   // helper waves (no slab) join the same barrier
-    }
-  };
-  // The matrix block at a different place of the iteration for each of the three wavefronts that share a SIMD (wavefront w runs on
-  // SIMD w % 4): one group's matrix instructions run under the other groups' loads / splits / stores instead of all twelve
-  // wavefronts moving data together and then queueing for the matrix pipe together.  The write-out of tile t moves into iteration
-  // t + 1 (its staging buffer and row-map slot are not reused before the barrier that ends it).
-  const int grp = cbufs == 2 ? (wv >> 2) % 3 : 2;
-  bool have_prev = false;
-  int64_t prev_tile = 0;
-  for (; tile < ntiles; tile += gridDim.x) {
-    auto out_prev = [&]() {
-      if (have_prev && !(FSW_PROJECT_ABL & 2)) write_out(cbufs == 2 ? buf ^ 1 : 0, prev_tile, rs == 0 ? 2 : rs - 1);
-      FSW_STAMP(5);
-    };
-    FSW_STAMP(6);
-    if (grp == 0) {
-      matrix(tile);
-      move_in(tile);
-      out_prev();
-    } else if (grp == 1) {
-      move_in(tile);
-      matrix(tile);
-      out_prev();
-    } else {
-      move_in(tile);
-      out_prev();
-      matrix(tile);
-    }
-    __syncthreads();
-    FSW_STAMP(4);                                        // barrier
-#if FSW_PROJECT_STAMPS
-    stamp_sum[7] += 1;
-#endif
-    have_prev = true;
-    prev_tile = tile;
-    buf ^= 1;
-    rs = rs == 2 ? 0 : rs + 1;
-  }
-  if (have_prev && !(FSW_PROJECT_ABL & 2)) write_out(cbufs == 2 ? buf ^ 1 : 0, prev_tile, rs == 0 ? 2 : rs - 1);
-#else
-  // (written out inline, not through the lambdas above: the same statements through move_in() / matrix() compiled to a loop that
-  // measured 0.70-0.72 ms against 0.65-0.68 ms for this one)
+  // (written out inline: the same statements through two lambdas -- next tile in, matrix block -- compiled to a loop that measured
+  // 0.70-0.72 ms against 0.65-0.68 ms for this one)
   for (; tile < ntiles; tile += gridDim.x) {
     const int64_t next = tile + gridDim.x, next2 = next + gridDim.x;
     FSW_STAMP(6);                                        // tail of the previous iteration: output stores issued
@@ -558,34 +462,17 @@ __global__ void __launch_bounds__(KS <= 8 ? 768 : 512) k_project_bf3(const float
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[0][s], acc, 0, 0, 0);
       }
       FSW_STAMP(2);                                      // matrix instructions issued
-#if FSW_PROJECT_DIRECT_C
-      // straight from the accumulators: every store instruction covers two rows x 32 columns = two whole 128-byte lines
-      if (col_ok && !(FSW_PROJECT_ABL & 2)) {
-        const int64_t row0 = tile * BS_ROWS;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int R = (r & 3) + 8 * (r >> 2) + 4 * fh;   // C/D map of the 32x32 MFMA
-          if (row0 + R < n) {
-            if (second) Y2[(int64_t)rmap[rs * BS_ROWS + R] * ldy2 + c] = acc[r] + add;
-            else Xp[(row0 + R) * ldp + c] = acc[r] + add;
-          }
-        }
-      }
-#else
       if (cbufs == 1) __syncthreads();   // uniform: the previous tile has left the single staging buffer
       float* cs = Cs + (cbufs == 2 ? buf : 0) * BS_ROWS * ldc + wv * 32 + fr;
 #pragma unroll
       for (int r = 0; r < 16; ++r) cs[((r & 3) + 8 * (r >> 2) + 4 * fh) * ldc] = acc[r] + add;   // C/D map of the 32x32 MFMA
       FSW_STAMP(3);                                      // accumulators drained into the staging tile
-#endif
     } else if (cbufs == 1) {
       __syncthreads();                   // helper waves (no slab) join the same barrier
     }
     __syncthreads();
     FSW_STAMP(4);                                        // barrier
-#if !FSW_PROJECT_DIRECT_C
     if (!(FSW_PROJECT_ABL & 2)) write_out(cbufs == 2 ? buf : 0, tile, rs);
-#endif
     FSW_STAMP(5);                                        // staging tile read, output stores issued
 #if FSW_PROJECT_STAMPS
     stamp_sum[7] += 1;
@@ -593,7 +480,6 @@ __global__ void __launch_bounds__(KS <= 8 ? 768 : 512) k_project_bf3(const float
     buf ^= 1;
     rs = rs == 2 ? 0 : rs + 1;
   }
-#endif
   if (stats && nonfinite) atomicOr(&stats[FSW_STAT_FLAGS], FSW_FLAG_X_NONFINITE);
 #if FSW_PROJECT_STAMPS
   if (lane == 0 && blockIdx.x < 1024 && blockIdx.y == 0 && wv < 12)
@@ -699,7 +585,8 @@ static int project_launch(const float* X, int64_t n, int d, int64_t ldx, const f
     // B-stationary kernels: one wave per 32-column slab, persistent over 32-row tiles (d <= 128: <= 12 slab waves so that
     // the B-operand registers fit without spilling, d <= 256: 4; >= 8 waves so that every X tile is two / four 16-byte
     // loads per thread -- waves without a slab only help moving X)
-    const bool exact = d <= 128 && getenv("FSW_PROJECT_EXACT_FP32") && atoi(getenv("FSW_PROJECT_EXACT_FP32")) != 0;
+    static const bool exact_env = [] { const char* e = getenv("FSW_PROJECT_EXACT_FP32"); return e && atoi(e) != 0; }();
+    const bool exact = d <= 128 && exact_env;
     const int nsl1 = (int)ceil_div(S, 32), nsl2 = (int)ceil_div(H2, 32);
 #ifndef FSW_PROJECT_NARROW_MAX
 #define FSW_PROJECT_NARROW_MAX 64   // widest output (columns) of the wavefront-per-tile kernel; 0: never
@@ -714,17 +601,13 @@ static int project_launch(const float* X, int64_t n, int d, int64_t ldx, const f
       return 0;
     }
     const int nslabs = exact ? (int)ceil_div(S + H2, 32) : nsl1 + nsl2;
-    // FSW_PROJECT_GROUPS=2 (experiment): d <= 128 with the slabs in two column groups of <= 6 waves, single C staging buffer, two
-    // workgroups per CU.  Measured SLOWER at config 3 (0.99 against 0.67 ms: X is read twice and every tile pays a second barrier)
-    static const int split_groups = [] { const char* e = getenv("FSW_PROJECT_GROUPS"); return e ? atoi(e) : 1; }();
-    const bool split = split_groups == 2 && d <= 128 && !exact;
-    const int max_slab_waves = d <= 128 ? (split ? 6 : 12) : 4;
+    const int max_slab_waves = d <= 128 ? 12 : 4;
     const int ngroups = (int)ceil_div(nslabs, max_slab_waves);
     const int nwaves = (int)ceil_div(nslabs, ngroups);
     const int64_t ntiles = ceil_div(n, BS_ROWS);
     dim3 grid((unsigned)std::min<int64_t>(ntiles, 256), (unsigned)ngroups);
-    const int threads = std::max(nwaves, split ? 6 : 8) * 64;
-    const int cbufs = split ? 1 : 2;
+    const int threads = std::max(nwaves, 8) * 64;
+    constexpr int cbufs = 2;   // C staging tiles: double buffered
     if (exact) {
       // FSW_PROJECT_EXACT_FP32=1: exact-fp32 MFMA kernel instead of bf16x3 (same accuracy class, 2.7x the matrix cycles)
 #define FSW_LAUNCH_BS(KQ)                                                                                                   \

@@ -167,9 +167,6 @@ __device__ __forceinline__ SegPair<V> wave_segscan_dpp(SegPair<V> v) {
 #ifndef FSW_SEG_HALO
 #define FSW_SEG_HALO 1    // carry from the previous tile's last group when it holds a segment head (no descriptor round trip)
 #endif
-#ifndef FSW_SEG_PREFETCH
-#define FSW_SEG_PREFETCH 0   // 1: issue the loads of the workgroup's next tile before the current tile is scanned.  Measured slower
-#endif                       // (150 registers -> 3 workgroups per CU): 4.68 against 5.27 TB/s at 2.56e9 elements; 6 per CU cover the loads
 
 template <class V, class I>
 struct SegTile {
@@ -319,10 +316,6 @@ __global__ void __launch_bounds__(kSegThreads, FSW_SEG_MINWAVES) k_segscan_chain
       halo.s = readlane_any(halo.s, kWave - 1);
       halo.f = __builtin_amdgcn_readlane(halo.f, kWave - 1);
     }
-#if FSW_SEG_PREFETCH
-    // the next tile of this workgroup: its loads are in flight while this tile is scanned, looked back and stored
-    if (tile + gridDim.x < ntiles) load_tile(tile + gridDim.x, cur);
-#endif
     // ---- lane-local scans and the scan across the lanes, group by group ----
     SegPair<V> pre[Q];      // everything of this wavefront's chunk that logically precedes the lane's elements of group q
     SegPair<V> wcarry;      // running aggregate of the chunk
@@ -424,9 +417,9 @@ __global__ void __launch_bounds__(kSegThreads, FSW_SEG_MINWAVES) k_segscan_chain
       }
     }
     __syncthreads();   // carry_s / wave_tot are reused by the next tile
-#if !FSW_SEG_PREFETCH
+    // (issued here, not before the scan: with the next tile's loads in flight under the scan the kernel took 150 registers -> 3
+    // workgroups per CU, 4.68 against 5.27 TB/s at 2.56e9 elements; 6 per CU cover the loads)
     if (tile + gridDim.x < ntiles) load_tile(tile + gridDim.x, cur);
-#endif
   }
 }
 

@@ -321,12 +321,12 @@ def test_long_rows_weighted_and_global_scratch_path(dev):
         assert relerr(out.cpu().numpy(), ref) < TOL
 
 
-def test_merge_path_rows_beyond_one_partition_chunk_and_with_ties(dev, monkeypatch):
+def test_merge_path_rows_beyond_one_partition_chunk_and_with_ties(dev):
     """csrc/merge_path.h on one neighbourhood of 2.2M vertices (an FSW_readout of a whole graph): 269 sorted blocks of 8192, nine
     merge levels with runs without a partner on several of them, more tile boundaries per level (538) than the 512 kept in LDS at a
     time; a second, shorter row whose features are drawn from 40 distinct vectors, so that almost every key is tied (merge path keeps
     ties in any order -- the readout must not care).  General weights (k_embed_mergepath_w, incl. a mass-deficient row) and unit
-    weights (k_embed_mergepath behind FSW_GIANT_MERGEPATH=1; the default k_embed_giant on the same rows)."""
+    weights (k_embed_giant on the same rows)."""
     from fsw_gnn_amd import build_csr
     rng = np.random.default_rng(41)
     sizes = [2_200_000, 50_000]
@@ -340,11 +340,7 @@ def test_merge_path_rows_beyond_one_partition_chunk_and_with_ties(dev, monkeypat
     w = (rng.random(rec.size) + 0.1).astype(np.float32)
     w[rec == 1] *= 0.7 / w[rec == 1].sum()                         # mass 0.7 < tau: the pad element carries 0.3
     rowptr = np.concatenate([[0], np.cumsum(sizes)])
-    for weights, merge_path in ((w, False), (None, True), (None, False)):
-        if merge_path:
-            monkeypatch.setenv("FSW_GIANT_MERGEPATH", "1")
-        else:
-            monkeypatch.delenv("FSW_GIANT_MERGEPATH", raising=False)
+    for weights in (w, None):
         E = make_embedding(dev, V, fr, enable_bias=False)
         with torch.no_grad():
             graph = build_csr(t(rec, dev, torch.int64), t(snd, dev, torch.int64), None if weights is None else t(weights, dev), 2, n)
@@ -432,12 +428,12 @@ def test_wave_sort_rows_every_size_class(dev, S):
 
 
 @pytest.mark.parametrize("S", [11, 12])
-def test_hub_rows_every_size_class(dev, S, monkeypatch):
+def test_hub_rows_every_size_class(dev, S):
     """Rows of 2049..70001 neighbours at both ends of the four hub classes (csrc/embed_hub.hip: a workgroup of 2 / 4 / 8 / 16
     wavefronts holds one slice's line, 2048 keys per wavefront, merge levels above a wavefront through LDS) and two rows above
-    them (k_embed_giant: blocks of 16384 keys + block sweeps; with FSW_GIANT_MERGEPATH=1 k_embed_mergepath: blocks of 8192 +
-    merge-path levels, 5 and 9 blocks = runs without a partner at two levels); general weights: k_embed_hub_w's capacity classes up
-    to 8191 neighbours, above them k_embed_mergepath_w ((key, weight) blocks of 8192 + merge-path levels, csrc/merge_path.h); a zero
+    them (k_embed_giant: blocks of 16384 keys + block sweeps); general weights: k_embed_hub_w's capacity classes up to 8191
+    neighbours, above them k_embed_mergepath_w ((key, weight) blocks of 8192 + merge-path levels, csrc/merge_path.h: 5 and 9 blocks =
+    runs without a partner at two levels); a zero
     frequency; a mass-deficient row; several rows per class so that the XCD-interleaved block order is exercised.
     S = 11: 4-byte gathers; S = 12 (a multiple of 4): the 16-byte gather forms."""
     from fsw_gnn_amd import build_csr, _lib
@@ -455,11 +451,7 @@ def test_hub_rows_every_size_class(dev, S, monkeypatch):
     w[rec == 0] *= 0.3 / w[rec == 0].sum()
     w[rec == 18] *= 0.4 / w[rec == 18].sum()          # the longest row is mass-deficient too: its pad element carries weight
     rowptr = np.concatenate([[0], np.cumsum(sizes)])
-    for weights, giant_merge_path in ((None, False), (None, True), (w, False)):
-        if giant_merge_path:
-            monkeypatch.setenv("FSW_GIANT_MERGEPATH", "1")
-        else:
-            monkeypatch.delenv("FSW_GIANT_MERGEPATH", raising=False)
+    for weights in (None, w):
         E = make_embedding(dev, V, fr, enable_bias=False, encode_total_mass=True)
         with torch.no_grad():
             graph = build_csr(t(rec, dev, torch.int64), t(snd, dev, torch.int64), None if weights is None else t(weights, dev), nrows, n)
