@@ -184,7 +184,7 @@ def sharded_embed_into(emb_mod, X, graph, out, out_scale=1.0, group=None, x_copy
     rank = dist.get_rank(group)
     if world == 1:
         return emb_mod.embed_into(X, graph, out, out_scale=out_scale, x_copy=x_copy, prepared=prepared)
-    has_mass = 1 if emb_mod.encode_total_mass else 0
+    has_mass = emb_mod.total_mass_encoding_dim
     parts = slice_partition(emb_mod.nSlices, world)
     ka, kb = parts[rank]
     if prepared is None:
@@ -254,7 +254,7 @@ def sharded_embed_autograd(emb_mod, X, graph, out_scale=1.0, group=None, edge_fe
         return emb_mod.embed_autograd(X, graph, out_scale=out_scale, edge_feat=edge_feat)
     if emb_mod.nSlices < world:
         raise NotImplementedError("fsw_gnn_amd: slice-parallel training needs at least one slice per rank")
-    has_mass = 1 if emb_mod.encode_total_mass else 0
+    has_mass = emb_mod.total_mass_encoding_dim
     parts = slice_partition(emb_mod.nSlices, world)
     local = emb_mod.embed_autograd(X, graph, out_scale=out_scale, edge_feat=edge_feat, slice_range=parts[rank], group=group,
                                    reduce_grads=True)
@@ -317,7 +317,7 @@ def consumer_weight(conv, group=None):
     device->host stats read so that it does not sit in the gap behind it)."""
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     emb = conv.fsw_embed
-    has_mass = 1 if emb.encode_total_mass else 0
+    has_mass = emb.total_mass_encoding_dim
     ka, kb = slice_partition(emb.nSlices, world)[rank]
     K = (has_mass if rank == 0 else 0) + (kb - ka)
     if K == 0:
@@ -333,18 +333,14 @@ def consumer_forward(conv, x, graph, prepared, scale, group=None, output="replic
     emb = conv.fsw_embed
     lin = conv.mlp[0]
     H, E = lin.out_features, conv.embed_dim
-    has_mass = 1 if emb.encode_total_mass else 0
+    has_mass = emb.total_mass_encoding_dim
     ka, kb = prepared["slice_range"]
     hm = has_mass if rank == 0 else 0            # rank 0 also carries the total-mass column (column 0 of W1)
     K = hm + (kb - ka)
     n = graph.num_rows
     cs, nchunks = (graph.chunk_rows, graph.num_chunks) if graph.chunk_rows else (round_chunk_rows(n, world), 1)
     assert graph.chunk_rows or cs >= n
-    act, slope, next_module = 0, 0.0, 1
-    if len(conv.mlp) > 1 and isinstance(conv.mlp[1], torch.nn.LeakyReLU):
-        act, slope, next_module = 2, float(conv.mlp[1].negative_slope), 2
-    elif len(conv.mlp) > 1 and isinstance(conv.mlp[1], torch.nn.ReLU):
-        act, next_module = 1, 2
+    act, slope, next_module = conv._fused_activation()
     st = prepared["stats"]
     if K > 0:
         if wq is None:
@@ -456,7 +452,7 @@ def exchange_forward(conv, x, graph, prepared, scale, group=None, output="replic
     covers under slice sharding (unit or general weights, rows of any degree, any tail whose modules act row by row)."""
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     emb = conv.fsw_embed
-    has_mass = 1 if emb.encode_total_mass else 0
+    has_mass = emb.total_mass_encoding_dim
     parts = slice_partition(emb.nSlices, world)
     ka, kb = parts[rank]
     wmax = max(b - a for a, b in parts)

@@ -162,56 +162,50 @@ class FSW_conv(_Base):
         chunk_rows > 0: degree bins per chunk of consecutive rows (graph.py; the multi-GPU pipeline).
         """
         if edge_features is not None:
-            src, dst = edge_index[0], edge_index[1]
-            ef = edge_features.detach().reshape(src.numel(), -1)
-            w = None
-            if self.self_loop_weight > 0:
-                loops = torch.arange(num_vertices, device=edge_index.device, dtype=torch.int64)
-                w = torch.cat([torch.ones(src.numel(), device=src.device, dtype=torch.float32),
-                               torch.full((num_vertices,), float(self.self_loop_weight), device=src.device, dtype=torch.float32)])
-                src, dst = torch.cat([src, loops]), torch.cat([dst, loops])
-                ef = torch.cat([ef, torch.zeros((num_vertices, ef.shape[1]), device=ef.device, dtype=ef.dtype)])
-            if self.edge_weighting == 'gcn':
-                if w is None:
-                    w = torch.ones(src.numel(), device=src.device, dtype=torch.float32)
-                deg = torch.zeros(num_vertices, device=src.device, dtype=torch.float32).scatter_add_(0, dst, w)
-                ds = torch.sqrt(deg)
-                w = w / ds[dst] / ds[src]
+            ef = edge_features.detach().reshape(edge_index.shape[1], -1)
+            src, dst, w, ef = self._weighted_edges(edge_index, num_vertices, ef)
             return build_csr_coalesced(dst, src, w, ef.contiguous(), num_vertices, num_vertices, want_slots=True)
-        if self.cache_graph:
-            # optional CSR reuse across calls / layers (SURVEY 8f #3).  Off by default: the reference rebuilds its
-            # adjacency on every forward (fsw_conv.py:352) and bench.py times the rebuild.  The cache entry keeps the
-            # edge_index tensor itself alive, so its address cannot be handed to another batch by the caching allocator;
-            # an in-place edit bumps _version.  The flags earlier inputs left behind are cleared on a hit.
-            key = (edge_index._version, tuple(edge_index.shape), int(num_vertices), float(self.self_loop_weight),
-                   self.edge_weighting, int(chunk_rows))
-            hit = getattr(self, '_graph_cache', None)
-            if hit is not None and hit[0] is edge_index and hit[1] == key:
-                hit[2].clear_input_flags()
-                return hit[2]
-            self.cache_graph = False
-            try:
-                graph = self.build_graph(edge_index, num_vertices, chunk_rows=chunk_rows)
-            finally:
-                self.cache_graph = True
-            self._graph_cache = (edge_index, key, graph)
-            return graph
+        if not self.cache_graph:
+            return self._build_graph_uncached(edge_index, num_vertices, chunk_rows)
+        # optional CSR reuse across calls / layers (SURVEY 8f #3).  Off by default: the reference rebuilds its
+        # adjacency on every forward (fsw_conv.py:352) and bench.py times the rebuild.  The cache entry keeps the
+        # edge_index tensor itself alive, so its address cannot be handed to another batch by the caching allocator;
+        # an in-place edit bumps _version.  The flags earlier inputs left behind are cleared on a hit.
+        key = (edge_index._version, tuple(edge_index.shape), int(num_vertices), float(self.self_loop_weight),
+               self.edge_weighting, int(chunk_rows))
+        hit = getattr(self, '_graph_cache', None)
+        if hit is not None and hit[0] is edge_index and hit[1] == key:
+            hit[2].clear_input_flags()
+            return hit[2]
+        graph = self._build_graph_uncached(edge_index, num_vertices, chunk_rows)
+        self._graph_cache = (edge_index, key, graph)
+        return graph
+
+    def _build_graph_uncached(self, edge_index, num_vertices, chunk_rows):
+        """build_graph without edge features: a fresh CSR."""
+        src, dst, w, _ = self._weighted_edges(edge_index, num_vertices)
+        return build_csr(dst, src, w, num_vertices, num_vertices, want_invperm=self._fusable(), chunk_rows=chunk_rows,
+                         hint=self._build_hint())
+
+    def _weighted_edges(self, edge_index, num_vertices, ef=None):
+        """(src, dst, w, ef) of the edge list with the self loops appended (weight self_loop_weight, zero features) and the 'gcn'
+        weighting applied (build_graph); w stays None for unit weights."""
         src, dst = edge_index[0], edge_index[1]
         w = None
         if self.self_loop_weight > 0:
             loops = torch.arange(num_vertices, device=edge_index.device, dtype=torch.int64)
             w = torch.cat([torch.ones(src.numel(), device=src.device, dtype=torch.float32),
                            torch.full((num_vertices,), float(self.self_loop_weight), device=src.device, dtype=torch.float32)])
-            src = torch.cat([src, loops])
-            dst = torch.cat([dst, loops])
+            src, dst = torch.cat([src, loops]), torch.cat([dst, loops])
+            if ef is not None:
+                ef = torch.cat([ef, torch.zeros((num_vertices, ef.shape[1]), device=ef.device, dtype=ef.dtype)])
         if self.edge_weighting == 'gcn':
             if w is None:
                 w = torch.ones(src.numel(), device=src.device, dtype=torch.float32)
             deg = torch.zeros(num_vertices, device=src.device, dtype=torch.float32).scatter_add_(0, dst, w)
             ds = torch.sqrt(deg)
             w = w / ds[dst] / ds[src]
-        return build_csr(dst, src, w, num_vertices, num_vertices, want_invperm=self._fusable(), chunk_rows=chunk_rows,
-                         hint=self._build_hint())
+        return src, dst, w, ef
 
     def forward(self, vertex_features, edge_index, edge_features=None):
         """vertex_features [n, in_channels], edge_index [2, E] long -> [n, out_channels] (fsw_conv.py:331-369)."""
@@ -256,7 +250,7 @@ class FSW_conv(_Base):
             return self._forward_slice_parallel(sp, x, vertex_features, edge_index, edge_features, needs_grad)
         graph = self.build_graph(edge_index, n, edge_features if self.edgefeat_dim > 0 else None)
         E = self.embed_dim
-        scale = float(self.message_weight_vs_self) if self.concat_self else 1.0      # fsw_conv.py:357-358
+        scale = self._message_scale
 
         if needs_grad:
             # training path: differentiable embedding (HIP forward + backward kernels), the tail through torch autograd
@@ -290,9 +284,7 @@ class FSW_conv(_Base):
                 nlong = st[_lib.STAT_NUM_LDS] + st[_lib.STAT_NUM_GLOBAL]
                 if nlong > 0:
                     self._finish_long_rows(x, graph, prepared, scale, yin, y, next_module, by_node)
-                for m in self.mlp[next_module:]:
-                    y = m(y)
-                return y
+                return self._mlp_from(y, next_module)
 
         if self._split_first_linear():
             emb = torch.empty((n, E), dtype=x.dtype, device=x.device)
@@ -344,19 +336,14 @@ class FSW_conv(_Base):
             # gradient on csrc/gemm_tn.hip
             out = LinearSplitTallFn.apply(emb, vertex_features.contiguous(), self.mlp[0].weight, self.mlp[0].bias,
                                           self.message_weight_vs_self)
-            for m in self.mlp[1:]:
-                out = m(out)
-            return self.bn_final(out) if self.bn_final is not None else out
+            return self._bn_final(self._mlp_from(out, 1))
         h = torch.cat((self.message_weight_vs_self * emb, vertex_features), dim=-1) if self.concat_self else emb
         if (self.mlp is not None and isinstance(self.mlp[0], torch.nn.Linear) and h.is_cuda and h.dtype == torch.float32
                 and h.shape[0] >= GEMM_TN_MIN_ROWS and self.mlp[0].weight.requires_grad and torch.is_grad_enabled()):
             # the first Linear layer with its weight gradient on csrc/gemm_tn.hip (a reduction over the rows), the rest as it is
             out = LinearTallFn.apply(h, self.mlp[0].weight, self.mlp[0].bias)
-            for m in self.mlp[1:]:
-                out = m(out)
-            return self.bn_final(out) if self.bn_final is not None else out
-        out = self.mlp(h) if self.mlp is not None else (torch.matmul(h, self.dim_reduct.transpose(0, 1)) if self.concat_self else h)
-        return self.bn_final(out) if self.bn_final is not None else out
+            return self._bn_final(self._mlp_from(out, 1))
+        return self._tail_buffer(h)
 
     def _split_first_linear(self):
         """Inference tail without the concat buffer: possible when the first module after cat((emb, x)) is a Linear layer."""
@@ -372,19 +359,46 @@ class FSW_conv(_Base):
         W = lin.weight.detach()
         y = torch.addmm(lin.bias.detach(), emb, W[:, :E].t()) if lin.bias is not None else emb @ W[:, :E].t()
         y.addmm_(x, W[:, E:].t())
-        for m in self.mlp[1:]:
-            y = m(y)
-        return self.bn_final(y) if self.bn_final is not None else y
+        return self._bn_final(self._mlp_from(y, 1))
 
     def _tail_buffer(self, buf):
-        """The same tail on the concat buffer the kernels filled in place (inference)."""
+        """The whole tail on cat((emb, x)): the concat buffer the kernels filled in place (inference), or torch's concatenation."""
+        return self._bn_final(self._mlp_or_dim_reduct(buf))
+
+    def _mlp_or_dim_reduct(self, h):
+        """The reference's MLP / dim_reduct (fsw_conv.py:361-366) without the final BatchNorm (FSW_readout stops here)."""
         if self.mlp is not None:
-            out = self.mlp(buf)
-        elif self.concat_self:
-            out = torch.matmul(buf, self.dim_reduct.transpose(0, 1))
-        else:
-            out = buf
-        return self.bn_final(out) if self.bn_final is not None else out
+            return self.mlp(h)
+        return torch.matmul(h, self.dim_reduct.transpose(0, 1)) if self.concat_self else h
+
+    def _mlp_from(self, y, k):
+        """Modules k.. of the MLP (the caller did the first k: split or fused first Linear layer, absorbed activation)."""
+        for m in self.mlp[k:]:
+            y = m(y)
+        return y
+
+    def _bn_final(self, y):
+        return self.bn_final(y) if self.bn_final is not None else y
+
+    @property
+    def _message_scale(self):
+        """Factor of the embedding in cat((message_weight_vs_self * emb, x)) (fsw_conv.py:357-358)."""
+        return float(self.message_weight_vs_self) if self.concat_self else 1.0
+
+    @staticmethod
+    def _needs_batch_statistics(modules):
+        """A BatchNorm layer among `modules` that normalises with the statistics of the rows it is given."""
+        return any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and (m.training or not m.track_running_stats) for m in modules)
+
+    def _fused_activation(self):
+        """(act, slope, next_module): the activation behind the first Linear layer that the fused kernel and fsw_add_bias_act_f32
+        absorb (0 none, 1 ReLU, 2 LeakyReLU) and the first module of the MLP left to torch.  Every rank of a sharded layer must stop
+        at the same one."""
+        if len(self.mlp) > 1 and isinstance(self.mlp[1], torch.nn.LeakyReLU):
+            return 2, float(self.mlp[1].negative_slope), 2
+        if len(self.mlp) > 1 and isinstance(self.mlp[1], torch.nn.ReLU):
+            return 1, 0.0, 2
+        return 0, 0.0, 1
 
     def _forward_slice_parallel(self, sp, x, vertex_features, edge_index, edge_features, needs_grad):
         """Slice-axis sharding over the ranks of sp['group'] (dist.py: gather / consumer / training forms)."""
@@ -395,7 +409,7 @@ class FSW_conv(_Base):
         emb_mod = self.fsw_embed
         n = x.shape[0]
         E = self.embed_dim
-        scale = float(self.message_weight_vs_self) if self.concat_self else 1.0
+        scale = self._message_scale
         has_ef = self.edgefeat_dim > 0
         stats = sp.get('stats')
         if stats is not None:
@@ -432,26 +446,19 @@ class FSW_conv(_Base):
                     # a 3-D tensor for its channels), the pad rows past the last node are zeroed again afterwards
                     R, row0 = res
                     rest = self.mlp[next_module:]
-                    if any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and (m.training or not m.track_running_stats)
-                           for m in rest):
+                    if self._needs_batch_statistics(rest):
                         raise NotImplementedError("fsw_gnn_amd: output='sharded' with a BatchNorm layer in batch-statistics mode "
                                                   "would normalise over this rank's rows only; call .eval() or use "
                                                   "output='replicated'")
                     if len(rest) > 0:
                         shape = R.shape
-                        R2 = R.reshape(-1, shape[-1])
-                        for m in rest:
-                            R2 = m(R2)
-                        R = R2.reshape(shape[0], shape[1], -1)
+                        R = self._mlp_from(R.reshape(-1, shape[-1]), next_module).reshape(shape[0], shape[1], -1)
                         for c in range(shape[0]):
                             valid = min(max(n - int(row0[c]), 0), shape[1])
                             if valid < shape[1]:
                                 R[c, valid:] = 0
                     return R, row0
-                y = res
-                for m in self.mlp[next_module:]:
-                    y = m(y)
-                return y
+                return self._mlp_from(res, next_module)
             if mode == 'consumer':
                 raise NotImplementedError("fsw_gnn_amd: the sharded-consumer form needs unit weights and rows of at most %d neighbours"
                                           % _lib.REG_MAX_DEG)
@@ -462,7 +469,7 @@ class FSW_conv(_Base):
             tail_mods = list(self.mlp) if self.mlp is not None else []
             if self.bn_final is not None:
                 tail_mods.append(self.bn_final)
-            if any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and (m.training or not m.track_running_stats) for m in tail_mods):
+            if self._needs_batch_statistics(tail_mods):
                 raise NotImplementedError("fsw_gnn_amd: the exchange form runs the tail on this rank's rows only; a BatchNorm layer in "
                                           "batch-statistics mode needs all rows (call .eval() or use mode='gather')")
             if prepared is None:
@@ -508,10 +515,10 @@ class FSW_conv(_Base):
             return False
         if self.self_loop_weight > 0 or self.edge_weighting != 'unit' or emb.total_mass_pad_thresh > 1.0 or self.edgefeat_dim > 0:
             return False
-        if emb.encode_total_mass and emb.total_mass_encoding_method != 'plain':
+        if not emb.plain_mass:
             return False
         width = emb.nSlices if num_slices is None else int(num_slices)
-        return int(_lib.lib().fsw_conv_fused_lds_bytes(width, 1 if emb.encode_total_mass else 0)) <= 64 * 1024
+        return int(_lib.lib().fsw_conv_fused_lds_bytes(width, emb.total_mass_encoding_dim)) <= 64 * 1024
 
     def _fused_weight(self, col0=0, K=None, want_w2=True):
         """(Wq, W2) of the first Linear layer W = [W1 | W2]: K columns of W1 from column col0 (default: all embed_dim
@@ -560,15 +567,10 @@ class FSW_conv(_Base):
         L = _lib.lib()
         emb = self.fsw_embed
         lin = self.mlp[0]
-        act, slope, next_module = 0, 0.0, 1
-        if len(self.mlp) > 1 and isinstance(self.mlp[1], torch.nn.LeakyReLU):
-            act, slope, next_module = 2, float(self.mlp[1].negative_slope), 2
-        elif len(self.mlp) > 1 and isinstance(self.mlp[1], torch.nn.ReLU):
-            act, next_module = 1, 2
-        has_mass = 1 if emb.encode_total_mass else 0
+        act, slope, next_module = self._fused_activation()
         bias = emb.bias.detach() if emb.enable_bias else None
         a = emb.make_args(graph, prepared["stats"], prepared["Xp"], prepared["ldp"], emb.freqs.detach(), emb.nSlices,
-                          prepared["table"], None, 0, bias.data_ptr() if bias is not None else None, scale, has_mass)
+                          prepared["table"], None, 0, bias.data_ptr() if bias is not None else None, scale, emb.total_mass_encoding_dim)
         rc = L.fsw_conv_fused_f32(ctypes.byref(a), wq.data_ptr(), wq.shape[1],
                                   lin.bias.data_ptr() if lin.bias is not None else None, lin.out_features,
                                   yin.data_ptr() if yin is not None else None, yin.stride(0) if yin is not None else 0,
@@ -601,11 +603,10 @@ class FSW_conv(_Base):
         emb = self.fsw_embed
         lin = self.mlp[0]
         H = lin.out_features
-        scale = float(self.message_weight_vs_self) if self.concat_self else 1.0
+        scale = self._message_scale
         y_all = torch.empty((world * per, H), dtype=x.dtype, device=x.device)
         y_loc = torch.empty((per, H), dtype=x.dtype, device=x.device)
-        # modules the fused kernel absorbs (Linear + ReLU / LeakyReLU): every rank must stop at the same one
-        next_module = 2 if len(self.mlp) > 1 and isinstance(self.mlp[1], (torch.nn.LeakyReLU, torch.nn.ReLU)) else 1
+        next_module = self._fused_activation()[2]      # every rank must stop at the same module
         if nl > 0:
             rel = edge_index[1] - r0
             mine = torch.nonzero((rel >= 0) & (rel < nl)).squeeze(1)                        # one compaction for both endpoints
@@ -638,10 +639,7 @@ class FSW_conv(_Base):
             y_all[rank * per:(rank + 1) * per].copy_(y_loc)
         else:
             dist.all_gather_into_tensor(y_all, y_loc, group=group)
-        y = y_all[:n]
-        for m in self.mlp[next_module:]:
-            y = m(y)
-        return self.bn_final(y) if self.bn_final is not None else y
+        return self._bn_final(self._mlp_from(y_all[:n], next_module))
 
     def enable_slice_parallel(self, group=None, enabled=True, mode='auto', chunks=None, output='replicated', stats=None):
         """Shard the slice axis of the embedding over the ranks of `group` (dist.py).
@@ -695,10 +693,7 @@ class FSW_readout(FSW_conv):
             assert int(graph_index.min()) >= 0 and int(graph_index.max()) < batch_size, 'all entries of graph_index must be in the range 0,...,batch_size-1'
             adj = torch.sparse_coo_tensor(torch.stack((graph_index, src)), torch.ones(num_vertices, dtype=torch.float64, device=src.device),
                                           size=(batch_size, num_vertices)).coalesce()
-            emb = emb_mod(vertex_features, W=adj, graph_mode=True)
-            if self.mlp is not None:
-                return self.mlp(emb)
-            return torch.matmul(emb, self.dim_reduct.transpose(0, 1)) if self.concat_self else emb
+            return self._mlp_or_dim_reduct(emb_mod(vertex_features, W=adj, graph_mode=True))
         graph = build_csr(graph_index.contiguous(), src, None, batch_size, num_vertices)
         needs_grad = torch.is_grad_enabled() and (vertex_features.requires_grad or any(p.requires_grad for p in self.parameters()))
         if needs_grad:
@@ -710,8 +705,4 @@ class FSW_readout(FSW_conv):
             emb_mod.embed_into(vertex_features.contiguous(), graph, emb)
         if graph.flags & 1:
             raise AssertionError('all entries of graph_index must be in the range 0,...,batch_size-1')
-        if self.mlp is not None:
-            return self.mlp(emb)
-        if self.concat_self:
-            return torch.matmul(emb, self.dim_reduct.transpose(0, 1))
-        return emb
+        return self._mlp_or_dim_reduct(emb)

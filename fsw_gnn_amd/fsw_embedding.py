@@ -13,7 +13,9 @@ csrc/embed_wsort_bwd.hip) for every weight mode and degree class; gradients flow
 total-mass scale (the weights W are constants).
 Edge features (d_edge > 0) go through the coalescing CSR build and the general-weight kernels.
 dtype=torch.float64 modules and gradients w.r.t. the weights W / sparse edge features run on the generic kernels
-(csrc/embed_generic.hip: any degree, float64 arithmetic).
+(csrc/embed_generic.hip: any degree, float64 arithmetic) through _GenericEmbedFn, which also serves Cartesian mode below.
+The 'homog' / 'homog_alt' total-mass methods are one epilogue in torch (_homog_epilogue) on the kernels' 'plain' output: in place
+for inference, out of place under autograd.  Nothing per call is kept on the module: what a call needs travels as arguments.
 
 Cartesian mode, FSW_embedding(d_in, nSlices=S, nFreqs=F, collapse_freqs=...) (reference fsw_embedding.py:153-160, 241-259):
 every slice is sorted once and read out at all F frequencies (csrc/embed_cart.hip); output (<batch>, [nR,] S, F), or
@@ -25,12 +27,12 @@ bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters 
 """
 import ctypes
 import numbers
+import os
 import struct
 
 import numpy as np
-import os
-
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
@@ -47,12 +49,18 @@ fsw_embedding_basic_safety_checks = True
 _MASS_FN = {"identity": 0, "sqrt": 1, "log": 2}
 
 
+def _mass_f(fn, m):
+    """f(m) of total_mass_encoding_function fn, the host-side twin of the kernels' mass_fn."""
+    return m if fn == 'identity' else (2 * (m / (torch.sqrt(m + 1) + 1)) if fn == 'sqrt' else torch.log1p(m))
+
+
+def _mass_df(fn, m):
+    """f'(m)."""
+    return torch.ones_like(m) if fn == 'identity' else (1 / torch.sqrt(m + 1) if fn == 'sqrt' else 1 / (1 + m))
+
+
 def _round_up(v, m):
     return (v + m - 1) // m * m
-
-
-def edge_feat_rows(ctx):
-    return ctx.num_edge_rows
 
 
 def _grad_x(L, gXp, S, ldp, V, stream):
@@ -155,19 +163,18 @@ class _EmbedGraphFn(torch.autograd.Function):
     [mass column | slices ka..kb-1] and the parameter gradients are full-size tensors that are zero outside the block.
     With reduce_grads the block gradients of all ranks of `group` are summed by all_reduce inside backward, so that every rank ends with
     the gradients one GPU would compute (the mass column, replicated on every rank, is counted once).
+    epilogue = False: 'homog' / 'homog_alt' -- embed_autograd asks for the 'plain' embedding without bias (`bias` is None) and
+    applies the epilogue with differentiable torch ops on top of it.
     """
 
     @staticmethod
-    def forward(ctx, X, projVecs, freqs, bias, mass_scale, edge_feat, module, graph, out_scale, slice_range, group, reduce_grads):
+    def forward(ctx, X, projVecs, freqs, bias, mass_scale, edge_feat, module, graph, out_scale, slice_range, group, reduce_grads,
+                epilogue):
         ka, kb = (0, module.nSlices) if slice_range is None else slice_range
-        has_mass = 1 if module.encode_total_mass else 0
         with torch.no_grad():
-            # 'homog' / 'homog_alt': embed_autograd asks for the 'plain' embedding (module._force_plain) and applies the
-            # epilogue with differentiable torch ops on top of it
-            assert (not module.encode_total_mass) or module.total_mass_encoding_method == 'plain' or module._force_plain
             prepared = module.prepare(X, graph, slice_range=slice_range)
-            out = torch.empty((graph.num_rows, has_mass + kb - ka), dtype=X.dtype, device=X.device)
-            module.embed_into(X, graph, out, out_scale=out_scale, prepared=prepared)
+            out = torch.empty((graph.num_rows, module.total_mass_encoding_dim + kb - ka), dtype=X.dtype, device=X.device)
+            module.embed_into(X, graph, out, out_scale=out_scale, prepared=prepared, epilogue=epilogue)
         ctx.module, ctx.graph, ctx.prepared, ctx.out_scale = module, graph, prepared, float(out_scale)
         ctx.slice_range, ctx.group, ctx.reduce_grads = (ka, kb), group, bool(reduce_grads)
         ctx.num_edge_rows = 0 if edge_feat is None else edge_feat.shape[0]
@@ -183,7 +190,7 @@ class _EmbedGraphFn(torch.autograd.Function):
         group = ctx.group
         sharded = ctx.reduce_grads        # group may be None = the default process group
         L = _lib.lib()
-        S, has_mass = kb - ka, (1 if module.encode_total_mass else 0)
+        S, has_mass = kb - ka, module.total_mass_encoding_dim
         V = Vfull.detach()[ka:kb]
         fr = freqs_full.detach()[ka:kb].contiguous()
         g = g.contiguous()
@@ -193,66 +200,61 @@ class _EmbedGraphFn(torch.autograd.Function):
         need_xp = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         gEf = None
         gVb = gfb = None          # block gradients (rows ka..kb-1 of projVecs, entries ka..kb-1 of freqs)
-        if S > 0 and graph.ef is not None and (need_xp or ctx.needs_input_grad[2] or ctx.needs_input_grad[5]):
-            # edge features: the kernels store the gradient of every key; everything else is index_add + three GEMMs
+        has_ef = graph.ef is not None
+        if S > 0 and (need_xp or ctx.needs_input_grad[2] or (has_ef and ctx.needs_input_grad[5])):
             nnz = st[_lib.STAT_NNZ]
-            scratch = None
-            if st[_lib.STAT_NUM_GLOBAL] > 0:
-                scratch = torch.empty(int(L.fsw_embed_scratch_bytes(st[_lib.STAT_MAX_DEGREE])), dtype=torch.uint8, device=X.device)
-            gkey = torch.zeros((max(nnz, 1), S), dtype=torch.float32, device=X.device)
-            gf = torch.zeros(S, dtype=torch.float32, device=X.device)
-            a = module.make_args(graph, st, Xp, ldp, fr, S, table, None, 0, None, out_scale, has_mass, scratch, slice_offset=ka)
-            _lib.check(L.fsw_embed_backward_keys_f32(ctypes.byref(a), None, _lib.ptr(g), g.stride(0), _lib.ptr(gkey), S, _lib.ptr(gf), stream),
-                       "fsw_embed_backward_keys_f32")
-            gkey, ef = gkey[:nnz], graph.ef[:nnz]
-            if need_xp:
-                gXp = torch.zeros((X.shape[0], S), dtype=torch.float32, device=X.device).index_add_(0, graph.col[:nnz].long(), gkey)
-                if ctx.needs_input_grad[0]:
-                    gX = gXp @ V[:, :module.d_in]
-                if ctx.needs_input_grad[1]:
-                    gVb = torch.cat([gXp.t() @ X.detach(), gkey.t() @ ef], dim=1)
-            if ctx.needs_input_grad[2]:
-                gfb = gf
-            if ctx.needs_input_grad[5]:
-                slot = graph.slot_of_edge[:edge_feat_rows(ctx)].long()
-                gslots = gkey @ V[:, module.d_in:]
-                gEf = torch.where((slot >= 0)[:, None], gslots[slot.clamp(min=0)], torch.zeros((), device=X.device))
-        elif S > 0 and (need_xp or ctx.needs_input_grad[2]):
-            gXp = torch.zeros((X.shape[0], ldp), dtype=torch.float32, device=X.device)
-            dtable = None
-            if prepared["unit_fast"]:
-                dtable = torch.empty_like(table)
-                _lib.check(L.fsw_unit_dcoeff_table(_lib.ptr(fr), S, _lib.REG_MAX_DEG, _lib.ptr(dtable), ldp, stream), "fsw_unit_dcoeff_table")
             scratch = None
             if st[_lib.STAT_NUM_GLOBAL] > 0:
                 scratch = torch.empty(int(L.fsw_embed_scratch_bytes(st[_lib.STAT_MAX_DEGREE])), dtype=torch.uint8, device=X.device)
             gf = torch.zeros(S, dtype=torch.float32, device=X.device)
             a = module.make_args(graph, st, Xp, ldp, fr, S, table, None, 0, None, out_scale, has_mass, scratch, slice_offset=ka)
-            nnz = st[_lib.STAT_NNZ]
-            if prepared["unit_fast"] and need_xp and 0 < nnz * S * 4 <= module.store_sum_budget(X.device):
-                # store-and-sum: every neighbour's key gradient is stored once (plain stores), then summed sender by sender over
-                # the sender-major entry list -- no float atomics, reproducible gradients
-                gkey = torch.empty((nnz, S), dtype=torch.float32, device=X.device)
-                cptr, order = graph.sender_major()
-                _lib.check(L.fsw_embed_backward_keys_f32(ctypes.byref(a), _lib.ptr(dtable), _lib.ptr(g), g.stride(0), _lib.ptr(gkey), S,
-                                                         _lib.ptr(gf), stream), "fsw_embed_backward_keys_f32")
-                _lib.check(L.fsw_segment_sum_rows_f32(_lib.ptr(gkey), S, _lib.ptr(cptr), _lib.ptr(order), graph.num_cols, nnz, S,
-                                                      _lib.ptr(gXp), ldp, stream), "fsw_segment_sum_rows_f32")
-                del gkey
+            if has_ef:
+                # edge features: the kernels store the gradient of every key; everything else is index_add + three GEMMs
+                gkey = torch.zeros((max(nnz, 1), S), dtype=torch.float32, device=X.device)
+                _lib.check(L.fsw_embed_backward_keys_f32(ctypes.byref(a), None, _lib.ptr(g), g.stride(0), _lib.ptr(gkey), S, _lib.ptr(gf),
+                                                         stream), "fsw_embed_backward_keys_f32")
+                gkey, ef = gkey[:nnz], graph.ef[:nnz]
+                if need_xp:
+                    gXp = torch.zeros((X.shape[0], S), dtype=torch.float32, device=X.device).index_add_(0, graph.col[:nnz].long(), gkey)
+                    if ctx.needs_input_grad[0]:
+                        gX = gXp @ V[:, :module.d_in]
+                    if ctx.needs_input_grad[1]:
+                        gVb = torch.cat([gXp.t() @ X.detach(), gkey.t() @ ef], dim=1)
+                if ctx.needs_input_grad[5]:
+                    slot = graph.slot_of_edge[:ctx.num_edge_rows].long()
+                    gslots = gkey @ V[:, module.d_in:]
+                    gEf = torch.where((slot >= 0)[:, None], gslots[slot.clamp(min=0)], torch.zeros((), device=X.device))
             else:
-                _lib.check(L.fsw_embed_backward_f32(ctypes.byref(a), _lib.ptr(dtable), _lib.ptr(g), g.stride(0), _lib.ptr(gXp), ldp,
-                                                    _lib.ptr(gf), stream), "fsw_embed_backward_f32")
-            if ctx.needs_input_grad[0]:
-                gX = _grad_x(L, gXp, S, ldp, V[:, :module.d_in], stream)
-            if ctx.needs_input_grad[1]:
-                gVb = gemm_tn(gXp[:, :S], X.detach())
+                gXp = torch.zeros((X.shape[0], ldp), dtype=torch.float32, device=X.device)
+                dtable = None
+                if prepared["unit_fast"]:
+                    dtable = torch.empty_like(table)
+                    _lib.check(L.fsw_unit_dcoeff_table(_lib.ptr(fr), S, _lib.REG_MAX_DEG, _lib.ptr(dtable), ldp, stream),
+                               "fsw_unit_dcoeff_table")
+                if prepared["unit_fast"] and need_xp and 0 < nnz * S * 4 <= module.store_sum_budget(X.device):
+                    # store-and-sum: every neighbour's key gradient is stored once (plain stores), then summed sender by sender over
+                    # the sender-major entry list -- no float atomics, reproducible gradients
+                    gkey = torch.empty((nnz, S), dtype=torch.float32, device=X.device)
+                    cptr, order = graph.sender_major()
+                    _lib.check(L.fsw_embed_backward_keys_f32(ctypes.byref(a), _lib.ptr(dtable), _lib.ptr(g), g.stride(0), _lib.ptr(gkey), S,
+                                                             _lib.ptr(gf), stream), "fsw_embed_backward_keys_f32")
+                    _lib.check(L.fsw_segment_sum_rows_f32(_lib.ptr(gkey), S, _lib.ptr(cptr), _lib.ptr(order), graph.num_cols, nnz, S,
+                                                          _lib.ptr(gXp), ldp, stream), "fsw_segment_sum_rows_f32")
+                    del gkey
+                else:
+                    _lib.check(L.fsw_embed_backward_f32(ctypes.byref(a), _lib.ptr(dtable), _lib.ptr(g), g.stride(0), _lib.ptr(gXp), ldp,
+                                                        _lib.ptr(gf), stream), "fsw_embed_backward_f32")
+                if ctx.needs_input_grad[0]:
+                    gX = _grad_x(L, gXp, S, ldp, V[:, :module.d_in], stream)
+                if ctx.needs_input_grad[1]:
+                    gVb = gemm_tn(gXp[:, :S], X.detach())
             if ctx.needs_input_grad[2]:
                 gfb = gf
         # block gradients -> full-size parameter gradients (zero outside the block), summed over the ranks when sharded
         if ctx.needs_input_grad[0] and gX is None:
             gX = torch.zeros_like(X)
         if ctx.needs_input_grad[5] and gEf is None:
-            gEf = torch.zeros((edge_feat_rows(ctx), module.d_edge), dtype=X.dtype, device=X.device)
+            gEf = torch.zeros((ctx.num_edge_rows, module.d_edge), dtype=X.dtype, device=X.device)
         if ctx.needs_input_grad[1]:
             gV = torch.zeros_like(Vfull)
             if gVb is not None:
@@ -264,7 +266,7 @@ class _EmbedGraphFn(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             gbias = torch.zeros(has_mass + module.nSlices, dtype=g.dtype, device=g.device)
             gb = out_scale * g.sum(dim=0)
-            if has_mass and ((not sharded) or dist_rank(group) == 0):
+            if has_mass and ((not sharded) or dist.get_rank(group) == 0):
                 gbias[0] = gb[0]                       # replicated column: counted once in the sum over the ranks
             gbias[has_mass + ka:has_mass + kb] = gb[has_mass:]
         if ctx.needs_input_grad[4]:
@@ -274,20 +276,28 @@ class _EmbedGraphFn(torch.autograd.Function):
             else:
                 rows = torch.repeat_interleave(torch.arange(graph.num_rows, device=X.device), deg)
                 m = torch.zeros(graph.num_rows, dtype=torch.float32, device=X.device).index_add_(0, rows, graph.w[:rows.numel()])
-            fn = module.total_mass_encoding_function
-            fm = m if fn == 'identity' else (2 * (m / (torch.sqrt(m + 1) + 1)) if fn == 'sqrt' else torch.log1p(m))
+            fm = _mass_f(module.total_mass_encoding_function, m)
             gscale = (out_scale * (g[:, 0] * fm).sum()).reshape(())     # identical on every rank: no reduction
         if sharded:
-            import torch.distributed as dist
             for t in (gX, gV, gfreqs, gbias, gEf):
                 if t is not None:
                     dist.all_reduce(t, group=group)
-        return gX, gV, gfreqs, gbias, gscale, gEf, None, None, None, None, None, None
+        return gX, gV, gfreqs, gbias, gscale, gEf, None, None, None, None, None, None, None
 
 
-def dist_rank(group):
-    import torch.distributed as dist
-    return dist.get_rank(group)
+def _flat_batch_index(idx, batch_dims):
+    """Row-major position in the flattened batch of every entry of a COO index matrix idx [len(batch_dims) + ..., nnz]."""
+    strides = torch.tensor(list(np.cumprod((batch_dims + (1,))[::-1])[::-1][1:]), device=idx.device, dtype=torch.int64)
+    return (idx[:len(batch_dims)] * strides[:, None]).sum(0)
+
+
+def _check_finite_nonnegative(Xf, wvals):
+    """Input validation of the generic paths (reference fsw_embedding.py:652-703); the tuned kernels check inside (_checked_stats)."""
+    if fsw_embedding_basic_safety_checks:
+        assert bool(torch.isfinite(Xf).all()), "The entries of X cannot contain NaNs or infs"
+        if wvals is not None:
+            assert bool(torch.isfinite(wvals).all()), "All entries of W must be finite"
+            assert bool((wvals >= 0).all()), "All entries of W must be nonnegative"
 
 
 class SimpleCSR:
@@ -309,100 +319,120 @@ class SimpleCSR:
                 "adjacency index out of range"
 
 
-def _generic_args(module, csr, Xp, ldp, Ke, freqs, wvals, out_scale, has_mass, mass_scale, scratch):
-    a = _lib.GenericArgs()
+def _value_args(a, module, Xp, ldp, freqs, S, out_scale, has_mass, mass_scale):
+    """The fields struct fsw_generic_args and struct fsw_cart_args have in common by name, for every entry point that takes one."""
     a.value_dtype = 1 if Xp.dtype == torch.float64 else 0
-    a.S = freqs.numel()
-    a.rowptr, a.col = csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None
-    a.w = wvals.data_ptr() if wvals is not None else None
-    a.num_rows, a.max_degree = csr.num_rows, csr.max_degree
-    a.Xp, a.ldp = Xp.data_ptr(), ldp
-    a.Ke, a.ldke = (Ke.data_ptr(), Ke.stride(0)) if Ke is not None else (None, 0)
-    a.freqs, a.tau = freqs.data_ptr(), float(module.total_mass_pad_thresh)
-    a.out_scale, a.has_mass = float(out_scale), has_mass
+    a.S, a.has_mass = S, has_mass
+    a.Xp, a.ldp, a.freqs = Xp.data_ptr(), ldp, freqs.data_ptr()
+    a.tau, a.out_scale = float(module.total_mass_pad_thresh), float(out_scale)
     a.mass_fn, a.mass_scale = _MASS_FN[module.total_mass_encoding_function], float(mass_scale)
-    a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
     return a
 
 
-class _GenericEmbedFn(torch.autograd.Function):
-    """out = out_scale * E(X, W) through the generic kernels (csrc/embed_generic.hip: any degree, float32 or float64 storage,
-    float64 arithmetic) with gradients for X, projVecs, freqs, bias, the total-mass scale, the WEIGHTS and the edge features.
+def _cart_args(module, Xp, ldp, freqs, S, out_scale, has_mass, mass_scale):
+    """struct fsw_cart_args with the fields both Cartesian entry points share."""
+    a = _value_args(_lib.CartArgs(), module, Xp, ldp, freqs, S, out_scale, has_mass, mass_scale)
+    a.F = module.nFreqs
+    return a
 
-    Two callers: every float64 module (the float64 build of the path, reference test_conv.py:24), and float32 modules whose
-    weights require a gradient (the tuned float32 backward kernels treat W as a constant).  Replaces the reference's sparse
-    autograd chain incl. ag.div_sparse_dense.backward (fsw_embedding.py:1656), ag.cumsum_sparse.backward (:2160, the reverse
-    segmented cumsum) and ag.permute_sparse.backward (:1286)."""
+
+def _project(X, V, d_in, S, ldp):
+    """Xp [n, ldp] = X . V[:, :d_in]^T in the dtype of X, without the by-products of the tuned forward (stats, copy of X)."""
+    L = _lib.lib()
+    stream = torch.cuda.current_stream(X.device).cuda_stream
+    Xp = torch.empty((X.shape[0], ldp), dtype=X.dtype, device=X.device)
+    if X.dtype == torch.float64:
+        _lib.check(L.fsw_project_f64(_lib.ptr(X), X.shape[0], d_in, X.stride(0), _lib.ptr(V), S, V.stride(0), _lib.ptr(Xp), ldp,
+                                     None, stream), "fsw_project_f64")
+    else:
+        _lib.check(L.fsw_project_f32(_lib.ptr(X), X.shape[0], d_in, X.stride(0), _lib.ptr(V), S, V.stride(0), _lib.ptr(Xp), ldp,
+                                     None, 0, None, stream), "fsw_project_f32")
+    return Xp
+
+
+class _GenericEmbedFn(torch.autograd.Function):
+    """out = out_scale * E(X, W) through the generic kernels (any degree, float32 or float64 storage, float64 arithmetic) with
+    gradients for X, projVecs, freqs, bias, the total-mass scale, the WEIGHTS and the edge features.  module.cartesian_mode picks
+    the entry point (`variant`); everything else is the same code for both:
+
+      fsw_embed_generic (csrc/embed_generic.hip): out [num_rows, has_mass + S], slice s read out at frequency s.
+      fsw_embed_cart_generic (csrc/embed_cart.hip): out [num_rows, has_mass + S F], column has_mass + s F + f = (slice s,
+        frequency f); bias flattened, gkey one column per slice, gf one entry per frequency; efvals is always None (no edge features).
+
+    Callers: every float64 module (the float64 build of the path, reference test_conv.py:24), float32 modules whose weights or
+    sparse edge features require a gradient (the tuned float32 backward kernels treat W as a constant), and Cartesian mode under
+    autograd.  Replaces the reference's sparse autograd chain incl. ag.div_sparse_dense.backward (fsw_embedding.py:1656),
+    ag.cumsum_sparse.backward (:2160, the reverse segmented cumsum) and ag.permute_sparse.backward (:1286)."""
+
+    @staticmethod
+    def variant(module):
+        """(args struct, entry point, rounding of the projection stride ldp)"""
+        if module.cartesian_mode:
+            return _lib.CartArgs, "fsw_embed_cart_generic", 32
+        return _lib.GenericArgs, "fsw_embed_generic", 64
+
+    @staticmethod
+    def launch(module, csr, aux, freqs, out_scale, mass_scale, what="", **fields):
+        """One call of the entry point: `fields` are out / ldo / bias (forward) or g / ldg / gkey / ldk / gfreq / gw (backward)."""
+        L = _lib.lib()
+        args_t, entry, _ = _GenericEmbedFn.variant(module)
+        Xp, ldp, Ke, wv = aux
+        scratch = torch.empty(int(getattr(L, entry + "_scratch_bytes")(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8,
+                              device=Xp.device)
+        a = _value_args(args_t(), module, Xp, ldp, freqs, module.nSlices, out_scale, module.total_mass_encoding_dim, mass_scale)
+        if module.cartesian_mode:
+            a.F = module.nFreqs
+        else:
+            a.Ke, a.ldke = (Ke.data_ptr(), Ke.stride(0)) if Ke is not None else (None, 0)
+        a.rowptr, a.col = csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None
+        a.w = wv.data_ptr() if wv is not None else None
+        a.num_rows, a.max_degree = csr.num_rows, csr.max_degree
+        a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        for name, value in fields.items():
+            setattr(a, name, value)
+        _lib.check(getattr(L, entry)(ctypes.byref(a), torch.cuda.current_stream(Xp.device).cuda_stream), entry + what)
 
     @staticmethod
     def forward(ctx, X, V, freqs, bias, mass_scale, wvals, efvals, module, csr, out_scale):
-        L = _lib.lib()
-        dev, dt = X.device, X.dtype
-        stream = torch.cuda.current_stream(dev).cuda_stream
         S, d_in = module.nSlices, module.d_in
-        has_mass = 1 if module.encode_total_mass else 0
         with torch.no_grad():
             Xc, Vd, fr = X.detach().contiguous(), V.detach(), freqs.detach().contiguous()
-            ldp = _round_up(S, 64)
-            Xp = torch.empty((Xc.shape[0], ldp), dtype=dt, device=dev)
-            if dt == torch.float64:
-                _lib.check(L.fsw_project_f64(_lib.ptr(Xc), Xc.shape[0], d_in, Xc.stride(0), _lib.ptr(Vd), S, Vd.stride(0), _lib.ptr(Xp), ldp,
-                                             None, stream), "fsw_project_f64")
-            else:
-                _lib.check(L.fsw_project_f32(_lib.ptr(Xc), Xc.shape[0], d_in, Xc.stride(0), _lib.ptr(Vd), S, Vd.stride(0), _lib.ptr(Xp), ldp,
-                                             None, 0, None, stream), "fsw_project_f32")
+            ldp = _round_up(S, _GenericEmbedFn.variant(module)[2])
+            Xp = _project(Xc, Vd, d_in, S, ldp)
             Ke = None
             if efvals is not None:
                 Ke = (efvals.detach() @ Vd[:, d_in:].t()).contiguous()        # [nnz, S], the reference's E x S edge term (:934-968)
             wv = wvals.detach().contiguous() if wvals is not None else None
-            scratch = torch.empty(int(L.fsw_embed_generic_scratch_bytes(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8, device=dev)
-            out = torch.empty((csr.num_rows, has_mass + S), dtype=dt, device=dev)
+            out = torch.empty((csr.num_rows, module.d_out), dtype=X.dtype, device=X.device)
             ms = float(mass_scale.detach()) if mass_scale is not None else 1.0
-            a = _generic_args(module, csr, Xp, ldp, Ke, fr, wv, out_scale, has_mass, ms, scratch)
-            a.out, a.ldo = out.data_ptr(), out.stride(0)
             b = bias.detach().contiguous() if bias is not None else None
-            a.bias = b.data_ptr() if b is not None else None
-            _lib.check(L.fsw_embed_generic(ctypes.byref(a), stream), "fsw_embed_generic")
+            ctx.aux = (Xp, ldp, Ke, wv)
+            _GenericEmbedFn.launch(module, csr, ctx.aux, fr, out_scale, ms, out=out.data_ptr(), ldo=out.stride(0),
+                                   bias=b.data_ptr() if b is not None else None)
         ctx.module, ctx.csr, ctx.out_scale, ctx.mass_scale_value = module, csr, float(out_scale), ms
-        ctx.aux = (Xp, ldp, Ke, wv)
         ctx.has_ef, ctx.has_w = efvals is not None, wvals is not None
         ctx.save_for_backward(X, V, freqs, efvals if efvals is not None else X.new_zeros(0))
         return out
 
     @staticmethod
+    def key_grads(ctx, g, gkey, gf, gw):
+        """The entry point in backward mode: stores gkey [nnz, S], accumulates gf [nFreqs] and gw [nnz] (each nullable)."""
+        freqs = ctx.saved_tensors[2]
+        _GenericEmbedFn.launch(ctx.module, ctx.csr, ctx.aux, freqs.detach().contiguous(), ctx.out_scale, ctx.mass_scale_value,
+                               " (backward)", g=g.data_ptr(), ldg=g.stride(0),
+                               gkey=gkey.data_ptr() if gkey is not None else None, ldk=gkey.shape[1] if gkey is not None else 0,
+                               gfreq=gf.data_ptr() if gf is not None else None, gw=gw.data_ptr() if gw is not None else None)
+
+    @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        return _GenericEmbedFn.host_backward(ctx, g.contiguous(), _GenericEmbedFn.key_grads)
-
-    @staticmethod
-    def key_grads(ctx, g, gkey, gf, gw):
-        """fsw_embed_generic in backward mode: stores gkey [nnz, S], accumulates gf [S] and gw [nnz] (each nullable)."""
-        L = _lib.lib()
-        module, csr = ctx.module, ctx.csr
-        X, V, freqs, efvals = ctx.saved_tensors
-        Xp, ldp, Ke, wv = ctx.aux
-        dev = X.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        has_mass = 1 if module.encode_total_mass else 0
-        scratch = torch.empty(int(L.fsw_embed_generic_scratch_bytes(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8, device=dev)
-        a = _generic_args(module, csr, Xp, ldp, Ke, freqs.detach().contiguous(), wv, ctx.out_scale, has_mass, ctx.mass_scale_value, scratch)
-        a.g, a.ldg = g.data_ptr(), g.stride(0)
-        a.gkey, a.ldk = (gkey.data_ptr(), gkey.shape[1]) if gkey is not None else (None, 0)
-        a.gfreq = gf.data_ptr() if gf is not None else None
-        a.gw = gw.data_ptr() if gw is not None else None
-        _lib.check(L.fsw_embed_generic(ctypes.byref(a), stream), "fsw_embed_generic (backward)")
-
-    @staticmethod
-    def host_backward(ctx, g, key_grads):
-        """Everything of the backward but the kernel call key_grads(ctx, g, gkey, gf, gw): the GEMMs of gX and gprojVecs, the
-        bias, total-mass scale and weight gradients.  Shared with _CartesianEmbedFn (gkey has one column per slice, gf one
-        entry per frequency)."""
+        """The kernel call key_grads, then the GEMMs of gX and gprojVecs, the bias, total-mass scale and weight gradients."""
+        g = g.contiguous()
         module, csr, out_scale = ctx.module, ctx.csr, ctx.out_scale
         X, V, freqs, efvals = ctx.saved_tensors
-        Xp, ldp, Ke, wv = ctx.aux
+        wv = ctx.aux[3]
         dev, dt = X.device, X.dtype
         S, d_in = module.nSlices, module.d_in
-        has_mass = 1 if module.encode_total_mass else 0
         need = ctx.needs_input_grad
         gX = gV = gfreqs = gbias = gscale = gW = gEf = None
         nnz = csr.nnz
@@ -412,7 +442,7 @@ class _GenericEmbedFn(torch.autograd.Function):
             gkey = torch.zeros((nnz, S), dtype=dt, device=dev) if want_key else None
             gf = torch.zeros(freqs.numel(), dtype=dt, device=dev) if need[2] else None
             gw = torch.zeros(nnz, dtype=dt, device=dev) if want_w else None
-            key_grads(ctx, g, gkey, gf, gw)
+            _GenericEmbedFn.key_grads(ctx, g, gkey, gf, gw)
             Vd = V.detach()
             if need[0] or need[1]:
                 gXp = torch.zeros((X.shape[0], S), dtype=dt, device=dev).index_add_(0, csr.col.long(), gkey)
@@ -435,102 +465,19 @@ class _GenericEmbedFn(torch.autograd.Function):
             gEf = torch.zeros_like(efvals)
         if need[3]:
             gbias = out_scale * g.sum(dim=0)
-        if has_mass and (need[4] or want_w):
+        if module.encode_total_mass and (need[4] or want_w):
             m = torch.zeros(csr.num_rows, dtype=dt, device=dev)
             if nnz:
                 m.index_add_(0, csr.rec, wv if wv is not None else torch.ones(nnz, dtype=dt, device=dev))
             fn = module.total_mass_encoding_function
             if need[4]:
-                fm = m if fn == 'identity' else (2 * (m / (torch.sqrt(m + 1) + 1)) if fn == 'sqrt' else torch.log1p(m))
-                gscale = (out_scale * (g[:, 0] * fm).sum()).reshape(())
+                gscale = (out_scale * (g[:, 0] * _mass_f(fn, m)).sum()).reshape(())
             if want_w:      # the total-mass column depends on the weights through m
-                dfm = torch.ones_like(m) if fn == 'identity' else (1 / torch.sqrt(m + 1) if fn == 'sqrt' else 1 / (1 + m))
-                gW = (gW if gW is not None else torch.zeros(nnz, dtype=dt, device=dev)) + (out_scale * ctx.mass_scale_value * g[:, 0] * dfm)[csr.rec]
+                gW = (gW if gW is not None else torch.zeros(nnz, dtype=dt, device=dev)) + (
+                    out_scale * ctx.mass_scale_value * g[:, 0] * _mass_df(fn, m))[csr.rec]
         if want_w and gW is None:
             gW = torch.zeros(nnz, dtype=dt, device=dev)
         return gX, gV, gfreqs, gbias, gscale, gW, gEf, None, None, None
-
-
-def _cart_args(module, Xp, ldp, freqs, S, out_scale, has_mass, mass_scale):
-    """struct fsw_cart_args with the fields both Cartesian entry points share."""
-    a = _lib.CartArgs()
-    a.value_dtype = 1 if Xp.dtype == torch.float64 else 0
-    a.S, a.F, a.has_mass = S, module.nFreqs, has_mass
-    a.Xp, a.ldp, a.freqs = Xp.data_ptr(), ldp, freqs.data_ptr()
-    a.tau, a.out_scale = float(module.total_mass_pad_thresh), float(out_scale)
-    a.mass_fn, a.mass_scale = _MASS_FN[module.total_mass_encoding_function], float(mass_scale)
-    return a
-
-
-class _CartesianEmbedFn(torch.autograd.Function):
-    """Cartesian mode through the generic kernel (csrc/embed_cart.hip, fsw_embed_cart_generic: any degree, float32 or float64
-    storage, float64 arithmetic): out [num_rows, has_mass + S F], column has_mass + s F + f = (slice s, frequency f).  Gradients
-    for X, projVecs, freqs, bias (flattened), the total-mass scale and the weights; the host side of the backward is
-    _GenericEmbedFn.host_backward.  Same arguments as _GenericEmbedFn (efvals is always None: no edge features here)."""
-
-    @staticmethod
-    def forward(ctx, X, V, freqs, bias, mass_scale, wvals, efvals, module, csr, out_scale):
-        L = _lib.lib()
-        dev, dt = X.device, X.dtype
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        S, d_in = module.nSlices, module.d_in
-        has_mass = 1 if module.encode_total_mass else 0
-        with torch.no_grad():
-            Xc, Vd, fr = X.detach().contiguous(), V.detach(), freqs.detach().contiguous()
-            ldp = _round_up(S, 32)
-            Xp = torch.empty((Xc.shape[0], ldp), dtype=dt, device=dev)
-            if dt == torch.float64:
-                _lib.check(L.fsw_project_f64(_lib.ptr(Xc), Xc.shape[0], d_in, Xc.stride(0), _lib.ptr(Vd), S, Vd.stride(0), _lib.ptr(Xp), ldp,
-                                             None, stream), "fsw_project_f64")
-            else:
-                _lib.check(L.fsw_project_f32(_lib.ptr(Xc), Xc.shape[0], d_in, Xc.stride(0), _lib.ptr(Vd), S, Vd.stride(0), _lib.ptr(Xp), ldp,
-                                             None, 0, None, stream), "fsw_project_f32")
-            wv = wvals.detach().contiguous() if wvals is not None else None
-            out = torch.empty((csr.num_rows, module.d_out), dtype=dt, device=dev)
-            ms = float(mass_scale.detach()) if mass_scale is not None else 1.0
-            scratch = torch.empty(int(L.fsw_embed_cart_generic_scratch_bytes(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8,
-                                  device=dev)
-            b = bias.detach().contiguous() if bias is not None else None
-            a = _CartesianEmbedFn.args(module, csr, Xp, ldp, fr, wv, out_scale, has_mass, ms, scratch)
-            a.out, a.ldo = out.data_ptr(), out.stride(0)
-            a.bias = b.data_ptr() if b is not None else None
-            _lib.check(L.fsw_embed_cart_generic(ctypes.byref(a), stream), "fsw_embed_cart_generic")
-        ctx.module, ctx.csr, ctx.out_scale, ctx.mass_scale_value = module, csr, float(out_scale), ms
-        ctx.aux = (Xp, ldp, None, wv)
-        ctx.has_ef, ctx.has_w = False, wvals is not None
-        ctx.save_for_backward(X, V, freqs, X.new_zeros(0))
-        return out
-
-    @staticmethod
-    def args(module, csr, Xp, ldp, freqs, wv, out_scale, has_mass, mass_scale, scratch):
-        a = _cart_args(module, Xp, ldp, freqs, module.nSlices, out_scale, has_mass, mass_scale)
-        a.rowptr, a.col = csr.rowptr.data_ptr(), csr.col.data_ptr() if csr.nnz else None
-        a.w = wv.data_ptr() if wv is not None else None
-        a.num_rows, a.max_degree = csr.num_rows, csr.max_degree
-        a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
-        return a
-
-    @staticmethod
-    def key_grads(ctx, g, gkey, gf, gw):
-        L = _lib.lib()
-        module, csr = ctx.module, ctx.csr
-        X, V, freqs, _ = ctx.saved_tensors
-        Xp, ldp, _, wv = ctx.aux
-        stream = torch.cuda.current_stream(X.device).cuda_stream
-        scratch = torch.empty(int(L.fsw_embed_cart_generic_scratch_bytes(csr.max_degree, max(csr.num_rows, 1))), dtype=torch.uint8,
-                              device=X.device)
-        a = _CartesianEmbedFn.args(module, csr, Xp, ldp, freqs.detach().contiguous(), wv, ctx.out_scale,
-                                   1 if module.encode_total_mass else 0, ctx.mass_scale_value, scratch)
-        a.g, a.ldg = g.data_ptr(), g.stride(0)
-        a.gkey, a.ldk = (gkey.data_ptr(), gkey.shape[1]) if gkey is not None else (None, 0)
-        a.gfreq = gf.data_ptr() if gf is not None else None
-        a.gw = gw.data_ptr() if gw is not None else None
-        _lib.check(L.fsw_embed_cart_generic(ctypes.byref(a), stream), "fsw_embed_cart_generic (backward)")
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        return _GenericEmbedFn.host_backward(ctx, g.contiguous(), _CartesianEmbedFn.key_grads)
 
 
 class FSW_embedding(nn.Module):
@@ -799,8 +746,7 @@ class FSW_embedding(nn.Module):
                 # is element j of multiset b; absent entries are absent elements (weight 0)
                 idx, wvals = W.indices(), W.values()
                 if batch_dims:
-                    strides = torch.tensor(list(np.cumprod((batch_dims + (1,))[::-1])[::-1][1:]), device=X.device, dtype=torch.int64)
-                    rec = (idx[:len(batch_dims)] * strides[:, None]).sum(0)
+                    rec = _flat_batch_index(idx, batch_dims)
                 else:
                     rec = torch.zeros(idx.shape[1], device=X.device, dtype=torch.int64)
                 snd = (rec * n + idx[-1]).contiguous()
@@ -833,11 +779,7 @@ class FSW_embedding(nn.Module):
                     efvals = X_edge[tuple(idx)].reshape(wvals.shape[0], -1)
             if self.d_edge > 0:
                 assert efvals.shape[1] == self.d_edge, 'X_edge must carry d_edge features per edge'
-            if batch_dims:
-                strides = torch.tensor(list(np.cumprod((batch_dims + (1,))[::-1])[::-1][1:]), device=X.device, dtype=torch.int64)
-                b = (idx[:len(batch_dims)] * strides[:, None]).sum(0)
-            else:
-                b = 0
+            b = _flat_batch_index(idx, batch_dims) if batch_dims else 0
             rec = (b * nR + idx[-2]).contiguous()
             snd = (b * n + idx[-1]).contiguous()
             Xf = X.reshape(B * n, d)
@@ -850,7 +792,10 @@ class FSW_embedding(nn.Module):
         if generic and num_rows > 0 and Xf.shape[0] > 0:
             if self.d_out == 0:
                 return torch.zeros(out_shape + (0,), dtype=X.dtype, device=X.device)
-            return self._forward_generic(Xf.contiguous(), rec, snd, wvals, efvals, num_rows).reshape(out_shape + (self.d_out,))
+            if self.nSlices == 0:
+                raise NotImplementedError("fsw_gnn_amd: nSlices == 0 with encode_total_mass is not supported")
+            bias = self.bias if self.enable_bias else None
+            return self._forward_generic(Xf.contiguous(), rec, snd, wvals, efvals, num_rows, bias).reshape(out_shape + (self.d_out,))
         if num_rows == 0 or Xf.shape[0] == 0:
             # nothing to embed / empty multisets only: the reference returns an empty tensor, resp. the embedding of the
             # pad element alone; the kernels need at least one row and one point
@@ -868,19 +813,13 @@ class FSW_embedding(nn.Module):
             self.embed_into(Xf, graph, out, out_scale=1.0, serialize_num_slices=serialize_num_slices)
         return out.reshape(out_shape + (self.d_out,))
 
-    def _forward_generic(self, Xf, rec, snd, wvals, efvals, num_rows):
-        """The generic-kernel path (float64 modules; float32 with gradients of W / X_edge): differentiable in everything."""
-        if self.nSlices == 0:
-            raise NotImplementedError("fsw_gnn_amd: nSlices == 0 with encode_total_mass is not supported")
-        if fsw_embedding_basic_safety_checks:      # reference fsw_embedding.py:652-703
-            assert bool(torch.isfinite(Xf).all()), "The entries of X cannot contain NaNs or infs"
-            if wvals is not None:
-                assert bool(torch.isfinite(wvals).all()), "All entries of W must be finite"
-                assert bool((wvals >= 0).all()), "All entries of W must be nonnegative"
+    def _forward_generic(self, Xf, rec, snd, wvals, efvals, num_rows, bias):
+        """The generic-kernel path (float64 modules; float32 with gradients of W / X_edge; Cartesian mode under autograd):
+        differentiable in everything.  bias (flattened): in the kernel for the 'plain' method, in the torch epilogue otherwise."""
+        _check_finite_nonnegative(Xf, wvals)
         csr = SimpleCSR(rec, snd, num_rows, Xf.shape[0])
-        bias = self.bias if self.enable_bias else None
         scale = self.total_mass_encoding_scale if self.encode_total_mass else None
-        plain = (not self.encode_total_mass) or self.total_mass_encoding_method == 'plain'
+        plain = self.plain_mass
         P = _GenericEmbedFn.apply(Xf, self.projVecs, self.freqs, bias if plain else None, scale, wvals, efvals, self, csr, 1.0)
         return P if plain else self._homog_epilogue(P, 1.0, bias)
 
@@ -894,23 +833,14 @@ class FSW_embedding(nn.Module):
         if S * F == 0:
             raise NotImplementedError("fsw_gnn_amd: Cartesian mode with nSlices * nFreqs == 0 and encode_total_mass is not supported")
         bias = self.bias.reshape(-1) if self.enable_bias else None
-        plain = (not self.encode_total_mass) or self.total_mass_encoding_method == 'plain'
+        plain = self.plain_mass
         if Xf.shape[0] == 0:
             # empty multisets only: the embedding of the pad element alone is 0 and so is f(0) for every mass encoding and method,
             # which leaves the bias (any dtype; differentiable in the bias)
             Z = torch.zeros((num_rows, self.d_out), dtype=dt, device=dev)
             return Z + bias if bias is not None else Z
         if generic:
-            if fsw_embedding_basic_safety_checks:      # reference fsw_embedding.py:652-703
-                assert bool(torch.isfinite(Xf).all()), "The entries of X cannot contain NaNs or infs"
-                if wvals is not None:
-                    assert bool(torch.isfinite(wvals).all()), "All entries of W must be finite"
-                    assert bool((wvals >= 0).all()), "All entries of W must be nonnegative"
-            csr = SimpleCSR(rec, snd, num_rows, Xf.shape[0])
-            scale = self.total_mass_encoding_scale if self.encode_total_mass else None
-            P = _CartesianEmbedFn.apply(Xf.contiguous(), self.projVecs, self.freqs, bias if plain else None, scale, wvals, None, self,
-                                        csr, 1.0)
-            return P if plain else self._homog_epilogue(P, 1.0, bias)
+            return self._forward_generic(Xf.contiguous(), rec, snd, wvals, None, num_rows, bias)
         graph = build_csr(rec, snd, wvals.contiguous() if wvals is not None else None, num_rows, Xf.shape[0])
         with torch.no_grad():
             out = torch.empty((num_rows, self.d_out), dtype=dt, device=dev)
@@ -925,7 +855,7 @@ class FSW_embedding(nn.Module):
         L = _lib.lib()
         dev = X.device
         S, F = self.nSlices, self.nFreqs
-        has_mass = 1 if self.encode_total_mass else 0
+        has_mass = self.total_mass_encoding_dim
         assert X.is_contiguous() and X.dtype == torch.float32 and out.stride(1) == 1 and out.shape[0] == graph.num_rows
         assert out.shape[1] >= has_mass + S * F and graph.num_chunks == 1
         step = S if (serialize_num_slices is None or serialize_num_slices >= S) else int(serialize_num_slices)
@@ -936,7 +866,7 @@ class FSW_embedding(nn.Module):
         fr = self.freqs.detach().contiguous()
         V = self.projVecs.detach()
         table = None
-        if graph.w is None and self.total_mass_pad_thresh <= 1.0:
+        if self._unit_fast(graph):
             table = torch.empty((int(L.fsw_unit_table_rows(_lib.REG_MAX_DEG)), F), dtype=torch.float32, device=dev)
             _lib.check(L.fsw_unit_coeff_table(_lib.ptr(fr), F, _lib.REG_MAX_DEG, _lib.ptr(table), F, stream), "fsw_unit_coeff_table")
         st = None
@@ -955,8 +885,7 @@ class FSW_embedding(nn.Module):
                                           dtype=torch.uint8, device=dev)
             first = k0 == 0
             col0 = 0 if first else has_mass + k0 * F
-            ms = struct.unpack('f', struct.pack('i', st[_lib.STAT_USER]))[0] if self.encode_total_mass else 1.0
-            a = _cart_args(self, Xp, ldp, fr, k1 - k0, out_scale, has_mass if first else 0, ms)
+            a = _cart_args(self, Xp, ldp, fr, k1 - k0, out_scale, has_mass if first else 0, self._mass_scale_read(st))
             a.rowptr, a.col = graph.rowptr.data_ptr(), graph.col.data_ptr()
             a.w = graph.w.data_ptr() if graph.w is not None else None
             a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), bsh.ctypes.data
@@ -969,19 +898,28 @@ class FSW_embedding(nn.Module):
             _lib.check(L.fsw_embed_cart_f32(ctypes.byref(a), stream), "fsw_embed_cart_f32")
         return out
 
-    def _homog_epilogue(self, P, out_scale, bias):
-        """'homog' / 'homog_alt' (reference fsw_embedding.py:874-882, 1136-1144) on the 'plain' embedding P = [f(m) scale | emb]
-        without bias, out of place so that autograd differentiates it."""
+    def _homog_epilogue(self, P, out_scale, bias, in_place=False):
+        """'homog' / 'homog_alt' (reference fsw_embedding.py:874-882, 1136-1144) on the 'plain' embedding without bias that the
+        kernels wrote into the left d_out columns of P = [f(m) scale | emb]: rarely used epilogues, done with elementwise torch ops.
+        Out of place (autograd differentiates it), or in_place on P without a full-size temporary (inference)."""
+        emb = P[:, 1:self.d_out]
         tm = P[:, 0:1] / out_scale
-        emb = P[:, 1:]
         norm = emb.abs().mean(dim=-1, keepdim=True) / out_scale
         if self.total_mass_encoding_method == 'homog':
-            col0 = out_scale * tm * norm
+            col0, factor = out_scale * tm * norm, None
         else:
             col0 = out_scale * torch.where(tm <= 1, tm * (2 - tm), torch.ones_like(tm)) * norm
-            emb = emb * torch.where(tm <= 1, tm.square(), 2 * tm - 1)
-        out = torch.cat([col0, emb], dim=1)
-        return out + out_scale * bias if bias is not None else out
+            factor = torch.where(tm <= 1, tm.square(), 2 * tm - 1)      # one per row
+        if in_place:
+            P[:, 0:1] = col0
+            if factor is not None:
+                emb.mul_(factor)
+            out = P[:, :self.d_out]
+        else:
+            out = torch.cat([col0, emb if factor is None else emb * factor], dim=1)
+        if bias is not None:
+            out = out.add_(out_scale * bias) if in_place else out + out_scale * bias
+        return P if in_place else out
 
     def embed_autograd(self, X, graph, out_scale=1.0, edge_feat=None, slice_range=None, group=None, reduce_grads=False):
         """Differentiable embedding of a CSR graph (training path): see _EmbedGraphFn.  edge_feat: the per-input-edge
@@ -989,18 +927,14 @@ class FSW_embedding(nn.Module):
         slice_range / group: this rank's block of slices under slice sharding (dist.py)."""
         bias = self.bias if self.enable_bias else None
         scale = self.total_mass_encoding_scale if self.encode_total_mass else None
-        if (not self.encode_total_mass) or self.total_mass_encoding_method == 'plain':
+        if self.plain_mass:
             return _EmbedGraphFn.apply(X, self.projVecs, self.freqs, bias, scale, edge_feat, self, graph, out_scale, slice_range, group,
-                                       reduce_grads)
+                                       reduce_grads, True)
         if slice_range is not None:
             raise NotImplementedError("slice sharding supports total_mass_encoding_method='plain' only")
         # 'homog' / 'homog_alt' (reference fsw_embedding.py:874-882, 1136-1144): the 'plain' embedding without bias from the
         # kernels, then the same epilogue as embed_into(), out of place so that autograd differentiates it
-        self._force_plain = True
-        try:
-            P = _EmbedGraphFn.apply(X, self.projVecs, self.freqs, None, scale, edge_feat, self, graph, out_scale, None, None, False)
-        finally:
-            self._force_plain = False
+        P = _EmbedGraphFn.apply(X, self.projVecs, self.freqs, None, scale, edge_feat, self, graph, out_scale, None, None, False, False)
         return self._homog_epilogue(P, out_scale, bias)
 
     # ------------------------------------------------------------------------------------------------
@@ -1023,7 +957,19 @@ class FSW_embedding(nn.Module):
         except Exception:   # noqa: BLE001 -- no query, keep the fixed ceiling
             pass
         return cap
-    _force_plain = False   # embed_autograd: 'plain' mass column and no bias from the kernels, epilogue in torch
+
+    @property
+    def plain_mass(self):
+        """The kernels' output is final: no total-mass column, or the 'plain' method (no 'homog' / 'homog_alt' epilogue)."""
+        return (not self.encode_total_mass) or self.total_mass_encoding_method == 'plain'
+
+    def _unit_fast(self, graph):
+        """Unit weights and no padding above one element: the coefficients depend on the degree alone (unit coefficient table)."""
+        return graph.w is None and self.total_mass_pad_thresh <= 1.0
+
+    def _mass_scale_read(self, st):
+        """The total-mass scale as _checked_stats parked it in the stats words st (float32 bits in an int)."""
+        return struct.unpack('f', struct.pack('i', st[_lib.STAT_USER]))[0] if self.encode_total_mass else 1.0
 
     def prepare(self, X, graph: CSRGraph, x_copy=None, linear2=None, slice_range=None):
         """Projection of a block of slices (default: all) + (unit weights) coefficient table + the one device->host stats
@@ -1038,41 +984,52 @@ class FSW_embedding(nn.Module):
         Returns a dict that embed_into(prepared=...) or FSW_conv's fused Linear path consume.  Input validation
         (reference fsw_embedding.py:652-703) happens here: the kernels set flag bits, the host reads them once.
         """
-        L = _lib.lib()
-        dev = X.device
         ka, kb = (0, self.nSlices) if slice_range is None else slice_range
         assert 0 <= ka <= kb <= self.nSlices, 'bad slice_range'
-        S = kb - ka
         assert X.is_contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        unit_fast = graph.w is None and self.total_mass_pad_thresh <= 1.0
-        if S == 0:      # a rank without slices (more ranks than slices): only the stats
+        unit_fast = self._unit_fast(graph)
+        if kb == ka:      # a rank without slices (more ranks than slices): only the stats
             if x_copy is not None:
                 x_copy.copy_(X)
             return {"Xp": None, "ldp": 0, "table": None, "stats": self._checked_stats(graph), "unit_fast": unit_fast,
                     "slice_range": (ka, kb)}
-        ldp = _round_up(S, 64)
-        Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=dev)
+        ldp, Xp, table = self._projection_buffers(X, kb - ka, unit_fast)
+        self._project_slices(X, graph, ka, kb, Xp, ldp, table, x_copy, linear2)
+        st = self._checked_stats(graph)
+        return {"Xp": Xp, "ldp": ldp, "table": table, "stats": st, "unit_fast": unit_fast, "slice_range": (ka, kb)}
+
+    def _projection_buffers(self, X, width, unit_fast):
+        """(ldp, Xp [num_cols, ldp], unit coefficient table [rows, ldp] or None) for projections of up to `width` slices at a time."""
+        ldp = _round_up(width, 64)
+        Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=X.device)
+        table = None
+        if unit_fast:
+            table = torch.empty((int(_lib.lib().fsw_unit_table_rows(_lib.REG_MAX_DEG)), ldp), dtype=torch.float32, device=X.device)
+        return ldp, Xp, table
+
+    def _project_slices(self, X, graph, ka, kb, Xp, ldp, table, x_copy=None, linear2=None, first=True):
+        """Xp[:, :kb - ka] = X . projVecs[ka:kb]^T and (table given) the unit coefficient table of freqs[ka:kb].  The by-products
+        -- the input flags into graph.stats_dev, the copy of X into x_copy -- belong to the `first` projection of a forward."""
+        L = _lib.lib()
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        S = kb - ka
         V = self.projVecs.detach()[ka:kb]
+        stats = _lib.ptr(graph.stats_dev) if first else None
         if linear2 is not None:
             W2, b2, Y2 = linear2
             assert x_copy is None and W2.is_contiguous() and W2.shape[1] == self.d_in and Y2.stride(1) == 1
             rc = L.fsw_project_linear_f32(_lib.ptr(X), X.shape[0], self.d_in, X.stride(0), _lib.ptr(V), S, V.stride(0),
                                           _lib.ptr(Xp), ldp, _lib.ptr(W2), W2.shape[0], W2.stride(0), _lib.ptr(b2),
-                                          _lib.ptr(Y2), Y2.stride(0), _lib.ptr(graph.invperm), _lib.ptr(graph.stats_dev), stream)
+                                          _lib.ptr(Y2), Y2.stride(0), _lib.ptr(graph.invperm), stats, stream)
         else:
             rc = L.fsw_project_f32(_lib.ptr(X), X.shape[0], self.d_in, X.stride(0), _lib.ptr(V), S, V.stride(0), _lib.ptr(Xp),
-                                   ldp, _lib.ptr(x_copy), x_copy.stride(0) if x_copy is not None else 0,
-                                   _lib.ptr(graph.stats_dev), stream)
+                                   ldp, _lib.ptr(x_copy) if first else None, x_copy.stride(0) if x_copy is not None else 0,
+                                   stats, stream)
         _lib.check(rc, "fsw_project_f32")
-        table = None
-        if unit_fast:
-            table = torch.empty((int(L.fsw_unit_table_rows(_lib.REG_MAX_DEG)), ldp), dtype=torch.float32, device=dev)
+        if table is not None:
             fr = self.freqs.detach()[ka:kb]
             rc = L.fsw_unit_coeff_table(_lib.ptr(fr), S, _lib.REG_MAX_DEG, _lib.ptr(table), ldp, stream)
             _lib.check(rc, "fsw_unit_coeff_table")
-        st = self._checked_stats(graph)
-        return {"Xp": Xp, "ldp": ldp, "table": table, "stats": st, "unit_fast": unit_fast, "slice_range": (ka, kb)}
 
     def _checked_stats(self, graph):
         """The one device->host copy of a forward: validation flags, degree-class counts and -- parked in the spare stats
@@ -1113,7 +1070,7 @@ class FSW_embedding(nn.Module):
         a.out, a.ldo, a.bias = out_ptr, ldo, bias_ptr
         a.out_scale, a.has_mass = float(out_scale), has_mass
         a.mass_fn = _MASS_FN[self.total_mass_encoding_function]
-        a.mass_scale = struct.unpack('f', struct.pack('i', st[_lib.STAT_USER]))[0] if self.encode_total_mass else 1.0
+        a.mass_scale = self._mass_scale_read(st)
         a.num_reg_rows, a.num_lds_rows = min(st[_lib.STAT_NUM_REG], rows), min(st[_lib.STAT_NUM_LDS], rows)
         a.num_global_rows, a.num_zero_rows = min(st[_lib.STAT_NUM_GLOBAL], rows), min(st[_lib.STAT_NUM_ZERO], rows)
         a.max_degree = st[_lib.STAT_MAX_DEGREE]
@@ -1126,7 +1083,7 @@ class FSW_embedding(nn.Module):
         return a
 
     def embed_into(self, X, graph: CSRGraph, out, out_scale=1.0, serialize_num_slices=None, slice_range=None, x_copy=None,
-                   prepared=None, chunks=None, long_rows_only=False):
+                   prepared=None, chunks=None, long_rows_only=False, epilogue=True):
         """Writes out_scale * E(X, graph) into the left columns of `out` (row stride out.stride(0)).
 
         X [num_cols, d_in] float32 contiguous; out [num_rows, >= width] float32 with unit inner stride, where
@@ -1136,11 +1093,13 @@ class FSW_embedding(nn.Module):
         (FSW_conv's concat buffer, reference fsw_conv.py:357-358).
         prepared: the result of prepare() (its slice_range is used); chunks: row chunks to process (default all).
         long_rows_only: write only the rows of more than REG_MAX_DEG neighbours (the other rows of `out` are not touched).
+        epilogue = False: stop at what the kernels write for the 'homog' / 'homog_alt' methods, the 'plain' embedding without bias
+        (embed_autograd applies the epilogue out of place); no difference for the 'plain' method.
         This is the hot path: projection (MFMA) -> coefficient table -> fused neighbourhood kernels.
         """
         L = _lib.lib()
         dev = X.device
-        has_mass = 1 if self.encode_total_mass else 0
+        has_mass = self.total_mass_encoding_dim
         if x_copy is not None:
             assert x_copy.shape == X.shape and x_copy.stride(1) == 1 and x_copy.dtype == X.dtype
         if prepared is not None:
@@ -1156,28 +1115,21 @@ class FSW_embedding(nn.Module):
             return out
         if self.nSlices == 0:
             raise NotImplementedError("fsw_gnn_amd: nSlices == 0 with encode_total_mass is not supported")
-        method = self.total_mass_encoding_method
-        plain = (not self.encode_total_mass) or method == 'plain' or self._force_plain
-        if partial and not plain:
+        homog = epilogue and not self.plain_mass      # the 'homog' / 'homog_alt' epilogue follows the kernels and adds the bias
+        if partial and homog:
             raise NotImplementedError("slice sharding supports total_mass_encoding_method='plain' only")
-        bias = self.bias.detach() if (self.enable_bias and plain and not self._force_plain) else None
+        bias = self.bias.detach() if (self.enable_bias and epilogue and not homog) else None
         if bias is not None and partial:
             bias = torch.cat([bias[:has_mass], bias[has_mass + ka:has_mass + kb]])
-        unit_fast = graph.w is None and self.total_mass_pad_thresh <= 1.0
 
         step = S if (serialize_num_slices is None or serialize_num_slices >= S) else int(serialize_num_slices)
         assert step >= 1, 'serialize_num_slices must be None or a positive integer'
         if prepared is not None:
             assert step == S, 'a prepared projection covers its slices in one chunk'
             ldp, Xp, table, st = prepared["ldp"], prepared["Xp"], prepared["table"], prepared["stats"]
-        else:
-            ldp = _round_up(step, 64)
-            Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=dev)
-            table = None
-            if unit_fast:
-                table = torch.empty((int(L.fsw_unit_table_rows(_lib.REG_MAX_DEG)), ldp), dtype=torch.float32, device=dev)
+        else:       # Xp and the table once per forward, refilled by every chunk of slices
+            ldp, Xp, table = self._projection_buffers(X, step, self._unit_fast(graph))
             st = None
-        V = self.projVecs.detach()[ka:kb]
         freqs = self.freqs.detach()[ka:kb]
         scratch = None
         assert (graph.ef is None) == (self.d_edge == 0), 'edge features must be given exactly when d_edge > 0'
@@ -1188,15 +1140,7 @@ class FSW_embedding(nn.Module):
             Sc = k1 - k0
             fc = freqs[k0:k1]
             if prepared is None:
-                Vc = V[k0:k1]
-                rc = L.fsw_project_f32(_lib.ptr(X), X.shape[0], self.d_in, X.stride(0), _lib.ptr(Vc), Sc, Vc.stride(0),
-                                       _lib.ptr(Xp), ldp, _lib.ptr(x_copy) if k0 == 0 else None,
-                                       x_copy.stride(0) if x_copy is not None else 0,
-                                       _lib.ptr(graph.stats_dev) if k0 == 0 else None, stream)
-                _lib.check(rc, "fsw_project_f32")
-                if unit_fast:
-                    rc = L.fsw_unit_coeff_table(_lib.ptr(fc), Sc, _lib.REG_MAX_DEG, _lib.ptr(table), ldp, stream)
-                    _lib.check(rc, "fsw_unit_coeff_table")
+                self._project_slices(X, graph, ka + k0, ka + k1, Xp, ldp, table, x_copy, first=(k0 == 0))
             if st is None:
                 st = self._checked_stats(graph)   # one device->host read per forward (flags + degree classes)
             if scratch is None and st[_lib.STAT_NUM_GLOBAL] > 0:
@@ -1213,19 +1157,8 @@ class FSW_embedding(nn.Module):
                 rc = L.fsw_embed_f32(ctypes.byref(a), stream)
                 _lib.check(rc, "fsw_embed_f32")
 
-        if not plain:
-            # 'homog' / 'homog_alt' (reference fsw_embedding.py:874-882, 1136-1144): rarely used epilogues, done with
-            # three elementwise torch ops on the kernel's 'plain' output (the kernel wrote f(m)*scale in column 0)
-            emb = out[:, 1:self.d_out]
-            tm = out[:, 0:1] / out_scale
-            norm = emb.abs().mean(dim=-1, keepdim=True) / out_scale
-            if method == 'homog':
-                out[:, 0:1] = out_scale * tm * norm
-            else:
-                out[:, 0:1] = out_scale * torch.where(tm <= 1, tm * (2 - tm), torch.ones_like(tm)) * norm
-                emb.mul_(torch.where(tm <= 1, tm.square(), 2 * tm - 1))
-            if self.enable_bias:
-                out[:, :self.d_out] += out_scale * self.bias.detach()
+        if homog:      # the kernels wrote f(m) * scale into column 0
+            self._homog_epilogue(out, out_scale, self.bias.detach() if self.enable_bias else None, in_place=True)
         return out
 
 
