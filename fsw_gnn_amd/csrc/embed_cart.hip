@@ -25,6 +25,7 @@
 // with the per-frequency terms of embed_generic.hip:17-20 summed over f (the weight gradient is linear in H_t, so H is summed
 // over the frequencies first and the reverse cumulative sum runs once per slice).
 #include <algorithm>
+#include "embed_cart.h"
 #include "embed_launch.h"
 #include "sortnet.h"
 #include "wave_sort.h"
@@ -36,8 +37,6 @@ namespace {
 constexpr int kCgThreads = 256;
 constexpr int kCgLdsElems = 2048;
 constexpr int kCartScratchBytesPerElem = 8 + 4 + 8 + 8 + 8;   // key, index, cumulative weight, H / reverse sum, key gradient
-constexpr int kCartRows = 64;                                 // rows per workgroup tile of the register path
-constexpr int kCartMaxLine = 2048;                            // longest line of the wavefront path
 
 template <class T>
 struct CartGen {
@@ -295,19 +294,6 @@ struct CartTuned {
   float mass_scale;
 };
 
-// Read-only inputs at wave-uniform addresses (coefficient table, frequencies) are read through the constant address space: the
-// compiler then issues scalar loads (s_load_dwordx4).  Through a generic pointer it must assume that the output stores may alias
-// them, and every coefficient becomes a vector-memory load next to the gathers.
-#if defined(__HIP_DEVICE_COMPILE__)
-template <class T>
-using ConstAS = const __attribute__((address_space(4))) T;
-#else
-template <class T>
-using ConstAS = const T;   // host pass of the same source: no address spaces
-#endif
-template <class T>
-__device__ __forceinline__ ConstAS<T>* as_const(const T* p) { return (ConstAS<T>*)p; }
-
 // VEC: four frequencies per step -- 16-byte coefficient loads (wave-uniform) and 16-byte output stores (F % 4 == 0, no mass column
 // in front of the run, 16-byte aligned rows: launch condition on the host)
 template <int D, bool VEC>
@@ -403,10 +389,6 @@ __device__ __forceinline__ void cart_reg_weighted(const CartTuned& a, int p, int
       orow[0] = mass_column((float)m, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
   }
 }
-
-#define FSW_CART_CASES_1_32(X)                                                                                         \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) \
-  X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
 
 template <bool UNIT, bool VEC>
 __global__ void __launch_bounds__(256) k_cart_reg(const CartTuned a) {
@@ -530,6 +512,8 @@ int launch_cart_wave(const CartTuned& t, bool weighted, int p0, int rows, int S,
   return 0;
 }
 
+}  // namespace
+
 int bin_upper_degree(int b) {
   constexpr int sizes[FSW_NUM_MID_BINS] = FSW_MID_SIZES;
   if (b <= FSW_REG_MAX_DEG) return b;
@@ -538,7 +522,21 @@ int bin_upper_degree(int b) {
   return 1 << 30;
 }
 
-}  // namespace
+int launch_cart_generic_f32(const fsw_cart_args* c, const int32_t* rows, int64_t num_rows, int min_deg, hipStream_t stream) {
+  return run_cart_generic<float>(c, rows, num_rows, min_deg, stream);
+}
+
+int cart_check_common(const fsw_cart_args* c) {
+  FSW_REQUIRE(c, "fsw_embed_cart: null args");
+  FSW_REQUIRE(c->rowptr && c->Xp && c->freqs && (c->num_rows == 0 || c->col || c->max_degree == 0), "fsw_embed_cart: null pointer");
+  FSW_REQUIRE(c->num_rows >= 0 && c->S >= 1 && c->F >= 1 && c->ldp >= c->S && c->max_degree >= 0 && c->tau > 0.0,
+              "fsw_embed_cart: bad sizes");
+  FSW_REQUIRE(c->S <= 65535 && (int64_t)c->S * c->F < (1ll << 31), "fsw_embed_cart: S <= 65535 and S * F < 2^31 required");
+  FSW_REQUIRE(c->has_mass == 0 || c->has_mass == 1, "fsw_embed_cart: has_mass must be 0 or 1");
+  FSW_REQUIRE(c->mass_fn >= 0 && c->mass_fn <= 2, "fsw_embed_cart: mass_fn must be 0, 1 or 2");
+  return 0;
+}
+
 }  // namespace fsw
 
 using namespace fsw;
@@ -549,17 +547,6 @@ extern "C" size_t fsw_embed_cart_generic_scratch_bytes(int64_t max_degree, int64
   size_t nwg = (size_t)std::max<int64_t>(1, std::min<int64_t>(num_rows, 2048));
   nwg = std::max<size_t>(1, std::min<size_t>(nwg, cap / per_wg));
   return nwg * per_wg;
-}
-
-static int cart_check_common(const fsw_cart_args* c) {
-  FSW_REQUIRE(c, "fsw_embed_cart: null args");
-  FSW_REQUIRE(c->rowptr && c->Xp && c->freqs && (c->num_rows == 0 || c->col || c->max_degree == 0), "fsw_embed_cart: null pointer");
-  FSW_REQUIRE(c->num_rows >= 0 && c->S >= 1 && c->F >= 1 && c->ldp >= c->S && c->max_degree >= 0 && c->tau > 0.0,
-              "fsw_embed_cart: bad sizes");
-  FSW_REQUIRE(c->S <= 65535 && (int64_t)c->S * c->F < (1ll << 31), "fsw_embed_cart: S <= 65535 and S * F < 2^31 required");
-  FSW_REQUIRE(c->has_mass == 0 || c->has_mass == 1, "fsw_embed_cart: has_mass must be 0 or 1");
-  FSW_REQUIRE(c->mass_fn >= 0 && c->mass_fn <= 2, "fsw_embed_cart: mass_fn must be 0, 1 or 2");
-  return 0;
 }
 
 extern "C" int fsw_embed_cart_generic(const fsw_cart_args* c, fsw_stream_t stream_) {

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <stdlib.h>
 #include "embed_launch.h"
+#include "fourier_coef.h"
 #include "sortnet.h"
 #include "wave_sort.h"
 
@@ -30,35 +31,6 @@ constexpr int kWbSplitY = 4;
 #ifndef FSW_WSB_ABL
 #define FSW_WSB_ABL 0   // timing experiments on k_embed_wsort_bwd: 1 no atomics, 2 no sort, 4 no coefficient walk
 #endif
-
-// F and dF/dxi at normalised cumulative weight c, given sin and cos of 2 pi xi c; series for tiny phases (the two terms
-// of dF cancel there); xi == 0: F = 2 c, dF = 2 c.  FCoef holds the per-slice factors so that no division is left per element.
-struct FCoef {
-  double xi, a1, a2, a3;   // a1 = (1 + xi)/(pi xi), a2 = 1/(pi xi^2), a3 = 2 (1 + xi)/xi
-  __device__ __forceinline__ explicit FCoef(double x) : xi(x) {
-    const double r = x > 0.0 ? 1.0 / x : 0.0;
-    a1 = (1.0 + x) * r * (1.0 / kPi);
-    a2 = r * r * (1.0 / kPi);
-    a3 = 2.0 * (1.0 + x) * r;
-  }
-};
-__device__ __forceinline__ void F_dF_sc(const FCoef& f, double c, double s, double co, double& F, double& dF) {
-  const double x = 2.0 * kPi * f.xi * c;
-  if (x < 1e-4) {
-    const double q = 1.0 - x * x * (1.0 / 6.0);
-    F = (1.0 + f.xi) * 2.0 * c * q;
-    dF = 2.0 * c * q - (1.0 + f.xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * f.xi * (1.0 / 3.0);
-  } else {
-    F = f.a1 * s;
-    dF = fma(f.a3 * c, co, -(f.a2 * s));
-  }
-}
-__device__ __forceinline__ void F_dF(const FCoef& f, double c, double& F, double& dF) {
-  const double ph = f.xi * c;
-  double s, co;
-  sincospi(2.0 * (ph - rint(ph)), &s, &co);
-  F_dF_sc(f, c, s, co, F, dF);
-}
 
 // Walks the sorted line held by `ln` (ranks r0 + j, j < M, of a line of Dtot elements of which the first D are
 // neighbours): calls emit(element index, g * C) for every neighbour and returns this lane's share of the slice's gfreq.

@@ -19,8 +19,10 @@ for inference, out of place under autograd.  Nothing per call is kept on the mod
 
 Cartesian mode, FSW_embedding(d_in, nSlices=S, nFreqs=F, collapse_freqs=...) (reference fsw_embedding.py:153-160, 241-259):
 every slice is sorted once and read out at all F frequencies (csrc/embed_cart.hip); output (<batch>, [nR,] S, F), or
-(<batch>, [nR,] S*F + mass_dim) collapsed, column s*F + f (after the mass column).  no_grad float32 calls run on the tuned
-kernels, autograd calls and float64 modules on the generic Cartesian kernel.  It needs a HIP device at construction (this
+(<batch>, [nR,] S*F + mass_dim) collapsed, column s*F + f (after the mass column).  float32 calls run on the tuned kernels, under
+autograd through _CartEmbedFn (backward kernels of csrc/embed_cart_bwd.hip, the key gradients summed sender by sender without
+float atomics; gradients for X, projVecs, freqs, bias and the total-mass scale); float64 modules and calls whose W requires grad
+run on the generic Cartesian kernel (_GenericEmbedFn), as do the rows of more than 2048 neighbours.  It needs a HIP device at construction (this
 package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
 differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
 bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
@@ -480,6 +482,85 @@ class _GenericEmbedFn(torch.autograd.Function):
         return gX, gV, gfreqs, gbias, gscale, gW, gEf, None, None, None
 
 
+class _CartEmbedFn(torch.autograd.Function):
+    """Cartesian mode, float32: out = out_scale * E(X, graph) [num_rows, has_mass + S F] on the tuned kernels, with gradients for X,
+    projVecs, freqs, bias and the total-mass scale (the weights are constants: a W that requires grad takes _GenericEmbedFn).
+
+    Forward: one projection of all S slices (prepare_cartesian) + fsw_embed_cart_f32; the projection, the stats and the unit table
+    stay on ctx.  Backward: fsw_embed_cart_backward_keys_f32 (csrc/embed_cart_bwd.hip) stores the key gradient of every entry,
+    [nnz, S], and accumulates the frequency gradients; the store-and-sum pair (graph.sender_major + fsw_segment_sum_rows_f32) sums
+    the entries sender by sender without float atomics, then the two GEMMs of _EmbedGraphFn.  bias: None for 'homog' /
+    'homog_alt' (the caller applies _homog_epilogue on the 'plain' output)."""
+
+    @staticmethod
+    def forward(ctx, X, projVecs, freqs, bias, mass_scale, module, graph, out_scale):
+        with torch.no_grad():
+            prepared = module.prepare_cartesian(X, graph)
+            out = torch.empty((graph.num_rows, module.d_out), dtype=X.dtype, device=X.device)
+            module.embed_cartesian_into(X, graph, out, bias.detach().reshape(-1) if bias is not None else None, out_scale=out_scale,
+                                        prepared=prepared)
+        ctx.module, ctx.graph, ctx.prepared, ctx.out_scale = module, graph, prepared, float(out_scale)
+        ctx.bias_shape = bias.shape if bias is not None else None
+        ctx.save_for_backward(X, projVecs, freqs)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        module, graph, prepared, out_scale = ctx.module, ctx.graph, ctx.prepared, ctx.out_scale
+        X, V, freqs = ctx.saved_tensors
+        L = _lib.lib()
+        S, F, has_mass = module.nSlices, module.nFreqs, module.total_mass_encoding_dim
+        g = g.contiguous()
+        dev = X.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        st, ldp = prepared["stats"], prepared["ldp"]
+        nnz = st[_lib.STAT_NNZ]
+        need = ctx.needs_input_grad
+        gX = gV = gfreqs = gbias = gscale = None
+        if nnz > 0 and (need[0] or need[1] or need[2]):
+            fr = freqs.detach().contiguous()
+            table = prepared["table"]
+            dtable = None
+            if table is not None:
+                dtable = torch.empty_like(table)
+                _lib.check(L.fsw_unit_dcoeff_table(_lib.ptr(fr), F, _lib.REG_MAX_DEG, _lib.ptr(dtable), F, stream), "fsw_unit_dcoeff_table")
+            gf = torch.zeros(F, dtype=torch.float32, device=dev)
+            gkey = torch.empty((nnz, S), dtype=torch.float32, device=dev)      # every entry is stored
+            a = module._cart_tuned_args(graph, st, prepared["Xp"], ldp, fr, S, table, prepared["scratch"], out_scale, has_mass)
+            a.g, a.ldg, a.gkey, a.ldk, a.gfreq = g.data_ptr(), g.stride(0), gkey.data_ptr(), S, gf.data_ptr()
+            _lib.check(L.fsw_embed_cart_backward_keys_f32(ctypes.byref(a), _lib.ptr(dtable), F, stream), "fsw_embed_cart_backward_keys_f32")
+            if need[0] or need[1]:
+                gXp = torch.zeros((X.shape[0], ldp), dtype=torch.float32, device=dev)
+                cptr, order = graph.sender_major()
+                _lib.check(L.fsw_segment_sum_rows_f32(_lib.ptr(gkey), S, _lib.ptr(cptr), _lib.ptr(order), graph.num_cols, nnz, S,
+                                                      _lib.ptr(gXp), ldp, stream), "fsw_segment_sum_rows_f32")
+                del gkey
+                if need[0]:
+                    gX = _grad_x(L, gXp, S, ldp, V.detach(), stream)
+                if need[1]:
+                    gV = gemm_tn(gXp[:, :S], X.detach())
+            if need[2]:
+                gfreqs = gf
+        if need[0] and gX is None:
+            gX = torch.zeros_like(X)
+        if need[1] and gV is None:
+            gV = torch.zeros_like(V)
+        if need[2] and gfreqs is None:
+            gfreqs = torch.zeros_like(freqs)
+        if need[3]:
+            gbias = (out_scale * g.sum(dim=0)).reshape(ctx.bias_shape)
+        if need[4]:
+            deg = (graph.rowptr[1:] - graph.rowptr[:-1]).long()
+            if graph.w is None:
+                m = deg.to(torch.float32)                                  # unit weights: total mass = in-degree
+            else:
+                rows = torch.repeat_interleave(torch.arange(graph.num_rows, device=dev), deg)
+                m = torch.zeros(graph.num_rows, dtype=torch.float32, device=dev).index_add_(0, rows, graph.w[:rows.numel()])
+            gscale = (out_scale * (g[:, 0] * _mass_f(module.total_mass_encoding_function, m)).sum()).reshape(())
+        return gX, gV, gfreqs, gbias, gscale, None, None, None
+
+
 class FSW_embedding(nn.Module):
     def __init__(self,
                  d_in, d_out=None, nSlices=None, nFreqs=None, collapse_freqs=False,
@@ -786,8 +867,10 @@ class FSW_embedding(nn.Module):
             num_rows, out_shape = B * nR, batch_dims + (nR,)
 
         if self.cartesian_mode:
-            generic = self.get_dtype() == torch.float64 or needs_grad or (torch.is_grad_enabled() and torch.is_tensor(W) and W.requires_grad)
-            out = self._forward_cartesian(Xf, rec, snd, wvals, num_rows, generic, serialize_num_slices)
+            # float32 calls run on the tuned kernels, under autograd with their own backward; the generic kernel keeps float64
+            # modules and gradients of the weights (a W that requires grad selects it, whatever else does)
+            generic = self.get_dtype() == torch.float64 or (torch.is_grad_enabled() and torch.is_tensor(W) and W.requires_grad)
+            out = self._forward_cartesian(Xf, rec, snd, wvals, num_rows, generic, needs_grad, serialize_num_slices)
             return out.reshape(out_shape + ((self.d_out,) if self.collapse_freqs else (self.nSlices, self.nFreqs)))
         if generic and num_rows > 0 and Xf.shape[0] > 0:
             if self.d_out == 0:
@@ -814,7 +897,7 @@ class FSW_embedding(nn.Module):
         return out.reshape(out_shape + (self.d_out,))
 
     def _forward_generic(self, Xf, rec, snd, wvals, efvals, num_rows, bias):
-        """The generic-kernel path (float64 modules; float32 with gradients of W / X_edge; Cartesian mode under autograd):
+        """The generic-kernel path (float64 modules; float32 with gradients of W / X_edge, in Cartesian mode too):
         differentiable in everything.  bias (flattened): in the kernel for the 'plain' method, in the torch epilogue otherwise."""
         _check_finite_nonnegative(Xf, wvals)
         csr = SimpleCSR(rec, snd, num_rows, Xf.shape[0])
@@ -823,9 +906,10 @@ class FSW_embedding(nn.Module):
         P = _GenericEmbedFn.apply(Xf, self.projVecs, self.freqs, bias if plain else None, scale, wvals, efvals, self, csr, 1.0)
         return P if plain else self._homog_epilogue(P, 1.0, bias)
 
-    def _forward_cartesian(self, Xf, rec, snd, wvals, num_rows, generic, serialize_num_slices):
+    def _forward_cartesian(self, Xf, rec, snd, wvals, num_rows, generic, train, serialize_num_slices):
         """Cartesian mode: [num_rows, has_mass + S F], column has_mass + s F + f = (slice s, frequency f).  generic: the generic
-        kernel (float64 modules, autograd); otherwise the tuned float32 forward (csrc/embed_cart.hip)."""
+        kernel (float64 modules, gradients of W); otherwise the tuned float32 kernels (csrc/embed_cart.hip), under autograd
+        (train) with their backward (_CartEmbedFn, csrc/embed_cart_bwd.hip)."""
         dev, dt = Xf.device, Xf.dtype
         S, F = self.nSlices, self.nFreqs
         if num_rows == 0 or self.d_out == 0:
@@ -841,60 +925,110 @@ class FSW_embedding(nn.Module):
             return Z + bias if bias is not None else Z
         if generic:
             return self._forward_generic(Xf.contiguous(), rec, snd, wvals, None, num_rows, bias)
-        graph = build_csr(rec, snd, wvals.contiguous() if wvals is not None else None, num_rows, Xf.shape[0])
+        graph = build_csr(rec, snd, wvals.detach().contiguous() if wvals is not None else None, num_rows, Xf.shape[0])
+        if train:
+            # 'homog' / 'homog_alt': the 'plain' embedding without bias from the kernels, then the epilogue out of place so that
+            # autograd differentiates it (as embed_autograd does)
+            scale = self.total_mass_encoding_scale if self.encode_total_mass else None
+            P = _CartEmbedFn.apply(Xf.contiguous(), self.projVecs, self.freqs, self.bias if (plain and self.enable_bias) else None,
+                                   scale, self, graph, 1.0)
+            return P if plain else self._homog_epilogue(P, 1.0, bias)
         with torch.no_grad():
             out = torch.empty((num_rows, self.d_out), dtype=dt, device=dev)
             self.embed_cartesian_into(Xf.contiguous(), graph, out, bias.detach() if (bias is not None and plain) else None,
                                       serialize_num_slices)
             return out if plain else self._homog_epilogue(out, 1.0, bias.detach() if bias is not None else None)
 
-    def embed_cartesian_into(self, X, graph: CSRGraph, out, bias=None, serialize_num_slices=None, out_scale=1.0):
+    def _cart_unit_table(self, graph, fr):
+        """Unit coefficient table [rows, F] of the F frequencies (unit weights with tau <= 1), else None."""
+        if not self._unit_fast(graph):
+            return None
+        L = _lib.lib()
+        table = torch.empty((int(L.fsw_unit_table_rows(_lib.REG_MAX_DEG)), self.nFreqs), dtype=torch.float32, device=fr.device)
+        _lib.check(L.fsw_unit_coeff_table(_lib.ptr(fr), self.nFreqs, _lib.REG_MAX_DEG, _lib.ptr(table), self.nFreqs,
+                                          torch.cuda.current_stream(fr.device).cuda_stream), "fsw_unit_coeff_table")
+        return table
+
+    def _cart_scratch(self, graph, st):
+        """Scratch of the generic kernel for the rows above the wavefront class (None without such rows)."""
+        if st[_lib.STAT_MAX_DEGREE] < _lib.LDS_MAX_DEG:
+            return None
+        bsh = graph.bin_start_host[0]
+        long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[_lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS - 1])
+        return torch.empty(int(_lib.lib().fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
+                           dtype=torch.uint8, device=graph.rowptr.device)
+
+    def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass):
+        """struct fsw_cart_args of the tuned entry points (fsw_embed_cart_f32, fsw_embed_cart_backward_keys_f32) without the
+        output / gradient fields."""
+        a = _cart_args(self, Xp, ldp, fr, S, out_scale, has_mass, self._mass_scale_read(st))
+        a.rowptr, a.col = graph.rowptr.data_ptr(), graph.col.data_ptr()
+        a.w = graph.w.data_ptr() if graph.w is not None else None
+        a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), graph.bin_start_host[0].ctypes.data
+        a.num_rows, a.max_degree = graph.num_rows, st[_lib.STAT_MAX_DEGREE]
+        a.unit_table, a.ldt = (table.data_ptr(), self.nFreqs) if table is not None else (None, 0)
+        if scratch is not None:
+            a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        return a
+
+    def prepare_cartesian(self, X, graph: CSRGraph):
+        """What the tuned Cartesian forward needs and its backward needs again: ONE projection of all S slices at
+        ldp = round_up(S, 32) -- the call the generic path makes (_project), so both sort bit-identical keys --, the one
+        device->host stats read of the forward (input validation as in prepare()), the unit coefficient table and the scratch of
+        the longest rows."""
+        L = _lib.lib()
+        S = self.nSlices
+        assert X.is_contiguous() and X.dtype == torch.float32 and graph.num_chunks == 1
+        ldp = _round_up(S, 32)      # fsw_project_f32 takes its wavefront-per-tile kernel for <= 64 columns at this stride
+        Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=X.device)
+        V = self.projVecs.detach()
+        _lib.check(L.fsw_project_f32(_lib.ptr(X), X.shape[0], self.d_in, X.stride(0), _lib.ptr(V), S, V.stride(0), _lib.ptr(Xp), ldp,
+                                     None, 0, _lib.ptr(graph.stats_dev), torch.cuda.current_stream(X.device).cuda_stream),
+                   "fsw_project_f32")
+        st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
+        return {"Xp": Xp, "ldp": ldp, "stats": st, "table": self._cart_unit_table(graph, self.freqs.detach().contiguous()),
+                "scratch": self._cart_scratch(graph, st)}
+
+    def embed_cartesian_into(self, X, graph: CSRGraph, out, bias=None, serialize_num_slices=None, out_scale=1.0, prepared=None):
         """Tuned float32 Cartesian forward (fsw_embed_cart_f32) of a CSR graph into out [num_rows, d_out] (unit inner stride): the
         'plain' embedding, plus bias [has_mass + S F] when given.  serialize_num_slices chunks the slices; every chunk covers all
-        frequencies (reference fsw_embedding.py:848)."""
+        frequencies (reference fsw_embedding.py:848).  prepared: the result of prepare_cartesian() (all slices in one chunk), which
+        the caller keeps for the backward."""
         L = _lib.lib()
         dev = X.device
         S, F = self.nSlices, self.nFreqs
         has_mass = self.total_mass_encoding_dim
         assert X.is_contiguous() and X.dtype == torch.float32 and out.stride(1) == 1 and out.shape[0] == graph.num_rows
         assert out.shape[1] >= has_mass + S * F and graph.num_chunks == 1
-        step = S if (serialize_num_slices is None or serialize_num_slices >= S) else int(serialize_num_slices)
+        step = S if (prepared is not None or serialize_num_slices is None or serialize_num_slices >= S) else int(serialize_num_slices)
         assert step >= 1, 'serialize_num_slices must be None or a positive integer'
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ldp = _round_up(step, 32)      # fsw_project_f32 takes its wavefront-per-tile kernel for <= 64 columns at this stride
-        Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=dev)
         fr = self.freqs.detach().contiguous()
-        V = self.projVecs.detach()
-        table = None
-        if self._unit_fast(graph):
-            table = torch.empty((int(L.fsw_unit_table_rows(_lib.REG_MAX_DEG)), F), dtype=torch.float32, device=dev)
-            _lib.check(L.fsw_unit_coeff_table(_lib.ptr(fr), F, _lib.REG_MAX_DEG, _lib.ptr(table), F, stream), "fsw_unit_coeff_table")
-        st = None
-        scratch = None
+        if prepared is None and step == S:
+            prepared = self.prepare_cartesian(X, graph)
+        if prepared is not None:
+            Xp, ldp, st, table, scratch = (prepared[k] for k in ("Xp", "ldp", "stats", "table", "scratch"))
+        else:       # chunks of slices: Xp once per forward, refilled by every chunk
+            ldp = _round_up(step, 32)
+            Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=dev)
+            V = self.projVecs.detach()
+            table = self._cart_unit_table(graph, fr)
+            st = scratch = None
         for k0 in range(0, S, step):
             k1 = min(S, k0 + step)
-            Vc = V[k0:k1]
-            _lib.check(L.fsw_project_f32(_lib.ptr(X), X.shape[0], self.d_in, X.stride(0), _lib.ptr(Vc), k1 - k0, Vc.stride(0), _lib.ptr(Xp),
-                                         ldp, None, 0, _lib.ptr(graph.stats_dev) if k0 == 0 else None, stream), "fsw_project_f32")
-            if st is None:
-                st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
-                bsh = graph.bin_start_host[0]
-                if st[_lib.STAT_MAX_DEGREE] >= _lib.LDS_MAX_DEG:
-                    long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[_lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS - 1])
-                    scratch = torch.empty(int(L.fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
-                                          dtype=torch.uint8, device=dev)
+            if prepared is None:
+                Vc = V[k0:k1]
+                _lib.check(L.fsw_project_f32(_lib.ptr(X), X.shape[0], self.d_in, X.stride(0), _lib.ptr(Vc), k1 - k0, Vc.stride(0),
+                                             _lib.ptr(Xp), ldp, None, 0, _lib.ptr(graph.stats_dev) if k0 == 0 else None, stream),
+                           "fsw_project_f32")
+                if st is None:
+                    st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
+                    scratch = self._cart_scratch(graph, st)
             first = k0 == 0
             col0 = 0 if first else has_mass + k0 * F
-            a = _cart_args(self, Xp, ldp, fr, k1 - k0, out_scale, has_mass if first else 0, self._mass_scale_read(st))
-            a.rowptr, a.col = graph.rowptr.data_ptr(), graph.col.data_ptr()
-            a.w = graph.w.data_ptr() if graph.w is not None else None
-            a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), bsh.ctypes.data
-            a.num_rows, a.max_degree = graph.num_rows, st[_lib.STAT_MAX_DEGREE]
-            a.unit_table, a.ldt = (table.data_ptr(), F) if table is not None else (None, 0)
+            a = self._cart_tuned_args(graph, st, Xp, ldp, fr, k1 - k0, table, scratch, out_scale, has_mass if first else 0)
             a.out, a.ldo = out.data_ptr() + 4 * col0, out.stride(0)
             a.bias = (bias.data_ptr() + 4 * col0) if bias is not None else None
-            if scratch is not None:
-                a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
             _lib.check(L.fsw_embed_cart_f32(ctypes.byref(a), stream), "fsw_embed_cart_f32")
         return out
 

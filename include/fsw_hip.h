@@ -353,6 +353,7 @@ int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double
  *   out[r * ldo + has_mass + s F + f] = out_scale * ((1 + xi_f) sum_t Delta_t(xi_f) p_(t) + bias[has_mass + s F + f])
  *   out[r * ldo]                      = out_scale * (f(m_r) * mass_scale + bias[0])                     if has_mass
  * where p_(t) sorts Xp[col[e], s] over the row's entries (+ the pad element) and Delta_t is the readout of fsw_embed_generic.
+ * fsw_embed_cart_backward_keys_f32 (below) is the tuned float32 backward of fsw_embed_cart_f32 for keys and frequencies.
  * fsw_embed_cart_f32      tuned float32 forward on a graph of fsw_graph_build: needs perm, bin_start and bin_start_host,
  *                         unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1, and scratch of
  *                         fsw_embed_cart_generic_scratch_bytes(max_degree, rows above FSW_LDS_MAX_DEG) bytes when
@@ -403,6 +404,14 @@ typedef struct {
 size_t fsw_embed_cart_generic_scratch_bytes(int64_t max_degree, int64_t num_rows);
 int fsw_embed_cart_generic(const fsw_cart_args* args, fsw_stream_t stream);
 int fsw_embed_cart_f32(const fsw_cart_args* args, fsw_stream_t stream);
+/* Backward of fsw_embed_cart_f32 on the same graph (perm, bin_start, bin_start_host), float32 (csrc/embed_cart_bwd.hip).
+ * Reads   args->g [num_rows, ldg]  (column has_mass + s F + f; column 0 of a mass module is ignored here)
+ * Stores  args->gkey[e * ldk + s] = out_scale * sum_f g[r, has_mass + s F + f] * d out[r,s,f] / d key_e   for EVERY entry e, s < S
+ * Adds    args->gfreq[f]         += out_scale * sum_{r,s} g[r, has_mass + s F + f] * d out[r,s,f] / d xi_f  (nullable; caller zeroes)
+ * args->gw must be NULL (gradients w.r.t. the weights stay on fsw_embed_cart_generic).
+ * unit_dtable: fsw_unit_dcoeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1 (with args->unit_table as in the forward).
+ * scratch: as for fsw_embed_cart_f32 (rows above the wavefront class run on the generic kernel in backward mode). */
+int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* args, const float* unit_dtable, int64_t lddt, fsw_stream_t stream);
 
 /* ---- stand-alone segmented cumulative sum --------------------------------------------------------
  * Replaces segcumsum / segcumsum_cuda (reference fsw_embedding.py:2795-3012): inclusive scan of

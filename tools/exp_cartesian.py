@@ -9,7 +9,15 @@ time, so a lower bound of the fraction.  Byte model of (a)'s kernel: gathers 4 E
 gathers 4 E 256 + output 4 n 256 (+ 4 E).  The per-kernel split and the name of the dominant kernel come from a kernel trace of one
 configuration:
     python tools/exp_cartesian.py [--reps 20] [--only a|b|c]
-    rocprofv3 --kernel-trace --stats -d DIR -o cart -- python tools/exp_cartesian.py --only a   (profiles/r04_cartesian_a_kernel_stats.csv)"""
+    rocprofv3 --kernel-trace --stats -d DIR -o cart -- python tools/exp_cartesian.py --only a   (profiles/r04_cartesian_a_kernel_stats.csv)
+
+--train: one float32 TRAINING step (forward + backward, learnable slices and frequencies) instead, HIP events after warm-up:
+  graph  the config-3 graph with unit edges, d_in 128, S = F = 16 (graph_w, not in the default: the same graph with general weights,
+         a coalesced sparse W through the public forward -- it is timed after, and together with, graph)
+  pc     a point-cloud batch of 256 clouds x 1024 points, d_in 3, S = 64, F = 16, W = 'uniform'
+A package with the tuned backward (fsw_embedding._CartEmbedFn) takes it; --generic, or a package without it, takes the generic
+Cartesian kernel for forward and backward (what every autograd call of Cartesian mode ran on before the tuned backward):
+    python tools/exp_cartesian.py --train [--workload graph,pc] [--steps 10] [--warmup 2] [--generic]"""
 import argparse
 import os
 import sys
@@ -26,8 +34,78 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--slices", type=int, default=16)
 ap.add_argument("--freqs", type=int, default=16)
 ap.add_argument("--only", default="abc", help="subset of the configurations a, b, c to time")
+ap.add_argument("--train", action="store_true", help="time one training step (forward + backward) instead of the forwards")
+ap.add_argument("--workload", default="graph,pc", help="--train: subset of graph, graph_w, pc")
+ap.add_argument("--steps", type=int, default=10)
+ap.add_argument("--warmup", type=int, default=2)
+ap.add_argument("--generic", action="store_true", help="--train: the generic Cartesian kernel for forward and backward")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
+
+
+def train_leg():
+    from fsw_gnn_amd import fsw_embedding as fe
+    tuned = hasattr(fe, "_CartEmbedFn") and not args.generic
+    path = "tuned kernels (_CartEmbedFn)" if tuned else "generic Cartesian kernel (_GenericEmbedFn)"
+
+    def step_ms(step):
+        for _ in range(args.warmup):
+            step()
+        return bench.timed_ms(step, args.steps, dev) if args.steps > 1 else bench.timed_ms(step, 1, dev)
+
+    def graph_forward(mod, xg, rec, snd, rows):
+        """Unit edges (no weight tensor), which the public forward cannot express in graph mode: the module's own Cartesian
+        forward on the edge list.  Its signature gained the `train` flag with the tuned backward."""
+        if hasattr(fe, "_CartEmbedFn"):
+            return mod._forward_cartesian(xg, rec, snd, None, rows, not tuned, tuned, None)
+        return mod._forward_cartesian(xg, rec, snd, None, rows, True, None)
+
+    torch.manual_seed(7)
+    if "graph" in args.workload:
+        n, E, d = bench.N_NODES, bench.N_EDGES, bench.D_FEAT
+        xg, ei = bench.make_inputs(n, E, dev)
+        order = torch.argsort(ei[1], stable=True)            # the generic path wants the edges sorted by recipient
+        rec, snd = ei[1][order].contiguous(), ei[0][order].contiguous()
+        mod = FSW_embedding(d_in=d, nSlices=16, nFreqs=16, collapse_freqs=True, enable_bias=False, learnable_slices=True,
+                            learnable_freqs=True, freqs_init='spread', device=dev)
+        G = torch.randn((n, 256), device=dev)
+
+        def step():
+            mod.zero_grad(set_to_none=True)
+            graph_forward(mod, xg, rec, snd, n).backward(G)
+
+        print("train graph: n=%d E=%d (unit edges) d_in=%d S=16 F=16, %s: %.3f ms/step" % (n, E, d, path, step_ms(step)), flush=True)
+        if "graph_w" in args.workload:      # the same graph with general weights through the public forward (coalesced sparse W)
+            W = torch.sparse_coo_tensor(torch.stack([rec, snd]), torch.rand(E, device=dev) + 0.1, (n, n)).coalesce()
+            W.requires_grad_(args.generic and hasattr(fe, "_CartEmbedFn"))
+
+            def step_w():
+                mod.zero_grad(set_to_none=True)
+                mod(xg, W, graph_mode=True).backward(G)
+
+            print("train graph_w: the same graph, general weights, %s: %.3f ms/step" % (path, step_ms(step_w)), flush=True)
+            del W
+        del xg, ei, rec, snd, G
+    if "pc" in args.workload:
+        B, npts = 256, 1024
+        xc = torch.randn((B, npts, 3), device=dev)
+        mod = FSW_embedding(d_in=3, nSlices=64, nFreqs=16, collapse_freqs=True, enable_bias=False, learnable_slices=True,
+                            learnable_freqs=True, freqs_init='spread', device=dev)
+        G = torch.randn((B, 64 * 16), device=dev)
+        # --generic on a package with the tuned backward: only a W that requires grad selects the generic kernel (which then also
+        # computes the weight gradient, a reverse cumulative sum per slice on top of what 'uniform' costs there)
+        Wc = torch.full((B, npts), 1.0 / npts, device=dev).requires_grad_(True) if (args.generic and hasattr(fe, "_CartEmbedFn")) else 'uniform'
+
+        def step():
+            mod.zero_grad(set_to_none=True)
+            mod(xc, Wc).backward(G)
+
+        print("train pc: %d clouds x %d points d_in=3 S=64 F=16 W=uniform, %s: %.3f ms/step" % (B, npts, path, step_ms(step)), flush=True)
+
+
+if args.train:
+    train_leg()
+    sys.exit(0)
 n, E, d = bench.N_NODES, bench.N_EDGES, bench.D_FEAT
 S, F = args.slices, args.freqs
 x, ei = bench.make_inputs(n, E, dev)
