@@ -1,7 +1,8 @@
 // What the forward (embed_cart.hip) and the tuned backward (embed_cart_bwd.hip) of Cartesian mode share: the degree classes, the
 // constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
 #pragma once
-#include "fsw_common.h"
+#include <algorithm>
+#include "embed_launch.h"
 
 namespace fsw {
 
@@ -28,7 +29,32 @@ __device__ __forceinline__ ConstAS<T>* as_const(const T* p) { return (ConstAS<T>
 // embed_cart.hip
 int cart_check_common(const fsw_cart_args* c);                // the checks every Cartesian entry point starts with
 int bin_upper_degree(int b);                                  // largest in-degree of degree bin b
-// k_embed_cart_generic (float32 storage) on rows[0 .. num_rows - 1] of at least min_deg neighbours; forward or, with c->g, backward
-int launch_cart_generic_f32(const fsw_cart_args* c, const int32_t* rows, int64_t num_rows, int min_deg, hipStream_t stream);
+
+// The degree bins of 33 .. 2048 neighbours (bin_start_host bs) in groups of consecutive bins whose lines (extra = 1: + the pad
+// element of general weights) need the same number Mb of keys per lane of a wavefront: fn(Mb, p0, rows) for the rows
+// perm[p0 .. p0 + rows - 1] of every group, until one returns an error code.
+template <class Fn>
+int for_each_wave_group(const int32_t* bs, int extra, Fn fn) {
+  auto keys_per_lane = [&](int b) { return (int)std::min<uint32_t>(32, pow2ceil((uint32_t)ceil_div(bin_upper_degree(b) + extra, kWave))); };
+  for (int b = FSW_BIN_MID0; b < FSW_BIN_HUB0;) {
+    const int Mb = keys_per_lane(b);
+    int e = b + 1;                                            // one past the group's last bin
+    while (e < FSW_BIN_HUB0 && keys_per_lane(e) == Mb) ++e;
+    if (const int rc = fn(Mb, bs[b], bs[e] - bs[b])) return rc;
+    b = e;
+  }
+  return 0;
+}
+
+// Lines above kCartMaxLine elements (float32 storage): the generic kernel, forward or, with c->g, backward, on the rows of the last
+// LDS bin and above that have such a line.
+inline int launch_cart_long_rows(const fsw_cart_args* c, int extra, hipStream_t stream) {
+  const int min_long = kCartMaxLine + 1 - extra;
+  const int32_t* bs = c->bin_start_host;
+  const int p0 = bs[FSW_BIN_LDS0 + FSW_NUM_LDS_BINS - 1];
+  const int64_t rows = (int64_t)bs[FSW_NUM_BINS] - p0;
+  if (c->max_degree < min_long || rows <= 0) return 0;
+  return launch_embed_generic(generic_args(*c, true, c->F), 0, c->perm + p0, rows, min_long, stream);
+}
 
 }  // namespace fsw

@@ -13,17 +13,15 @@
 //                    the wavefront (wave_sort.h, WaveLine), the sorted keys and cumulative weights are staged in LDS, and the
 //                    readout lanes are (frequency, rank phase) pairs -- lane = f + NF q sums the ranks t = q (mod Q) for
 //                    frequency f, Q = 64 / NF -- so that F < 64 does not leave most lanes idle; LDS reads are broadcasts.
-//   longer lines     the generic kernel below (correct, not tuned: DESIGN.md).
+//   longer lines     the generic kernel in its Cartesian readout (k_embed_generic, embed_generic.hip; correct, not tuned: DESIGN.md).
 // Readout, by summation by parts of the reference's Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t)):
 //   out = (1 + xi) / (pi xi) sum_t sin(2 pi xi c_t) (p_(t) - p_(t+1)),  p_(L) = 0;   xi = 0:  out = sum_t 2 c_t (p_(t) - p_(t+1)).
 //
-// The generic kernel (fsw_embed_cart_generic) restates k_embed_generic of embed_generic.hip for the Cartesian product: any degree,
-// float32 or float64 storage, float64 arithmetic, forward and backward.  Backward, for the output gradient g:
+// fsw_embed_cart_generic (any degree, float32 or float64 storage, float64 arithmetic, forward and backward) is that same generic
+// kernel on every row; this file only checks its arguments.  Backward, for the output gradient g:
 //   gkey[e, s] = sum_f out_scale g[r, s F + f] (1 + xi_f) Delta_t(xi_f)                       (stored)
 //   gfreq[f]  += sum_{r, s} out_scale g[r, s F + f] d out[r, s F + f] / d xi_f                (accumulated)
 //   gw[e]     += sum_{s, f} out_scale g[r, s F + f] d out[r, s F + f] / d w_e                 (accumulated; mass column excluded)
-// with the per-frequency terms of embed_generic.hip:17-20 summed over f (the weight gradient is linear in H_t, so H is summed
-// over the frequencies first and the reverse cumulative sum runs once per slice).
 #include <algorithm>
 #include "embed_cart.h"
 #include "embed_launch.h"
@@ -33,244 +31,6 @@
 namespace fsw {
 
 namespace {
-
-constexpr int kCgThreads = 256;
-constexpr int kCgLdsElems = 2048;
-constexpr int kCartScratchBytesPerElem = 8 + 4 + 8 + 8 + 8;   // key, index, cumulative weight, H / reverse sum, key gradient
-
-template <class T>
-struct CartGen {
-  const int32_t* rowptr;
-  const int32_t* col;
-  const T* w;
-  const int32_t* rows;   // null: rows 0 .. num_rows - 1; else rows[0 .. num_rows - 1] (the tuned entry's long rows)
-  int64_t num_rows;
-  int min_deg;           // rows of fewer neighbours are skipped (belong to another kernel)
-  const T* Xp;
-  int64_t ldp;
-  const T* freqs;
-  int S, F;
-  double tau;
-  T* out;
-  int64_t ldo;
-  const T* bias;
-  double out_scale;
-  int has_mass, mass_fn;
-  double mass_scale;
-  const T* g;
-  int64_t ldg;
-  T* gkey;
-  int64_t ldk;
-  T* gfreq;
-  T* gw;
-  char* scratch;
-  int64_t line_elems;
-};
-
-__device__ __forceinline__ double sinc_c(double z) { return z == 0.0 ? 1.0 : sinpi(z) / (kPi * z); }
-__device__ __forceinline__ double dsinc_c(double z) { return z == 0.0 ? 0.0 : (cospi(z) - sinc_c(z)) / z; }
-
-__device__ __forceinline__ double cg_block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();
-  if (lane_id() == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ double cg_block_scan(double v, double* red, double* total) {
-  double inc = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const double t = __shfl_up(inc, off);
-    if (lane_id() >= off) inc += t;
-  }
-  __syncthreads();
-  if (lane_id() == kWave - 1) red[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  double base = 0.0, tot = 0.0;
-#pragma unroll
-  for (int i = 0; i < kCgThreads / kWave; ++i) {
-    if (i < (int)(threadIdx.x >> 6)) base += red[i];
-    tot += red[i];
-  }
-  *total = tot;
-  return base + inc;
-}
-
-// ---- generic kernel: one workgroup per row, slices in turn, frequencies per sorted slice -------------------------------------
-template <class T>
-__global__ void __launch_bounds__(kCgThreads) k_embed_cart_generic(const CartGen<T> a) {
-  __shared__ double lkey[kCgLdsElems];
-  __shared__ int lidx[kCgLdsElems];
-  __shared__ double red[4];
-  char* myscr = a.scratch + (int64_t)blockIdx.x * a.line_elems * kCartScratchBytesPerElem;
-  double* gkeyb = reinterpret_cast<double*>(myscr);
-  double* cw = gkeyb + a.line_elems;
-  double* hr = cw + a.line_elems;
-  double* gks = hr + a.line_elems;
-  int* gidx = reinterpret_cast<int*>(gks + a.line_elems);
-  const bool backward = a.g != nullptr;
-  const int tid = threadIdx.x;
-  for (int64_t i = blockIdx.x; i < a.num_rows; i += gridDim.x) {
-    const int64_t row = a.rows ? (int64_t)a.rows[i] : i;
-    const int start = a.rowptr[row];
-    const int D = a.rowptr[row + 1] - start;
-    if (D < a.min_deg) continue;                                           // workgroup-uniform
-    const int Dtot = D + 1;
-    int Dp = 1;
-    while (Dp < Dtot) Dp <<= 1;
-    const bool in_lds = Dp <= kCgLdsElems;
-    double* keys = in_lds ? lkey : gkeyb;
-    int* idx = in_lds ? lidx : gidx;
-    double part = 0.0;
-    for (int t = tid; t < D; t += kCgThreads) part += a.w ? (double)a.w[start + t] : 1.0;
-    const double m = cg_block_sum(part, red);
-    const double M = fmax(m, a.tau);
-    const double padw = fmax(a.tau - m, 0.0);
-    const double invM = 1.0 / M;
-    auto raw_weight = [&](int e) -> double { return e < D ? (a.w ? (double)a.w[start + e] : 1.0) : (e == D ? padw : 0.0); };
-    if (!backward && a.has_mass && tid == 0)
-      a.out[row * a.ldo] = (T)mass_column(m, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
-    for (int s = 0; s < a.S; ++s) {
-      for (int t = tid; t < Dp; t += kCgThreads) {
-        double key = __builtin_inf();
-        if (t < D) key = (double)a.Xp[(int64_t)a.col[start + t] * a.ldp + s];
-        else if (t == D) key = 0.0;
-        keys[t] = key;
-        idx[t] = t;
-      }
-      __syncthreads();
-      for (int size = 2; size <= Dp; size <<= 1) {
-        for (int st = size >> 1; st >= 1; st >>= 1) {
-          for (int j = tid; j < Dp; j += kCgThreads) {
-            const int k = j ^ st;
-            if (k > j) {
-              const double kj = keys[j], kk = keys[k];
-              const int ij = idx[j], ik = idx[k];
-              const bool up = (j & size) == 0;
-              const bool gt = kj > kk || (kj == kk && ij > ik);
-              if (gt == up) {
-                keys[j] = kk;
-                keys[k] = kj;
-                idx[j] = ik;
-                idx[k] = ij;
-              }
-            }
-          }
-          __syncthreads();
-        }
-      }
-      double run = 0.0;
-      for (int b0 = 0; b0 < Dtot; b0 += kCgThreads) {
-        const int t = b0 + tid;
-        const double wv = t < Dtot ? raw_weight(idx[t]) * invM : 0.0;
-        double tot;
-        const double inc = cg_block_scan(wv, red, &tot);
-        if (t < Dtot) cw[t] = run + inc;
-        run += tot;
-      }
-      __syncthreads();
-      if (backward)
-        for (int t = tid; t < Dtot; t += kCgThreads) { gks[t] = 0.0; hr[t] = 0.0; }   // each t is owned by one thread below
-      for (int f = 0; f < a.F; ++f) {
-        const double xi = (double)a.freqs[f];
-        const int64_t oc = (int64_t)a.has_mass + (int64_t)s * a.F + f;
-        const double gk = backward ? a.out_scale * (double)a.g[row * a.ldg + oc] : 0.0;
-        if (backward && gk == 0.0) continue;                                           // workgroup-uniform
-        double acc = 0.0, dacc = 0.0;
-        for (int t = tid; t < Dtot; t += kCgThreads) {
-          const double wv = raw_weight(idx[t]) * invM;
-          const double c = cw[t];
-          const double B = xi * (2.0 * c - wv);
-          const double sc = sinc_c(xi * wv);
-          const double cb = cospi(B);
-          const double delta = 2.0 * wv * sc * cb;
-          const double key = keys[t];
-          acc += delta * key;
-          if (backward) {
-            const double ddelta = 2.0 * wv * (wv * dsinc_c(xi * wv) * cb - sc * kPi * (2.0 * c - wv) * sinpi(B));
-            dacc += (delta + (1.0 + xi) * ddelta) * key;
-            gks[t] += gk * (1.0 + xi) * delta;
-            if (a.gw) {
-              const double knext = t + 1 < Dtot ? keys[t + 1] : 0.0;
-              hr[t] += gk * 2.0 * (1.0 + xi) * cospi(2.0 * xi * c) * (key - knext);
-            }
-          }
-        }
-        if (!backward) {
-          const double val = cg_block_sum(acc, red);
-          if (tid == 0) a.out[row * a.ldo + oc] = (T)(a.out_scale * ((1.0 + xi) * val + (a.bias ? (double)a.bias[oc] : 0.0)));
-        } else if (a.gfreq) {
-          const double dv = cg_block_sum(dacc, red);
-          if (tid == 0) atomic_add_t(&a.gfreq[f], gk * dv);
-        }
-      }
-      if (backward) {
-        if (a.gkey)
-          for (int t = tid; t < Dtot; t += kCgThreads) {
-            const int e = idx[t];
-            if (e < D) a.gkey[(int64_t)(start + e) * a.ldk + s] = (T)gks[t];
-          }
-        if (a.gw) {
-          __syncthreads();
-          double hc = 0.0;
-          for (int t = tid; t < Dtot; t += kCgThreads) hc += hr[t] * cw[t];
-          const double HC = cg_block_sum(hc, red);
-          double runr = 0.0;
-          const int nchunk = (Dtot + kCgThreads - 1) / kCgThreads;
-          for (int cix = nchunk - 1; cix >= 0; --cix) {
-            const int t = cix * kCgThreads + (kCgThreads - 1 - tid);
-            const double hv = t < Dtot ? hr[t] : 0.0;
-            double tot;
-            const double inc = cg_block_scan(hv, red, &tot);
-            __syncthreads();
-            if (t < Dtot) hr[t] = runr + inc;
-            runr += tot;
-          }
-          __syncthreads();
-          double rp = 0.0;
-          for (int t = tid; t < Dtot; t += kCgThreads)
-            if (idx[t] == D) rp = hr[t];
-          const double Rpad = cg_block_sum(rp, red);
-          const double corr = (m <= a.tau ? Rpad : 0.0) + (m >= a.tau ? HC : 0.0);
-          for (int t = tid; t < Dtot; t += kCgThreads) {
-            const int e = idx[t];
-            const double v = (hr[t] - corr) * invM;
-            if (e < D && v != 0.0) atomic_add_t(&a.gw[start + e], v);
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-int64_t cart_line_elems(int64_t max_degree) {
-  int64_t line = 1;
-  while (line < max_degree + 1) line <<= 1;
-  return line;
-}
-
-template <class T>
-int run_cart_generic(const fsw_cart_args* c, const int32_t* rows, int64_t num_rows, int min_deg, hipStream_t stream) {
-  CartGen<T> a;
-  a.rowptr = c->rowptr; a.col = c->col; a.w = (const T*)c->w; a.rows = rows; a.num_rows = num_rows; a.min_deg = min_deg;
-  a.Xp = (const T*)c->Xp; a.ldp = c->ldp; a.freqs = (const T*)c->freqs; a.S = c->S; a.F = c->F; a.tau = c->tau;
-  a.out = (T*)c->out; a.ldo = c->ldo; a.bias = (const T*)c->bias; a.out_scale = c->out_scale;
-  a.has_mass = c->has_mass; a.mass_fn = c->mass_fn; a.mass_scale = c->mass_scale;
-  a.g = (const T*)c->g; a.ldg = c->ldg; a.gkey = (T*)c->gkey; a.ldk = c->ldk; a.gfreq = (T*)c->gfreq; a.gw = (T*)c->gw;
-  a.line_elems = cart_line_elems(c->max_degree);
-  a.scratch = (char*)c->scratch;
-  const int64_t per_wg = a.line_elems * kCartScratchBytesPerElem;
-  int64_t nwg = std::min<int64_t>(num_rows, 2048);
-  nwg = std::min<int64_t>(nwg, (int64_t)(c->scratch_bytes / (size_t)per_wg));
-  FSW_REQUIRE(c->scratch && nwg >= 1, "fsw_embed_cart: scratch buffer too small (need fsw_embed_cart_generic_scratch_bytes)");
-  k_embed_cart_generic<T><<<(unsigned)nwg, kCgThreads, 0, stream>>>(a);
-  FSW_LAUNCH_CHECK();
-  return 0;
-}
 
 // ---- tuned float32 forward ------------------------------------------------------------------------------------------------
 struct CartTuned {
@@ -522,10 +282,6 @@ int bin_upper_degree(int b) {
   return 1 << 30;
 }
 
-int launch_cart_generic_f32(const fsw_cart_args* c, const int32_t* rows, int64_t num_rows, int min_deg, hipStream_t stream) {
-  return run_cart_generic<float>(c, rows, num_rows, min_deg, stream);
-}
-
 int cart_check_common(const fsw_cart_args* c) {
   FSW_REQUIRE(c, "fsw_embed_cart: null args");
   FSW_REQUIRE(c->rowptr && c->Xp && c->freqs && (c->num_rows == 0 || c->col || c->max_degree == 0), "fsw_embed_cart: null pointer");
@@ -541,14 +297,6 @@ int cart_check_common(const fsw_cart_args* c) {
 
 using namespace fsw;
 
-extern "C" size_t fsw_embed_cart_generic_scratch_bytes(int64_t max_degree, int64_t num_rows) {
-  const size_t per_wg = (size_t)cart_line_elems(max_degree) * kCartScratchBytesPerElem;
-  const size_t cap = (size_t)1 << 30;
-  size_t nwg = (size_t)std::max<int64_t>(1, std::min<int64_t>(num_rows, 2048));
-  nwg = std::max<size_t>(1, std::min<size_t>(nwg, cap / per_wg));
-  return nwg * per_wg;
-}
-
 extern "C" int fsw_embed_cart_generic(const fsw_cart_args* c, fsw_stream_t stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   int rc;
@@ -561,8 +309,7 @@ extern "C" int fsw_embed_cart_generic(const fsw_cart_args* c, fsw_stream_t strea
     FSW_REQUIRE(c->out && c->ldo >= width, "fsw_embed_cart_generic: bad output");
   }
   if (c->num_rows == 0) return 0;
-  return c->value_dtype == 0 ? run_cart_generic<float>(c, nullptr, c->num_rows, 0, stream)
-                             : run_cart_generic<double>(c, nullptr, c->num_rows, 0, stream);
+  return launch_embed_generic(generic_args(*c, true, c->F), c->value_dtype, nullptr, c->num_rows, 0, stream);
 }
 
 extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) {
@@ -603,31 +350,17 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   }
   // 33 <= line <= 2048: one wavefront per (row, slice); consecutive bins that need the same keys per lane share a launch
   const int extra = unit_fast ? 0 : 1;
-  int b = FSW_BIN_MID0;
-  while (b < FSW_BIN_HUB0) {
-    const int Mb = (int)std::min<uint32_t>(32, pow2ceil((uint32_t)ceil_div(bin_upper_degree(b) + extra, kWave)));
-    int e = b;
-    while (e + 1 < FSW_BIN_HUB0 &&
-           (int)std::min<uint32_t>(32, pow2ceil((uint32_t)ceil_div(bin_upper_degree(e + 1) + extra, kWave))) == Mb)
-      ++e;
-    const int p0 = bs[b], rows = bs[e + 1] - bs[b];
+  rc = for_each_wave_group(bs, extra, [&](int Mb, int p0, int rows) {
     switch (Mb) {
-      case 1: rc = launch_cart_wave<1>(t, !unit_fast, p0, rows, c->S, stream); break;
-      case 2: rc = launch_cart_wave<2>(t, !unit_fast, p0, rows, c->S, stream); break;
-      case 4: rc = launch_cart_wave<4>(t, !unit_fast, p0, rows, c->S, stream); break;
-      case 8: rc = launch_cart_wave<8>(t, !unit_fast, p0, rows, c->S, stream); break;
-      case 16: rc = launch_cart_wave<16>(t, !unit_fast, p0, rows, c->S, stream); break;
-      default: rc = launch_cart_wave<32>(t, !unit_fast, p0, rows, c->S, stream); break;
+      case 1: return launch_cart_wave<1>(t, !unit_fast, p0, rows, c->S, stream);
+      case 2: return launch_cart_wave<2>(t, !unit_fast, p0, rows, c->S, stream);
+      case 4: return launch_cart_wave<4>(t, !unit_fast, p0, rows, c->S, stream);
+      case 8: return launch_cart_wave<8>(t, !unit_fast, p0, rows, c->S, stream);
+      case 16: return launch_cart_wave<16>(t, !unit_fast, p0, rows, c->S, stream);
+      default: return launch_cart_wave<32>(t, !unit_fast, p0, rows, c->S, stream);
     }
-    if (rc) return rc;
-    b = e + 1;
-  }
-  // longer lines (D > 2048; general weights: D + 1 > 2048): the generic kernel on the rows of the last LDS bin and above
-  const int min_long = kCartMaxLine + 1 - extra;
-  if (c->max_degree >= min_long) {
-    const int p0 = bs[FSW_BIN_LDS0 + FSW_NUM_LDS_BINS - 1];
-    const int64_t rows = (int64_t)bs[FSW_NUM_BINS] - p0;
-    if (rows > 0 && (rc = run_cart_generic<float>(c, c->perm + p0, rows, min_long, stream))) return rc;
-  }
-  return 0;
+  });
+  if (rc) return rc;
+  // longer lines (D > 2048; general weights: D + 1 > 2048): the generic kernel
+  return launch_cart_long_rows(c, extra, stream);
 }

@@ -14,7 +14,7 @@
 //   33 <= L <= 2048  one wavefront per (row, slice), the line sorted across it as 64-bit (key, index) words (wave_sort.h); every
 //                    lane keeps its M sorted elements and accumulates their gradients over the frequency loop (g_f and xi_f
 //                    wave-uniform); the lower bound of a lane's first element comes from its neighbour lane.
-//   longer lines     k_embed_cart_generic in backward mode (embed_cart.hip), as in the forward.
+//   longer lines     the generic kernel in backward mode (k_embed_generic, embed_generic.hip), as in the forward.
 // gfreq: the register class sums a workgroup's partials in LDS, the wavefront class across the wavefront; one float atomic per
 // (workgroup resp. wavefront, frequency).
 #include <algorithm>
@@ -411,30 +411,17 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
   }
   // 33 <= line <= 2048: one wavefront per (row, slice); the forward's grouping of the degree bins by keys per lane
   const int extra = unit_fast ? 0 : 1;
-  auto keys_per_lane = [&](int b) { return (int)std::min<uint32_t>(32, pow2ceil((uint32_t)ceil_div(bin_upper_degree(b) + extra, kWave))); };
-  int b = FSW_BIN_MID0;
-  while (b < FSW_BIN_HUB0) {
-    const int Mb = keys_per_lane(b);
-    int e = b;
-    while (e + 1 < FSW_BIN_HUB0 && keys_per_lane(e + 1) == Mb) ++e;
-    const int p0 = bs[b], rows = bs[e + 1] - bs[b];
+  rc = for_each_wave_group(bs, extra, [&](int Mb, int p0, int rows) {
     switch (Mb) {
-      case 1: rc = launch_cart_bwd_wave<1>(t, !unit_fast, p0, rows, stream); break;
-      case 2: rc = launch_cart_bwd_wave<2>(t, !unit_fast, p0, rows, stream); break;
-      case 4: rc = launch_cart_bwd_wave<4>(t, !unit_fast, p0, rows, stream); break;
-      case 8: rc = launch_cart_bwd_wave<8>(t, !unit_fast, p0, rows, stream); break;
-      case 16: rc = launch_cart_bwd_wave<16>(t, !unit_fast, p0, rows, stream); break;
-      default: rc = launch_cart_bwd_wave<32>(t, !unit_fast, p0, rows, stream); break;
+      case 1: return launch_cart_bwd_wave<1>(t, !unit_fast, p0, rows, stream);
+      case 2: return launch_cart_bwd_wave<2>(t, !unit_fast, p0, rows, stream);
+      case 4: return launch_cart_bwd_wave<4>(t, !unit_fast, p0, rows, stream);
+      case 8: return launch_cart_bwd_wave<8>(t, !unit_fast, p0, rows, stream);
+      case 16: return launch_cart_bwd_wave<16>(t, !unit_fast, p0, rows, stream);
+      default: return launch_cart_bwd_wave<32>(t, !unit_fast, p0, rows, stream);
     }
-    if (rc) return rc;
-    b = e + 1;
-  }
-  // longer lines (D > 2048; general weights: D + 1 > 2048): the generic kernel in backward mode on the rows of the last LDS bin and above
-  const int min_long = kCartMaxLine + 1 - extra;
-  if (c->max_degree >= min_long) {
-    const int p0 = bs[FSW_BIN_LDS0 + FSW_NUM_LDS_BINS - 1];
-    const int64_t rows = (int64_t)bs[FSW_NUM_BINS] - p0;
-    if (rows > 0 && (rc = launch_cart_generic_f32(c, c->perm + p0, rows, min_long, stream))) return rc;
-  }
-  return 0;
+  });
+  if (rc) return rc;
+  // longer lines (D > 2048; general weights: D + 1 > 2048): the generic kernel in backward mode
+  return launch_cart_long_rows(c, extra, stream);
 }

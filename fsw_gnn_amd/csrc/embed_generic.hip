@@ -1,9 +1,9 @@
-// Generic neighbourhood kernels, any in-degree, float32 or float64 storage: the float64 build of the path and the
-// gradients with respect to the weights.  gfx950.
+// The generic neighbourhood kernel, any in-degree, float32 or float64 storage: the float64 build of the path, the gradients with
+// respect to the weights, and the long rows of tuned Cartesian mode.  gfx950.
 //
-// The tuned kernels (embed_reg / embed_mid / embed_hub / embed_wsort) are float32, specialised per degree class and treat the
-// weights as constants.  This file restates the same per-neighbourhood computation once, for every degree and both value
-// types, with all arithmetic in float64:
+// The tuned kernels (embed_reg / embed_mid / embed_hub / embed_wsort, embed_cart) are float32, specialised per degree class and
+// treat the weights as constants.  This file states the same per-neighbourhood computation once, for every degree, both value
+// types and both readouts, with all arithmetic in float64:
 //   T = double   FSW_embedding / FSW_conv(dtype=torch.float64) (the reference's test_conv.py runs the layer in float64,
 //                test_conv.py:24): forward and backward, pinned to the reference's float64 goldens at 1e-12;
 //   T = float    d loss / d W for the float32 path (reference ag.div_sparse_dense.backward fsw_embedding.py:1656,
@@ -14,50 +14,25 @@
 // workgroup scan (the segmented cumsum of fsw_embedding.py:1031-1032); readout
 //   Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t))      (fsw_embedding.py:1047-1075, the product form: no cancellation)
 //   out     = (1 + xi) sum_t Delta_t p_(t)                      (fsw_embedding.py:1084-1109).
-// Backward: d out / d p_(t) = (1 + xi) Delta_t stored per CSR entry (gkey), d out / d xi summed per slice, and for the weights
-//   d out / d c_t = 2 (1 + xi) cos(2 pi xi c_t) (p_(t) - p_(t+1)),   c_t = A_t / M,  A_t = raw cumulative weight,  M = max(m, tau)
+// The sorted slice s is read out at
+//   diagonal   (fsw_embed_generic)        xi = freqs[s] alone, into column has_mass + s;
+//   Cartesian  (fsw_embed_cart_generic)   every xi = freqs[f], f < F, into column has_mass + s F + f (reference :1037-1045).
+// Backward, with gk = out_scale g[row, column] per readout: d out / d p_(t) = (1 + xi) Delta_t, summed over the slice's readouts
+// and stored per CSR entry (gkey), d out / d xi summed per frequency, and for the weights
+//   d out / d c_t = 2 (1 + xi) cos(2 pi xi c_t) (p_(t) - p_(t+1)) = H_t,   c_t = A_t / M,  A_t = raw cumulative weight,  M = max(m, tau)
 //   d out / d a_j = [ R(rank_j) - [m <= tau] R(rank_pad) - [m >= tau] sum_t H_t c_t ] / M,   R(r) = sum_{t >= r} H_t
 // (a reverse cumulative sum over the sorted order; the two clamps pass gradients like the reference's custom_lowclamp, :1735-1744).
+// The weight gradient is linear in H_t, so gk H_t is summed over the slice's readouts first and the reverse cumulative sum runs once
+// per slice.  With one readout per slice this gives what multiplying by gk at the end gives: the forward, gkey (0 + x) and gfreq
+// bit for bit, and gw up to float64 rounding (gk (R - corr) became the reverse sum of gk H_t minus its own corr).
 #include <algorithm>
-#include "fsw_common.h"
+#include "embed_launch.h"
 
 namespace fsw {
 
 constexpr int kGenThreads = 256;
 constexpr int kGenLdsElems = 2048;   // lines up to this many elements are sorted in LDS
-
-template <class T>
-struct GenArgs {
-  const int32_t* rowptr;
-  const int32_t* col;
-  const T* w;        // [nnz] raw weights or null (unit)
-  int64_t num_rows;
-  const T* Xp;       // [num_cols, ldp]
-  int64_t ldp;
-  const T* Ke;       // [nnz, ldke] edge-feature term of every key, or null
-  int64_t ldke;
-  const T* freqs;
-  int S;
-  double tau;
-  // forward
-  T* out;
-  int64_t ldo;
-  const T* bias;
-  double out_scale;
-  int has_mass, mass_fn;
-  double mass_scale;
-  // backward (g != null): gkey [nnz, ldk] stored, gfreq [S] and gw [nnz] accumulated with atomics (zeroed by the caller)
-  const T* g;
-  int64_t ldg;
-  T* gkey;
-  int64_t ldk;
-  T* gfreq;
-  T* gw;
-  // scratch: per workgroup line_elems * kGenScratchBytesPerElem bytes
-  char* scratch;
-  int64_t line_elems;
-};
-constexpr int kGenScratchBytesPerElem = 8 + 4 + 8 + 8;   // key, index, cumulative weight, H / reverse sum
+constexpr int kGenMaxWorkgroups = 2048;
 
 __device__ __forceinline__ double sinc_g(double z) { return z == 0.0 ? 1.0 : sinpi(z) / (kPi * z); }
 __device__ __forceinline__ double dsinc_g(double z) { return z == 0.0 ? 0.0 : (cospi(z) - sinc_g(z)) / z; }   // reference sp.dsinc :2760-2774
@@ -94,20 +69,33 @@ __device__ __forceinline__ double block_inclusive_scan(double v, double* red /* 
 }
 
 template <class T>
-__global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs<T> a) {
+__global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs a) {
   __shared__ double lkey[kGenLdsElems];
   __shared__ int lidx[kGenLdsElems];
   __shared__ double red[4];
+  const T* const w = (const T*)a.w;
+  const T* const Xp = (const T*)a.Xp;
+  const T* const Ke = (const T*)a.Ke;
+  const T* const freqs = (const T*)a.freqs;
+  const T* const bias = (const T*)a.bias;
+  const T* const g = (const T*)a.g;
+  T* const out = (T*)a.out;
+  T* const gkey = (T*)a.gkey;
+  T* const gfreq = (T*)a.gfreq;
+  T* const gw = (T*)a.gw;
   char* myscr = a.scratch + (int64_t)blockIdx.x * a.line_elems * kGenScratchBytesPerElem;
   double* gkeyb = reinterpret_cast<double*>(myscr);                       // [line_elems] keys (rows above the LDS size)
   double* cw = gkeyb + a.line_elems;                                      // [line_elems] cumulative normalised weight
-  double* hr = cw + a.line_elems;                                         // [line_elems] H_t, then reverse sums
-  int* gidx = reinterpret_cast<int*>(hr + a.line_elems);                  // [line_elems]
-  const bool backward = a.g != nullptr;
+  double* hr = cw + a.line_elems;                                         // [line_elems] sum of gk H_t, then reverse sums
+  double* gks = hr + a.line_elems;                                        // [line_elems] key gradient of the sorted element
+  int* gidx = reinterpret_cast<int*>(gks + a.line_elems);                 // [line_elems]
+  const bool backward = g != nullptr;
   const int tid = threadIdx.x;
-  for (int64_t row = blockIdx.x; row < a.num_rows; row += gridDim.x) {
+  for (int64_t i = blockIdx.x; i < a.num_rows; i += gridDim.x) {
+    const int64_t row = a.rows ? (int64_t)a.rows[i] : i;
     const int start = a.rowptr[row];
     const int D = a.rowptr[row + 1] - start;
+    if (D < a.min_deg) continue;                                           // workgroup-uniform
     const int Dtot = D + 1;                                                // + the pad element
     int Dp = 1;
     while (Dp < Dtot) Dp <<= 1;
@@ -116,21 +104,21 @@ __global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs<T> 
     int* idx = in_lds ? lidx : gidx;
     // total mass, pad weight, normalisation (fsw_embedding.py:778-829)
     double part = 0.0;
-    for (int t = tid; t < D; t += kGenThreads) part += a.w ? (double)a.w[start + t] : 1.0;
+    for (int t = tid; t < D; t += kGenThreads) part += w ? (double)w[start + t] : 1.0;
     const double m = block_sum(part, red);
     const double M = fmax(m, a.tau);
     const double padw = fmax(a.tau - m, 0.0);
     const double invM = 1.0 / M;
-    auto raw_weight = [&](int e) -> double { return e < D ? (a.w ? (double)a.w[start + e] : 1.0) : (e == D ? padw : 0.0); };
+    auto raw_weight = [&](int e) -> double { return e < D ? (w ? (double)w[start + e] : 1.0) : (e == D ? padw : 0.0); };
     if (!backward && a.has_mass && tid == 0)
-      a.out[row * a.ldo] = (T)mass_column(m, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
-    for (int k = 0; k < a.S; ++k) {
+      out[row * a.ldo] = (T)mass_column(m, a.mass_fn, a.mass_scale, bias, a.out_scale);
+    for (int s = 0; s < a.S; ++s) {
       // A. keys
       for (int t = tid; t < Dp; t += kGenThreads) {
         double key = __builtin_inf();
         if (t < D) {
-          key = (double)a.Xp[(int64_t)a.col[start + t] * a.ldp + k];
-          if (a.Ke) key += (double)a.Ke[(int64_t)(start + t) * a.ldke + k];
+          key = (double)Xp[(int64_t)a.col[start + t] * a.ldp + s];
+          if (Ke) key += (double)Ke[(int64_t)(start + t) * a.ldke + s];
         } else if (t == D) {
           key = 0.0;
         }
@@ -141,18 +129,18 @@ __global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs<T> 
       // B. bitonic sort by (key, index)
       for (int size = 2; size <= Dp; size <<= 1) {
         for (int st = size >> 1; st >= 1; st >>= 1) {
-          for (int i = tid; i < Dp; i += kGenThreads) {
-            const int j = i ^ st;
-            if (j > i) {
-              const double ki = keys[i], kj = keys[j];
-              const int ii = idx[i], ij = idx[j];
-              const bool up = (i & size) == 0;
-              const bool gt = ki > kj || (ki == kj && ii > ij);
+          for (int j = tid; j < Dp; j += kGenThreads) {
+            const int k = j ^ st;
+            if (k > j) {
+              const double kj = keys[j], kk = keys[k];
+              const int ij = idx[j], ik = idx[k];
+              const bool up = (j & size) == 0;
+              const bool gt = kj > kk || (kj == kk && ij > ik);
               if (gt == up) {
-                keys[i] = kj;
-                keys[j] = ki;
-                idx[i] = ij;
-                idx[j] = ii;
+                keys[j] = kk;
+                keys[k] = kj;
+                idx[j] = ik;
+                idx[k] = ij;
               }
             }
           }
@@ -170,40 +158,50 @@ __global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs<T> 
         run += tot;
       }
       __syncthreads();
-      const double xi = (double)a.freqs[k];
-      // D. readout (and the per-key coefficients for the backward)
-      const double gk = backward ? a.out_scale * (double)a.g[row * a.ldg + a.has_mass + k] : 0.0;
-      double acc = 0.0, dacc = 0.0;
-      for (int t = tid; t < Dtot; t += kGenThreads) {
-        const int e = idx[t];
-        const double wv = raw_weight(e) * invM;
-        const double c = cw[t];
-        const double B = xi * (2.0 * c - wv);            // phase / pi
-        const double sc = sinc_g(xi * wv);
-        const double cb = cospi(B);
-        const double delta = 2.0 * wv * sc * cb;
-        const double key = keys[t];
-        acc += delta * key;
-        if (backward) {
-          const double ddelta = 2.0 * wv * (wv * dsinc_g(xi * wv) * cb - sc * kPi * (2.0 * c - wv) * sinpi(B));
-          dacc += (delta + (1.0 + xi) * ddelta) * key;
-          if (e < D && a.gkey) a.gkey[(int64_t)(start + e) * a.ldk + k] = (T)(gk * (1.0 + xi) * delta);
-          if (a.gw) {
-            const double knext = t + 1 < Dtot ? keys[t + 1] : 0.0;
-            hr[t] = 2.0 * (1.0 + xi) * cospi(2.0 * xi * c) * (key - knext);
+      if (backward)
+        for (int t = tid; t < Dtot; t += kGenThreads) { gks[t] = 0.0; hr[t] = 0.0; }   // each t is owned by one thread below
+      // D. readouts of the sorted slice (and the per-key coefficients for the backward)
+      const int f0 = a.cartesian ? 0 : s, f1 = a.cartesian ? a.F : s + 1;
+      for (int f = f0; f < f1; ++f) {
+        const double xi = (double)freqs[f];
+        const int64_t oc = (int64_t)a.has_mass + (a.cartesian ? (int64_t)s * a.F + f : (int64_t)s);
+        const double gk = backward ? a.out_scale * (double)g[row * a.ldg + oc] : 0.0;
+        if (backward && gk == 0.0) continue;                                           // workgroup-uniform
+        double acc = 0.0, dacc = 0.0;
+        for (int t = tid; t < Dtot; t += kGenThreads) {
+          const double wv = raw_weight(idx[t]) * invM;
+          const double c = cw[t];
+          const double B = xi * (2.0 * c - wv);            // phase / pi
+          const double sc = sinc_g(xi * wv);
+          const double cb = cospi(B);
+          const double delta = 2.0 * wv * sc * cb;
+          const double key = keys[t];
+          acc += delta * key;
+          if (backward) {
+            const double ddelta = 2.0 * wv * (wv * dsinc_g(xi * wv) * cb - sc * kPi * (2.0 * c - wv) * sinpi(B));
+            dacc += (delta + (1.0 + xi) * ddelta) * key;
+            gks[t] += gk * (1.0 + xi) * delta;
+            if (gw) {
+              const double knext = t + 1 < Dtot ? keys[t + 1] : 0.0;
+              hr[t] += gk * 2.0 * (1.0 + xi) * cospi(2.0 * xi * c) * (key - knext);
+            }
           }
         }
-      }
-      if (!backward) {
-        const double val = block_sum(acc, red);
-        if (tid == 0)
-          a.out[row * a.ldo + a.has_mass + k] = (T)(a.out_scale * ((1.0 + xi) * val + (a.bias ? (double)a.bias[a.has_mass + k] : 0.0)));
-      } else {
-        if (a.gfreq) {
+        if (!backward) {
+          const double val = block_sum(acc, red);
+          if (tid == 0) out[row * a.ldo + oc] = (T)(a.out_scale * ((1.0 + xi) * val + (bias ? (double)bias[oc] : 0.0)));
+        } else if (gfreq) {
           const double dv = block_sum(dacc, red);
-          if (tid == 0 && gk != 0.0) atomic_add_t(&a.gfreq[k], gk * dv);
+          if (tid == 0) atomic_add_t(&gfreq[f], gk * dv);
         }
-        if (a.gw) {
+      }
+      if (backward) {
+        if (gkey)
+          for (int t = tid; t < Dtot; t += kGenThreads) {
+            const int e = idx[t];
+            if (e < D) gkey[(int64_t)(start + e) * a.ldk + s] = (T)gks[t];
+          }
+        if (gw) {
           // E. weights: reverse cumulative sums of H over the sorted order, sum_t H_t c_t, the pad element's rank
           __syncthreads();
           double hc = 0.0;
@@ -228,7 +226,8 @@ __global__ void __launch_bounds__(kGenThreads) k_embed_generic(const GenArgs<T> 
           const double corr = (m <= a.tau ? Rpad : 0.0) + (m >= a.tau ? HC : 0.0);
           for (int t = tid; t < Dtot; t += kGenThreads) {
             const int e = idx[t];
-            if (e < D && gk != 0.0) atomic_add_t(&a.gw[start + e], gk * (hr[t] - corr) * invM);
+            const double v = (hr[t] - corr) * invM;
+            if (e < D && v != 0.0) atomic_add_t(&gw[start + e], v);
           }
         }
       }
@@ -272,23 +271,38 @@ __global__ void __launch_bounds__(256) k_project_f64(const double* __restrict__ 
   if (stats && nonfinite && ct == 0) atomicOr(&stats[FSW_STAT_FLAGS], FSW_FLAG_X_NONFINITE);
 }
 
-template <class T>
-static int run_generic(const fsw_generic_args* g, hipStream_t stream) {
-  GenArgs<T> a;
-  a.rowptr = g->rowptr; a.col = g->col; a.w = (const T*)g->w; a.num_rows = g->num_rows;
-  a.Xp = (const T*)g->Xp; a.ldp = g->ldp; a.Ke = (const T*)g->Ke; a.ldke = g->ldke; a.freqs = (const T*)g->freqs; a.S = g->S;
-  a.tau = g->tau; a.out = (T*)g->out; a.ldo = g->ldo; a.bias = (const T*)g->bias; a.out_scale = g->out_scale;
-  a.has_mass = g->has_mass; a.mass_fn = g->mass_fn; a.mass_scale = g->mass_scale;
-  a.g = (const T*)g->g; a.ldg = g->ldg; a.gkey = (T*)g->gkey; a.ldk = g->ldk; a.gfreq = (T*)g->gfreq; a.gw = (T*)g->gw;
-  int64_t line = 1;
-  while (line < g->max_degree + 1) line <<= 1;
-  a.line_elems = line;
-  a.scratch = (char*)g->scratch;
-  const int64_t per_wg = line * kGenScratchBytesPerElem;
-  int64_t nwg = std::min<int64_t>(g->num_rows, 2048);
-  nwg = std::min<int64_t>(nwg, (int64_t)(g->scratch_bytes / (size_t)per_wg));
-  FSW_REQUIRE(nwg >= 1, "fsw_embed_generic: scratch buffer too small (need fsw_embed_generic_scratch_bytes)");
-  k_embed_generic<T><<<(unsigned)nwg, kGenThreads, 0, stream>>>(a);
+// The scratch of a launch on num_rows rows of up to max_degree neighbours within `bytes` bytes: one line per workgroup, of the
+// next power of two >= max_degree + 1 elements (the bitonic sort's size, pad element included).
+struct GenScratch {
+  int64_t line_elems;
+  size_t wg_bytes;
+  int64_t workgroups;   // 0: not even one line fits
+};
+
+static GenScratch generic_scratch_layout(int64_t max_degree, int64_t num_rows, size_t bytes) {
+  GenScratch l;
+  l.line_elems = 1;
+  while (l.line_elems < max_degree + 1) l.line_elems <<= 1;
+  l.wg_bytes = (size_t)l.line_elems * kGenScratchBytesPerElem;
+  l.workgroups = std::min<int64_t>(std::min<int64_t>(num_rows, kGenMaxWorkgroups), (int64_t)(bytes / l.wg_bytes));
+  return l;
+}
+
+static size_t generic_scratch_bytes(int64_t max_degree, int64_t num_rows) {
+  const GenScratch l = generic_scratch_layout(max_degree, std::max<int64_t>(num_rows, 1), (size_t)1 << 30);
+  return (size_t)std::max<int64_t>(l.workgroups, 1) * l.wg_bytes;
+}
+
+int launch_embed_generic(GenArgs a, int value_dtype, const int32_t* rows, int64_t num_rows, int min_deg, hipStream_t stream) {
+  a.rows = rows;
+  a.num_rows = num_rows;
+  a.min_deg = min_deg;
+  const GenScratch l = generic_scratch_layout(a.max_degree, num_rows, a.scratch ? a.scratch_bytes : 0);
+  a.line_elems = l.line_elems;
+  FSW_REQUIRE(l.workgroups >= 1, a.cartesian ? "fsw_embed_cart: scratch buffer too small (need fsw_embed_cart_generic_scratch_bytes)"
+                                             : "fsw_embed_generic: scratch buffer too small (need fsw_embed_generic_scratch_bytes)");
+  if (value_dtype == 0) k_embed_generic<float><<<(unsigned)l.workgroups, kGenThreads, 0, stream>>>(a);
+  else k_embed_generic<double><<<(unsigned)l.workgroups, kGenThreads, 0, stream>>>(a);
   FSW_LAUNCH_CHECK();
   return 0;
 }
@@ -298,13 +312,11 @@ static int run_generic(const fsw_generic_args* g, hipStream_t stream) {
 using namespace fsw;
 
 extern "C" size_t fsw_embed_generic_scratch_bytes(int64_t max_degree, int64_t num_rows) {
-  int64_t line = 1;
-  while (line < max_degree + 1) line <<= 1;
-  const size_t per_wg = (size_t)line * kGenScratchBytesPerElem;
-  const size_t cap = (size_t)1 << 30;
-  size_t nwg = (size_t)std::max<int64_t>(1, std::min<int64_t>(num_rows, 2048));
-  nwg = std::max<size_t>(1, std::min<size_t>(nwg, cap / per_wg));
-  return nwg * per_wg;
+  return generic_scratch_bytes(max_degree, num_rows);
+}
+
+extern "C" size_t fsw_embed_cart_generic_scratch_bytes(int64_t max_degree, int64_t num_rows) {
+  return generic_scratch_bytes(max_degree, num_rows);
 }
 
 extern "C" int fsw_embed_generic(const fsw_generic_args* g, fsw_stream_t stream_) {
@@ -320,7 +332,10 @@ extern "C" int fsw_embed_generic(const fsw_generic_args* g, fsw_stream_t stream_
     FSW_REQUIRE(g->out && g->ldo >= g->S + g->has_mass, "fsw_embed_generic: bad output");
   }
   if (g->num_rows == 0) return 0;
-  return g->value_dtype == 0 ? run_generic<float>(g, stream) : run_generic<double>(g, stream);
+  GenArgs a = generic_args(*g, false, 1);
+  a.Ke = g->Ke;
+  a.ldke = g->ldke;
+  return launch_embed_generic(a, g->value_dtype, nullptr, g->num_rows, 0, stream);
 }
 
 extern "C" int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double* V, int S, int64_t ldv, double* Xp,

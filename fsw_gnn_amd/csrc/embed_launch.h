@@ -30,6 +30,59 @@ int launch_embed_wsort_lds(const fsw_embed_args& a, int64_t rows_upper, hipStrea
 int launch_embed_wsort_global(const fsw_embed_args& a, int64_t rows_upper, hipStream_t stream);                     // above
 size_t embed_global_scratch_bytes(int64_t max_degree);                                                              // embed_wsort_bwd.hip
 
+// embed_generic.hip: the generic kernel (any degree, float32 or float64 storage behind the void pointers, float64 arithmetic),
+// forward (g == null) or backward.  Sorted slice s is read out at freqs[s] into column has_mass + s (diagonal), or, cartesian, at
+// every freqs[f], f < F, into column has_mass + s F + f.
+struct GenArgs {
+  const int32_t* rowptr;
+  const int32_t* col;
+  const void* w;         // [nnz] raw weights or null (unit)
+  const int32_t* rows;   // null: rows 0 .. num_rows - 1; else rows[0 .. num_rows - 1] (the long rows of the tuned Cartesian entries)
+  int64_t num_rows;
+  int min_deg;           // rows of fewer neighbours are skipped (they belong to another kernel)
+  const void* Xp;        // [num_cols, ldp]
+  int64_t ldp;
+  const void* Ke;        // [nnz, ldke] edge-feature term of every key, or null
+  int64_t ldke;
+  const void* freqs;
+  int S, F;
+  bool cartesian;
+  double tau;
+  // forward
+  void* out;
+  int64_t ldo;
+  const void* bias;
+  double out_scale;
+  int has_mass, mass_fn;
+  double mass_scale;
+  // backward: gkey [nnz, ldk] stored, gfreq and gw [nnz] accumulated with atomics (zeroed by the caller)
+  const void* g;
+  int64_t ldg;
+  void* gkey;
+  int64_t ldk;
+  void* gfreq;
+  void* gw;
+  // scratch: per workgroup line_elems * kGenScratchBytesPerElem bytes (max_degree and scratch_bytes: for the launcher)
+  char* scratch;
+  size_t scratch_bytes;
+  int64_t max_degree, line_elems;
+};
+constexpr int kGenScratchBytesPerElem = 8 + 4 + 8 + 8 + 8;   // key, index, cumulative weight, H / reverse sum, key gradient
+
+// the fields fsw_generic_args and fsw_cart_args have in common by name (rows, num_rows, min_deg, line_elems: the launcher's)
+template <class P>
+GenArgs generic_args(const P& p, bool cartesian, int F) {
+  GenArgs a = {};
+  a.rowptr = p.rowptr; a.col = p.col; a.w = p.w; a.Xp = p.Xp; a.ldp = p.ldp; a.freqs = p.freqs; a.S = p.S; a.F = F;
+  a.cartesian = cartesian; a.tau = p.tau; a.out = p.out; a.ldo = p.ldo; a.bias = p.bias; a.out_scale = p.out_scale;
+  a.has_mass = p.has_mass; a.mass_fn = p.mass_fn; a.mass_scale = p.mass_scale;
+  a.g = p.g; a.ldg = p.ldg; a.gkey = p.gkey; a.ldk = p.ldk; a.gfreq = p.gfreq; a.gw = p.gw;
+  a.scratch = (char*)p.scratch; a.scratch_bytes = p.scratch_bytes; a.max_degree = p.max_degree;
+  return a;
+}
+// value_dtype 0 float32, 1 float64; rows[0 .. num_rows - 1] (null: all of 0 .. num_rows - 1) of at least min_deg neighbours
+int launch_embed_generic(GenArgs a, int value_dtype, const int32_t* rows, int64_t num_rows, int min_deg, hipStream_t stream);
+
 // backward: embed_mid_bwd.hip (33 .. 128) and embed_wsort_bwd.hip (everything above FSW_REG_MAX_DEG; global: rows above FSW_LDS_MAX_DEG)
 int launch_embed_mid_bwd(const fsw_embed_args& a, int64_t rows_upper, const float* g, int64_t ldg, float* gXp, int64_t ldgp,
                          float* gfreq, float* gkey, int64_t ldk, hipStream_t stream);

@@ -13,7 +13,7 @@ csrc/embed_wsort_bwd.hip) for every weight mode and degree class; gradients flow
 total-mass scale (the weights W are constants).
 Edge features (d_edge > 0) go through the coalescing CSR build and the general-weight kernels.
 dtype=torch.float64 modules and gradients w.r.t. the weights W / sparse edge features run on the generic kernels
-(csrc/embed_generic.hip: any degree, float64 arithmetic) through _GenericEmbedFn, which also serves Cartesian mode below.
+(csrc/embed_generic.hip: any degree, float64 arithmetic) through _GenericEmbedFn, which also serves Cartesian mode below (the same kernel).
 The 'homog' / 'homog_alt' total-mass methods are one epilogue in torch (_homog_epilogue) on the kernels' 'plain' output: in place
 for inference, out of place under autograd.  Nothing per call is kept on the module: what a call needs travels as arguments.
 
@@ -358,7 +358,7 @@ class _GenericEmbedFn(torch.autograd.Function):
     the entry point (`variant`); everything else is the same code for both:
 
       fsw_embed_generic (csrc/embed_generic.hip): out [num_rows, has_mass + S], slice s read out at frequency s.
-      fsw_embed_cart_generic (csrc/embed_cart.hip): out [num_rows, has_mass + S F], column has_mass + s F + f = (slice s,
+      fsw_embed_cart_generic (the same kernel; arguments checked in csrc/embed_cart.hip): out [num_rows, has_mass + S F], column has_mass + s F + f = (slice s,
         frequency f); bias flattened, gkey one column per slice, gf one entry per frequency; efvals is always None (no edge features).
 
     Callers: every float64 module (the float64 build of the path, reference test_conv.py:24), float32 modules whose weights or

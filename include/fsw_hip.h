@@ -291,8 +291,8 @@ int fsw_graph_transpose(const int32_t* col, int64_t nnz, int64_t num_cols, int32
 int fsw_segment_sum_rows_f32(const float* src, int64_t lds, const int32_t* ptr, const int32_t* order, int64_t num_out, int64_t nnz,
                              int S, float* out, int64_t ldo, fsw_stream_t stream);
 
-/* ---- generic neighbourhood kernels: any in-degree, float32 or float64 storage, float64 arithmetic ------------------------
- * (csrc/embed_generic.hip)  Two uses:
+/* ---- generic neighbourhood kernel: any in-degree, float32 or float64 storage, float64 arithmetic -------------------------
+ * (csrc/embed_generic.hip; fsw_embed_cart_generic below is the same kernel read out at every frequency)  Two uses:
  *   value_dtype 1 (float64): the float64 build of the path -- FSW_embedding / FSW_conv(dtype=torch.float64), which the
  *       reference's own test_conv.py runs (test_conv.py:24); forward (g == NULL) and backward (g != NULL);
  *   value_dtype 0 (float32): gradients with respect to the weights for the float32 path (gw), which the tuned backward
@@ -308,7 +308,10 @@ int fsw_segment_sum_rows_f32(const float* src, int64_t lds, const int32_t* ptr, 
  *           gfreq[k]          += out_scale * sum_r g[r, k] * d out[r, k] / d xi_k          (accumulated; nullable)
  *           gw[e]             += out_scale * sum_k g[r, k] * d out[r, k] / d w_e           (accumulated; nullable; the
  *                                total-mass column's dependence on w is NOT included).
- * scratch: fsw_embed_generic_scratch_bytes(max_degree, num_rows) bytes.                                                */
+ * scratch: fsw_embed_generic_scratch_bytes(max_degree, num_rows) bytes: 36 bytes per element of a line of the next power of two
+ *          >= max_degree + 1 elements, one line for each of up to 2048 workgroups, at most 1 GiB.  The diagonal and the Cartesian
+ *          entry share the layout, so both *_scratch_bytes functions return the same value (the diagonal one returned 28 bytes
+ *          per element, 7/9 of this, while it had a kernel of its own); always ask the library for the size.          */
 typedef struct {
   int32_t value_dtype;   /* 0 float32, 1 float64 */
   int32_t S;
@@ -347,7 +350,7 @@ int fsw_embed_generic(const fsw_generic_args* args, fsw_stream_t stream);
 int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double* V, int S, int64_t ldv, double* Xp,
                     int64_t ldp, int32_t* stats, fsw_stream_t stream);
 
-/* ---- Cartesian slice x frequency mode (csrc/embed_cart.hip) -------------------------------------------------------------
+/* ---- Cartesian slice x frequency mode (csrc/embed_cart.hip; the generic kernel: csrc/embed_generic.hip) ------------------------
  * FSW_embedding(d_in, nSlices=S, nFreqs=F) (reference fsw_embedding.py:241-259, 1037-1045): every slice s is sorted once and read
  * out at every frequency f.  Column has_mass + s * F + f of out belongs to (slice s, frequency f) (torch.flatten order, :853-854):
  *   out[r * ldo + has_mass + s F + f] = out_scale * ((1 + xi_f) sum_t Delta_t(xi_f) p_(t) + bias[has_mass + s F + f])
@@ -357,9 +360,10 @@ int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double
  * fsw_embed_cart_f32      tuned float32 forward on a graph of fsw_graph_build: needs perm, bin_start and bin_start_host,
  *                         unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1, and scratch of
  *                         fsw_embed_cart_generic_scratch_bytes(max_degree, rows above FSW_LDS_MAX_DEG) bytes when
- *                         max_degree >= FSW_LDS_MAX_DEG (those rows run on the generic kernel).
- * fsw_embed_cart_generic  any degree, float32 or float64 storage (value_dtype), float64 arithmetic, on a plain CSR (perm, bin_start
- *                         ignored); forward (g == NULL) or backward (g != NULL): for the output gradient g [num_rows, ldg]
+ *                         max_degree >= FSW_LDS_MAX_DEG (those rows run on the generic kernel of fsw_embed_cart_generic).
+ * fsw_embed_cart_generic  the kernel of fsw_embed_generic with every sorted slice read out at all F frequencies: any degree, float32 or
+ *                         float64 storage (value_dtype), float64 arithmetic, on a plain CSR (perm, bin_start ignored; no edge term);
+ *                         forward (g == NULL) or backward (g != NULL): for the output gradient g [num_rows, ldg]
  *                           gkey[e * ldk + s]  = sum_f out_scale g[r, has_mass + s F + f] d out / d key_e     (stored; nullable)
  *                           gfreq[f]          += out_scale sum_{r,s} g[r, has_mass + s F + f] d out / d xi_f  (nullable)
  *                           gw[e]             += out_scale sum_{s,f} g[r, has_mass + s F + f] d out / d w_e   (nullable; the

@@ -138,6 +138,64 @@ def test_weight_gradients_vs_reference_autograd(dev, dtype, tol):
     assert relerr(W.grad.cpu().numpy(), gw["cloud_gW"]) < tol
 
 
+def diag_vs_cart_graph(unit):
+    """Eight recipients of in-degree 0, 1, 2, 255, 256 (Dtot on both sides of the 256-thread scan chunk), 2047 (Dtot = 2048, the last
+    LDS line), 2048 (the first global-scratch line) and 300 over 2100 senders; senders 0 and 1 have the same feature row and are
+    neighbours of every recipient of two or more (tied keys -> the index tie-break).  Weighted: total masses 0.4, 0.9, 2.0 (row of
+    255), 0.5 (row of 300) and hundreds, i.e. rows below and above the pad threshold for tau = 1 and for tau = 3; unit: mass =
+    degree (the row of one neighbour sits exactly on tau = 1)."""
+    rng = np.random.default_rng(7)
+    n, d = 2100, 4
+    X = rng.standard_normal((n, d))
+    X[1] = X[0]
+    rows, cols, vals = [], [], []
+    for r, D in enumerate((0, 1, 2, 255, 256, 2047, 2048, 300)):
+        c = np.sort(np.concatenate([[0, 1], 2 + rng.choice(n - 2, D - 2, replace=False)])) if D >= 2 else np.arange(5, 5 + D)
+        w = rng.uniform(0.05, 1.0, D)
+        if D in (1, 2, 255, 300):
+            w *= {1: 0.4, 2: 0.9, 255: 2.0, 300: 0.5}[D] / w.sum()
+        rows.append(np.full(D, r))
+        cols.append(c)
+        vals.append(np.ones(D) if unit else w)
+    return X, np.stack([np.concatenate(rows), np.concatenate(cols)]).astype(np.int64), np.concatenate(vals)
+
+
+@pytest.mark.parametrize("dtype,ftol,gtol", [(torch.float64, F64, G64), (torch.float32, 1e-5, 2e-5)])
+def test_diagonal_entry_equals_diagonal_columns_of_cartesian_entry(dev, dtype, ftol, gtol):
+    """The generic kernel's two entry points are one computation: fsw_embed_generic (slice s at frequency s) gives the columns
+    s * S + s of fsw_embed_cart_generic (every slice at every frequency) on the same projVecs and frequencies, forward and -- with
+    the output gradient confined to those columns -- in the gradients of X, projVecs, freqs and W.  Float64 modules, and float32
+    modules whose W requires a gradient, take the generic kernel in both modes."""
+    from fsw_gnn_amd import FSW_embedding
+    S, d = 3, 4
+    rng = np.random.default_rng(8)
+    V, freqs, R = rng.standard_normal((S, d)), np.array([0.0, 0.7, 2.3]), rng.standard_normal((8, S))
+    diag_cols = torch.arange(S, device=dev) * (S + 1)
+    for unit, tau in ((False, 1.0), (False, 3.0), (True, 1.0), (True, 3.0)):
+        Xn, idx, vals = diag_vs_cart_graph(unit)
+        res = []
+        for cart in (False, True):
+            kw = dict(nSlices=S, nFreqs=S, collapse_freqs=True) if cart else dict(d_out=S)
+            E = FSW_embedding(d_in=d, enable_bias=False, total_mass_pad_thresh=tau, learnable_slices=True, learnable_freqs=True,
+                              device=dev, dtype=dtype, **kw)
+            with torch.no_grad():
+                E.projVecs.copy_(t(V, dev, dtype))
+                E.freqs.copy_(t(freqs, dev, dtype))
+            X = t(Xn, dev, dtype).requires_grad_(True)
+            w = t(vals, dev, dtype).requires_grad_(True)
+            A = torch.sparse_coo_tensor(torch.from_numpy(idx).to(dev), w, (8, Xn.shape[0]), is_coalesced=True)
+            out = E(X, A, graph_mode=True)
+            assert tuple(out.shape) == (8, S * S if cart else S)
+            out = out[:, diag_cols] if cart else out
+            (out * t(R, dev, dtype)).sum().backward()
+            res.append([a.detach().cpu().numpy() for a in (out, X.grad, E.projVecs.grad, E.freqs.grad, w.grad)])
+        errs = [relerr(c, a) for a, c in zip(*res)]
+        print("diag vs cart %s unit=%s tau=%g: out %.3e gX %.3e gV %.3e gfreqs %.3e gW %.3e" % ((str(dtype), unit, tau) + tuple(errs)))
+        assert np.abs(res[0][0][0]).max() == 0.0 and np.abs(res[0][0][1:]).max() > 0.0      # the empty row; the others are not
+        assert errs[0] < ftol, (unit, tau, errs)
+        assert max(errs[1:]) < gtol, (unit, tau, errs)
+
+
 def test_float64_conv_replays_the_reference_test_script(dev):
     """The reference's own test_conv.py (:9-57): float64 FSW_conv with edge features, three MLP layers, homogeneous 'log'
     degree encoding with a learnable scale, self_loop_weight 0.2, final BatchNorm, eval mode.  Same state_dict, same inputs:
