@@ -75,7 +75,7 @@ __device__ __forceinline__ void unit_bwd_rows(int p, int pe, const int32_t* __re
     for (int u = 0; u < D; ++u)
 #pragma unroll
       for (int t = u + 1; t < D; ++t) {
-        const int before = key[t] < key[u];   // t sorts ahead of u only when strictly smaller (ties keep edge order)
+        const int before = key[t] < key[u];   // t sorts ahead of u only when strictly smaller (ties keep entry order: the project's rule)
         rank[u] += before;
         rank[t] += 1 - before;
       }

@@ -4,7 +4,7 @@
 //   gkey[e, s]  = out_scale sum_f g[r, s F + f] C_f(rank_s(e))                          stored for every entry e of the graph
 //   gfreq[f]   += out_scale sum_{r, s} g[r, s F + f] sum_t dC_f(t)/dxi p_(t)
 // The degree classes are the forward's, on the same degree bins, so that the two stay in step; every line is sorted ONCE with its
-// entry indices (equal keys keep entry order, as in the generic kernel and the reference) and read out at all F frequencies:
+// entry indices (equal keys keep entry order, as in the generic kernel: the project's rule) and read out at all F frequencies:
 //   1 <= D <= 32     one lane per (row, slice).  Unit weights with tau <= 1: the coefficient rows of fsw_unit_coeff_table and
 //                    fsw_unit_dcoeff_table are wave-uniform and come through the constant address space, kFC frequencies per step;
 //                    the lanes' kFC frequency partials are summed across the wavefront by a transposing butterfly (kFC + 2 lane

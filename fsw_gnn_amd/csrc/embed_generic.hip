@@ -10,7 +10,7 @@
 //                ag.cumsum_sparse.backward :2160 = reverse segmented cumsum, ag.permute_sparse.backward :1286).
 // One workgroup per recipient row, looping over the slices.  Per (row, slice): (key, element index) pairs -- the reference's
 // pad element x = 0 (fsw_embedding.py:787-821) is element D -- sorted by a bitonic network in LDS (up to 2048 elements) or in
-// the workgroup's global scratch (any degree), ties by element index (= the reference's stable order); cumulative weights by a
+// the workgroup's global scratch (any degree), ties by element index (the project's rule, DESIGN.md "equal keys"; the reference's order there is unspecified); cumulative weights by a
 // workgroup scan (the segmented cumsum of fsw_embedding.py:1031-1032); readout
 //   Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t))      (fsw_embedding.py:1047-1075, the product form: no cancellation)
 //   out     = (1 + xi) sum_t Delta_t p_(t)                      (fsw_embedding.py:1084-1109).

@@ -1,8 +1,8 @@
 // Backward of the neighbourhood embedding for rows of FSW_REG_MAX_DEG < in-degree <= 128, one lane per slice.  gfx950.
 //
 // Mirror of embed_mid.hip: one wavefront per recipient row and 64-slice chunk, the whole neighbourhood in the lane's
-// registers, here as (key, element index) pairs sorted by the network of the bin's padded size (equal keys by index = the
-// reference's stable order).  The lane then walks its ranks -- unit weights: sin and cos of the rank angle by a float64
+// registers, here as (key, element index) pairs sorted by the network of the bin's padded size (equal keys by index: this
+// project's rule -- the reference leaves their order unspecified, DESIGN.md "equal keys").  The lane then walks its ranks -- unit weights: sin and cos of the rank angle by a float64
 // rotation; general weights: cumulative weight in float64 + sincospi -- and drops g * [F(c_r) - F(c_r - w_r)] into the
 // element's ORIGINAL position of a wave-private LDS tile [element][lane] (bank = lane: conflict-free although every lane
 // scatters to its own permutation).  Then one wave-wide float atomic on 256 contiguous bytes of gXp[col_t] per neighbour

@@ -39,7 +39,7 @@ __device__ __forceinline__ float minmax_by_limit(float a, float b, float lim) { 
 
 // keys (and weights) of one line across the wave, blocked layout; ascending over element index l*M + j afterwards
 // TIEBREAK: the payload is the element index and equal keys are ordered by it (= a stable sort by key, the order the
-// reference's sort and the oracle produce; the backward kernels need it to hand tied neighbours the same coefficients)
+// oracle states; the reference's own order among equal keys is unspecified.  Every backward kernel uses this one order)
 // LL: lanes per line (64: one line across the wavefront; 16: four independent lines, one per DPP row -- every exchange of its
 // merge levels is then a single DPP move)
 template <int M, bool WEIGHTED, bool TIEBREAK = false, int LL = kWave>
@@ -165,8 +165,8 @@ struct WaveLine {
 };
 
 // The same line layout and merge structure for 64-bit words (pack_key_index: key, then element index): the backward
-// kernels sort these -- one unsigned 64-bit compare per pair orders by key with ties by index (= the reference's stable
-// order), and the element index comes back out of the low word.
+// kernels sort these -- one unsigned 64-bit compare per pair orders by key with ties by index (the project's
+// rule for equal keys), and the element index comes back out of the low word.
 template <int M>
 struct WaveLine64 {
   unsigned long long e[M];

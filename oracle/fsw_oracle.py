@@ -264,7 +264,7 @@ def _dsinc(z):
 
 
 def fsw_embed_csr_backward(X, rowptr, col, w, projVecs, freqs, G, total_mass_pad_thresh=1.0, chunk_elems=1 << 22,
-                           return_gXp=False, Xp_override=None, edge_feat=None, keys_override=None):
+                           return_gXp=False, Xp_override=None, edge_feat=None, keys_override=None, return_gkey=False):
     """Gradients of sum(out * G) for out = fsw_embed_csr(...) with respect to X, projVecs and freqs (float64).
 
     The reference obtains them by reverse-mode autograd through its sparse ops: sum_sparseToDense.backward,
@@ -278,6 +278,12 @@ def fsw_embed_csr_backward(X, rowptr, col, w, projVecs, freqs, G, total_mass_pad
     Xp_override: use these projections (e.g. the float32 ones of the path under test) to decide the sort order;
     two neighbours whose projections agree to float32 rounding may otherwise swap ranks between float32 and
     float64, which moves g (C[s] - C[s+1]) between two entries of gXp (the gradient is discontinuous there).
+    Equal keys are ranked by their position in the row (a stable sort; the pad element is the row's last position).  The
+    reference leaves the order among equal keys to an unstable torch.sort: its output, gfreqs and the sum of the key gradients
+    over every group of equal keys do not depend on that order, the gradient of a single tied key does -- entry order is this
+    project's rule, which this function states.
+    return_gkey: the gradient of every key, gkey [nnz, S] in CSR entry order, is appended to the result (with edge_feat it is what
+    g_edge_feat and the edge part of gV are formed from).
     """
     X = np.asarray(X, dtype=np.float64)
     V = np.asarray(projVecs, dtype=np.float64)
@@ -285,7 +291,6 @@ def fsw_embed_csr_backward(X, rowptr, col, w, projVecs, freqs, G, total_mass_pad
     if edge_feat is not None:      # edge features: returns (gX, gV [S, d_in + d_edge], gxi, g_edge_feat [nnz, d_edge])
         edge_feat = np.asarray(edge_feat, dtype=np.float64)
         Ve, V = V[:, X.shape[1]:], V[:, :X.shape[1]]
-        gkey_all = np.zeros((edge_feat.shape[0], V.shape[0]))
     xi = np.asarray(freqs, dtype=np.float64)
     G = np.asarray(G, dtype=np.float64)
     rowptr = np.asarray(rowptr, dtype=np.int64)
@@ -294,6 +299,8 @@ def fsw_embed_csr_backward(X, rowptr, col, w, projVecs, freqs, G, total_mass_pad
     tau = float(total_mass_pad_thresh)
     nrows = rowptr.shape[0] - 1
     S = V.shape[0]
+    if Ve is not None or return_gkey:
+        gkey_all = np.zeros((col.shape[0], S))
     deg = np.diff(rowptr)
     mass = np.zeros(nrows)
     np.add.at(mass, np.repeat(np.arange(nrows), deg), w)
@@ -341,11 +348,13 @@ def fsw_embed_csr_backward(X, rowptr, col, w, projVecs, freqs, G, total_mass_pad
             np.add.at(gXp, col[idx], gk[:, :D, :])                             # the pad element has no source row
             if gkey_all is not None:
                 gkey_all[idx] = gk[:, :D, :]
-    if gkey_all is not None:
-        return gXp @ V, np.concatenate([gXp.T @ X, gkey_all.T @ edge_feat], axis=1), gxi, gkey_all @ Ve
-    if return_gXp:
-        return gXp @ V, gXp.T @ X, gxi, gXp
-    return gXp @ V, gXp.T @ X, gxi
+    if Ve is not None:
+        res = (gXp @ V, np.concatenate([gXp.T @ X, gkey_all.T @ edge_feat], axis=1), gxi, gkey_all @ Ve)
+    elif return_gXp:
+        res = (gXp @ V, gXp.T @ X, gxi, gXp)
+    else:
+        res = (gXp @ V, gXp.T @ X, gxi)
+    return res + (gkey_all,) if return_gkey else res
 
 
 def mass_value(mass, function="identity"):

@@ -299,6 +299,63 @@ def case_grads_w(emb, conv):
     save("grads_w", **arrays)
 
 
+def ties_inputs():
+    """Inputs of case_ties: one recipient per degree (an empty row among them), one sender per entry, features drawn from five
+    values of which two are the two zeros, so that every slice of every row holds groups of equal keys."""
+    degs = np.array([1, 2, 5, 16, 0, 21, 33, 70, 130], dtype=np.int64)
+    n, S = int(degs.sum()), 4
+    vals = np.array([-1.0, -0.0, 0.0, 0.5, 2.0])
+    X = vals[synth.randint(111, 1, len(vals), n * S)].reshape(n, S)
+    rec = np.repeat(np.arange(degs.size), degs)
+    w = np.array([0.25, 0.5, 1.0])[synth.randint(112, 1, 3, n)]
+    w[np.nonzero(rec == 6)[0][4]] = 0.0                              # one zero weight (the row of 33)
+    for r, mass in ((3, 0.4), (7, 0.9)):                             # rows of 16 and 70: the pad element carries 0.6 and 0.1
+        w[rec == r] *= mass / w[rec == r].sum()
+    return dict(degrees=degs, X=X, w_general=w, V=np.eye(S), freqs=np.array([0.0, 0.37, 1.5, 7.25]),
+                R=synth.normal(113, 1, (degs.size, S), dtype=np.float64))
+
+
+def tie_group_sums(values, keys, rowptr):
+    """out[e, s] = sum of values[e', s] over the entries e' of e's row with keys[e', s] == keys[e, s] (-0.0 == 0.0): what every
+    order among equal keys agrees on."""
+    out = np.zeros_like(values)
+    for a, b in zip(rowptr[:-1], rowptr[1:]):
+        for s in range(values.shape[1]):
+            k = keys[a:b, s]
+            out[a:b, s] = ((k[:, None] == k[None, :]) * values[a:b, s][None, :]).sum(axis=1)
+    return out
+
+
+def case_ties(emb):
+    """Equal keys (tests/test_oracle_vs_golden.py::test_tied_keys_contract): the reference's float64 autograd on the tied input of
+    ties_inputs(), unit and general weights.  The reference sorts with an unstable torch.sort, so under ties its per-entry gX is one
+    of several valid answers -- on this input it differs from entry order already in the row of 5 neighbours -- and no per-entry
+    gX is stored.  Stored is what does not depend on the order: out, gfreqs and the sums of gX over every group of equal keys.
+    One group is left out (tie_sums_valid_general is False there): the zero keys of a row whose total mass is below the pad
+    threshold.  The pad element (key 0, no gradient entry of its own) belongs to that group, and the share of the group's sum
+    that falls to the pad depends on its place among the zeros."""
+    c = ties_inputs()
+    degs, X0, V, fr, R = c["degrees"], c["X"], c["V"], c["freqs"], c["R"]
+    n, S, nrows = X0.shape[0], X0.shape[1], degs.size
+    rowptr = np.concatenate([[0], np.cumsum(degs)])
+    rec = np.repeat(np.arange(nrows), degs)
+    dt = torch.float64
+    mass = np.bincount(rec, weights=c["w_general"], minlength=nrows)
+    arrays = dict(c, tie_sums_valid_general=~((mass[rec] < 1.0)[:, None] & (X0 == 0.0)))
+    for tag, w in (("unit", np.ones(n)), ("general", c["w_general"])):
+        A = torch.sparse_coo_tensor(torch.from_numpy(np.stack([rec, np.arange(n)])), torch.from_numpy(w), (nrows, n)).coalesce()
+        Em = emb.FSW_embedding(d_in=S, d_out=S, learnable_slices=True, learnable_freqs=True, device="cpu", dtype=dt,
+                               load_custom_cuda_lib=False, enable_bias=False)
+        set_params(Em, V, fr)
+        X = T(X0, dt).requires_grad_(True)
+        out = Em(X, A, graph_mode=True)
+        (out * torch.from_numpy(R)).sum().backward()
+        gX = X.grad.numpy()
+        arrays.update({"out_" + tag: out.detach().numpy(), "gfreqs_" + tag: Em.freqs.grad.numpy(),
+                       "tie_sums_" + tag: tie_group_sums(gX, X0, rowptr)})
+    save("ties", **arrays)
+
+
 def case_testconv64(emb, conv):
     """The configuration of the reference's own test_conv.py (:9-57) on deterministic inputs: float64, 100 vertices, 50 vertex /
     11 edge features, 35 outputs, three MLP layers, homogeneous degree encoding with the 'log' function and a learnable scale,
@@ -430,12 +487,14 @@ def main():
         case_edgefeat(emb, conv)
     elif what == "grads_w":
         case_grads_w(emb, conv)
+    elif what == "ties":
+        case_ties(emb)
     elif what == "testconv64":
         case_testconv64(emb, conv)
     elif what == "er1m":
         timings.update(case_er1m(emb, conv))
     else:
-        raise SystemExit("usage: python -m oracle.make_goldens [small|grads|grads_homog|coherence|edgefeat|grads_w|testconv64|er1m]")
+        raise SystemExit("usage: python -m oracle.make_goldens [small|grads|grads_homog|coherence|edgefeat|grads_w|ties|testconv64|er1m]")
     json.dump(timings, open(timings_path, "w"), indent=1, sort_keys=True)
 
 
