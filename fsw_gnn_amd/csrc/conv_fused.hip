@@ -27,6 +27,7 @@
 #include "fsw_common.h"
 #include "sortnet.h"
 #include "row_pipeline.h"
+#include "embed_cart.h"
 #ifndef FSW_FUSED_PIPE_BARRIER
 #define FSW_FUSED_PIPE_BARRIER 0   // measured: tools/exp_variants.sh
 #endif
@@ -176,6 +177,19 @@ __device__ __forceinline__ void slab_mma(const FusedArgs& a, const float* __rest
     if (g0 + u < ngroups) mma4(hp + 8 * (g0 + u), bq[u]);
 }
 
+// What a tile starts with, whatever fills its embedding columns: zero the K padding column(s) and the unused rows of H, record the
+// node ids, write the mass column.  K = has_mass + a.S.
+template <int TR>
+__device__ __forceinline__ void fused_tile_init(const FusedArgs& a, int D, int p, int nrows, int K, float* H, int* nodeS) {
+  if (threadIdx.x < TR) {
+    const int r = threadIdx.x;
+    for (int c = (r < nrows ? K : 0); c < a.ldh; ++c) H[r * a.ldh + c] = 0.f;
+    nodeS[r] = r < nrows ? a.perm[p + r] : -1;
+    if (a.has_mass && r < nrows)
+      H[r * a.ldh] = mass_column((float)D, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
+  }
+}
+
 // TR = rows of a workgroup's tile.  32: the output staging tile reuses H's LDS.  128 (narrow slice blocks, Hout <= 128): four
 // 32-row sub-tiles go through the matrix phase one after the other with a staging tile of their own -- a workgroup's start-up chain
 // (tile search, perm -> rowptr -> col -> first gather: three dependent round trips, ~5 us) is paid once per 128 rows instead of once
@@ -199,14 +213,7 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) k_conv_fused_unit(const F
   const int K = a.has_mass + a.S;  // embedding width = K of the fused product
   const int fr = lane & 31, fh = lane >> 5;
 
-  // zero the K padding column(s) and the unused rows of H, record node ids, mass column
-  if (threadIdx.x < TR) {
-    const int r = threadIdx.x;
-    for (int c = (r < nrows ? K : 0); c < a.ldh; ++c) H[r * a.ldh + c] = 0.f;
-    nodeS[r] = r < nrows ? a.perm[p + r] : -1;
-    if (a.has_mass && r < nrows)
-      H[r * a.ldh] = mass_column((float)D, a.mass_fn, a.mass_scale, a.bias, a.out_scale);
-  }
+  fused_tile_init<TR>(a, D, p, nrows, K, H, nodeS);
   FSW_FSTAMP(0);                                           // tile found, H padding / node ids / mass column
   // phase 1: embedding rows
   // a wave = one 64-slice chunk of a group of rows.  Four or more chunks: every wave walks all 32 rows of its chunks.
@@ -231,93 +238,88 @@ __global__ void __launch_bounds__(256, WAVES_PER_SIMD) k_conv_fused_unit(const F
     }
   }
   FSW_FSTAMP(1);                                           // phase 1: this wavefront's rows gathered, sorted, read out into H
-  const int nslabs = (a.Hout + 31) / 32;
-  if (nslabs <= 4) {
-    // ---- Hout <= 128: one slab per wave, output tile staged through LDS so that Y is written as whole rows ----
-    // Rows of Yin (= x . W2^T + b, stored by the projection kernel in perm order: this workgroup's 32 rows are one
-    // contiguous run).  Wave w finishes rows 8w..8w+7; lane owns columns lane and lane+64.  Issued after phase 1
-    // (registers are free again) and before the barrier: in flight while the other waves finish their rows.
-    // Branch-free (rows past the tile's end re-read its last row, columns past Hout the last column; neither is used): with a
-    // branch per load every load sat in its own basic block and waited for the one before it (s_waitcnt vmcnt(0) per block) --
-    // 10 us of a workgroup's 91 (tools/exp_fused_stamps.py)
-    float lb[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) lb[h] = (!a.Yin && a.lin_bias && lane + 64 * h < a.Hout) ? a.lin_bias[lane + 64 * h] : 0.f;
-    // TR == 32: the staging tile reuses H; TR == 128: its own LDS behind the node ids (four sub-tiles read H one after the other)
-    float* T = TR == kFusedRows ? smem : reinterpret_cast<float*>(nodeS + TR);   // [32][kLdT]
-#pragma unroll 1
-    for (int r0 = 0; r0 < TR; r0 += kFusedRows) {
-      if (TR > kFusedRows && r0 >= nrows) break;           // uniform
-      const int nsub = min(nrows - r0, kFusedRows);
-      float yin[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) yin[q] = 0.f;
-      if ((ABL & 2) == 0 && a.Yin) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int row = r0 + min(wv * 8 + (q >> 1), nsub - 1), c = min(lane + 64 * (q & 1), a.Hout - 1);
-          yin[q] = a.Yin[(int64_t)(a.yin_by_node ? a.perm[p + row] : p + row) * a.ldyin + c];
-        }
-      }
-      FSW_FSTAMP(2);                                       // Yin loads issued
-      __syncthreads();                       // first sub-tile: phase 1 complete; later ones: the previous epilogue has read T
-      FSW_FSTAMP(3);                                       // barrier: waited for the slowest wavefront's phase 1
-      f32x16 acc;
-      if (wv < nslabs) slab_mma<ABL>(a, H + r0 * a.ldh, wv, fr, fh, acc);
-      FSW_FSTAMP(4);                                       // matrix phase
-      if (TR == kFusedRows) __syncthreads(); // every wave has finished reading H: reuse it for the output tile
-      if (wv < nslabs) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * fh) * kLdT + wv * 32 + fr] = acc[r];
-      }
-      __syncthreads();
-      FSW_FSTAMP(5);                                       // barrier, accumulators into the staging tile, barrier
-#pragma unroll
-      for (int rr = 0; rr < 8; ++rr) {
-        const int row = wv * 8 + rr;
-        const int node = row < nsub ? nodeS[r0 + row] : -1;
-        if (node < 0) continue;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int c = lane + 64 * h;
-          if (c < a.Hout) {
-            float y = T[row * kLdT + c] + lb[h] + yin[rr * 2 + h];
-            if (a.act == 1) y = fmaxf(y, 0.f);
-            else if (a.act == 2) y = y >= 0.f ? y : a.slope * y;
-            if ((ABL & 4) == 0 || y == 12345.f) a.Y[(int64_t)node * a.ldy + c] = y;
-          }
-        }
-      }
-    }
-    FSW_FSTAMP(6);                                         // epilogue: + Yin, activation, Y rows stored
-    return;
-  }
+#include "conv_fused_tail.inc"
+}
 
-  // ---- wide layers (Hout > 128): slabs round-robin over the waves, every wave stores its own 32 x 32 tiles ----
-  __syncthreads();
-  for (int slab = wv; slab < nslabs; slab += 4) {
-    const int j = slab * 32 + fr;
-    float yin[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * fh;     // C/D map of the 32x32 MFMA
-      yin[r] = (a.Yin && row < nrows && j < a.Hout) ? a.Yin[(int64_t)(a.yin_by_node ? a.perm[p + row] : p + row) * a.ldyin + j] : 0.f;
+// ---- Cartesian layers: FSW_embedding(nSlices = S, nFreqs = F) in front of the same first Linear layer --------------------------
+// The embedding row of a node is [mass | S runs of F outputs], K = has_mass + S F wide; a slice is gathered and sorted ONCE and
+// read out at all F frequencies (embed_cart.hip), so phase 1 costs S lines per row where the diagonal kernel above costs K.
+// f.S holds S F (the width of the embedding block: K, the padding and phases 2 / 3 follow from it), f.table / f.ldt are unused.
+struct FusedCartArgs {
+  FusedArgs f;
+  int slices, F;
+  const float* ctable;   // fsw_unit_coeff_table of the F frequencies: [D (D - 1) / 2 + t][f]
+  int64_t ldct;
+};
+
+// phase 1 for the rows perm[p .. p + nrows) of in-degree D: the body of cart_reg_unit (embed_cart.hip) with LDS as the destination.
+// One lane per (row, slice) item, adjacent lanes on adjacent slices of one row: a neighbour's keys Xp[col, s .. s + 15] are one
+// 64-byte run per 16 lanes, as in the unfused kernel, whose time is the time of these gathers.  The price is paid in LDS: the lanes
+// of a row store F floats apart (banks of a store: address mod 32), 8- to 16-way conflicts at F = 16, i.e. about 2000 LDS cycles
+// for a 32 x 257 tile, against D gather instructions of 64 different cache lines each with lanes on adjacent ROWS (conflict-free
+// stores, ldh is odd, but 16 times the cache-line requests of the bound resource).  DESIGN.md "Cartesian layers" has the numbers.
+// Coefficients are wave-uniform and come through the constant address space (scalar loads), outputs are out_scale * (bias + sum).
+template <int D>
+__device__ __forceinline__ void fused_cart_rows(const FusedCartArgs& a, int p, int nrows, float* H) {
+  const FusedArgs& f_ = a.f;
+  const int F = a.F, ldh = f_.ldh;
+  if constexpr (D == 0) {      // the pad element alone embeds to 0: the bias is what is left
+    const int W = a.slices * F;
+    for (int i = threadIdx.x; i < nrows * W; i += blockDim.x) {
+      const int r = i / W, c = i - r * W;
+      H[r * ldh + f_.has_mass + c] = f_.bias ? f_.out_scale * f_.bias[f_.has_mass + c] : 0.f;
     }
-    f32x16 acc;
-    slab_mma<ABL>(a, H, slab, fr, fh, acc);
-    if (j < a.Hout) {
-      const float lb = (!a.Yin && a.lin_bias) ? a.lin_bias[j] : 0.f;
+  } else {
+    ConstAS<float>* tab = as_const(a.ctable + (int64_t)(D * (D - 1) / 2) * a.ldct);
+    const int items = nrows * a.slices;
+    for (int i = threadIdx.x; i < items; i += blockDim.x) {
+      const int r = i / a.slices, s = i - r * a.slices;
+      const int start = f_.rowptr[f_.perm[p + r]];
+      KeyNet<D> net;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int node = nodeS[(r & 3) + 8 * (r >> 2) + 4 * fh];
-        if (node >= 0) {
-          float y = acc[r] + lb + yin[r];
-          if (a.act == 1) y = fmaxf(y, 0.f);
-          else if (a.act == 2) y = y >= 0.f ? y : a.slope * y;
-          a.Y[(int64_t)node * a.ldy + j] = y;
-        }
+      for (int t = 0; t < D; ++t) net.k[t] = f_.Xp[(int64_t)f_.col[start + t] * f_.ldp + s];
+      sort_network<D>(net);
+      const int c0 = f_.has_mass + s * F;
+      float* h = H + r * ldh + c0;
+      for (int f = 0; f < F; ++f) {
+        float acc = f_.bias ? f_.bias[c0 + f] : 0.f;
+#pragma unroll
+        for (int t = 0; t < D; ++t) acc = fmaf(tab[(int64_t)t * a.ldct + f], net.k[t], acc);   // wave-uniform coefficient
+        h[f] = f_.out_scale * acc;
       }
     }
+  }
+}
+
+template <int WAVES_PER_SIMD>
+__global__ void __launch_bounds__(256, WAVES_PER_SIMD) k_conv_fused_cart(const FusedCartArgs ca) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* H = smem;                                                          // [32][ldh]
+  int* nodeS = reinterpret_cast<int*>(smem + ca.f.tile_floats);              // [32]
+  int D, p = 0, pe = 0;
+  if (!find_degree_tile<kFusedRows>(ca.f.bin_start, 0, FSW_REG_MAX_DEG, (int)blockIdx.x, D, p, pe)) return;
+  const int nrows = pe - p;
+  const int wv = wave_id();
+  const int lane = lane_id();
+  fused_tile_init<kFusedRows>(ca.f, D, p, nrows, ca.f.has_mass + ca.f.S, H, nodeS);
+  switch (D) {
+#define X(d)                           \
+  case d:                              \
+    fused_cart_rows<d>(ca, p, nrows, H); \
+    break;
+    FSW_CASES_0_32(X)
+#undef X
+    default:
+      break;
+  }
+#if FSW_FUSED_STAMPS
+  unsigned long long fst_last = clock64();
+#endif
+  {   // phases 2 and 3: the text k_conv_fused_unit runs, on the FusedArgs inside FusedCartArgs
+    const FusedArgs& a = ca.f;
+    constexpr int ABL = 0, TR = kFusedRows;
+    const int fr = lane & 31, fh = lane >> 5;
+#include "conv_fused_tail.inc"
   }
 }
 
@@ -465,6 +467,57 @@ extern "C" int fsw_conv_fused_f32(const fsw_embed_args* args, const float* Wq, i
     k_conv_fused_unit<0, FSW_REG_MAX_DEG, FSW_FUSED_NARROW_WAVES, 0, 2><<<(unsigned)nblocks, 256, lds, stream>>>(a);
   else
     k_conv_fused_unit<0, FSW_REG_MAX_DEG, 4><<<(unsigned)nblocks, 256, lds, stream>>>(a);
+  FSW_LAUNCH_CHECK();
+  return 0;
+}
+
+static size_t fused_tile_bytes(int K) {   // H [32][ldh] (also the staging tile [32][kLdT]) | node ids [32]
+  const int ldh = ((K + 7) & ~7) | 1;
+  return (size_t)kFusedRows * (ldh > kLdT ? ldh : kLdT) * sizeof(float) + kFusedRows * sizeof(int);
+}
+
+extern "C" size_t fsw_conv_fused_cart_lds_bytes(int S, int F, int has_mass) {
+  const int64_t K = (int64_t)has_mass + (int64_t)S * F;
+  return K > (1 << 20) ? (size_t)-1 : fused_tile_bytes((int)K);
+}
+
+extern "C" int fsw_conv_fused_cart_f32(const fsw_cart_args* c, const float* Wq, int64_t ldw, const float* lin_bias, int Hout,
+                                       const float* Yin, int64_t ldyin, int yin_by_node, int act, float slope, float* Y, int64_t ldy,
+                                       fsw_stream_t stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  int rc;
+  if ((rc = cart_check_common(c))) return rc;
+  FSW_REQUIRE(Wq && Y, "fsw_conv_fused_cart_f32: null pointer");
+  FSW_REQUIRE(c->value_dtype == 0 && !c->g, "fsw_conv_fused_cart_f32: float32 forward only");
+  FSW_REQUIRE(c->perm && c->bin_start && c->bin_start_host, "fsw_conv_fused_cart_f32: needs perm, bin_start and its host copy");
+  FSW_REQUIRE(c->w == nullptr && c->tau <= 1.0, "fsw_conv_fused_cart_f32: unit weights with tau <= 1 only");
+  FSW_REQUIRE(c->unit_table && c->ldt >= c->F, "fsw_conv_fused_cart_f32: needs the unit coefficient table of the F frequencies");
+  FSW_REQUIRE(!Yin || ldyin >= Hout, "fsw_conv_fused_cart_f32: bad Yin stride");
+  FSW_REQUIRE(Hout >= 1 && ldy >= Hout && ldw >= ((Hout + 31) / 32) * 32 && ldw % 32 == 0, "fsw_conv_fused_cart_f32: bad output sizes");
+  FSW_REQUIRE(((uintptr_t)Wq & 15) == 0, "fsw_conv_fused_cart_f32: Wq must be 16-byte aligned");
+  FSW_REQUIRE(act >= 0 && act <= 2, "fsw_conv_fused_cart_f32: act must be 0 (none), 1 (relu) or 2 (leaky relu)");
+  const size_t lds = fsw_conv_fused_cart_lds_bytes(c->S, c->F, c->has_mass);
+  FSW_REQUIRE(lds <= 64 * 1024, "fsw_conv_fused_cart_f32: S * F too wide for the fused tile (%zu B of LDS)", lds);
+  const int32_t* bs = c->bin_start_host;
+  // every row is finished here or not at all: the caller sends graphs with longer rows to fsw_embed_cart_f32 (fsw_conv.py)
+  FSW_REQUIRE(bs[FSW_NUM_BINS] == bs[FSW_BIN_MID0], "fsw_conv_fused_cart_f32: rows of at most %d neighbours only", FSW_REG_MAX_DEG);
+  FSW_REQUIRE(bs[FSW_BIN_MID0] - bs[0] == c->num_rows, "fsw_conv_fused_cart_f32: bin table does not cover num_rows");
+  int64_t tiles = 0;
+  for (int d = 0; d <= FSW_REG_MAX_DEG; ++d) tiles += ceil_div(bs[d + 1] - bs[d], kFusedRows);
+  if (tiles == 0) return 0;
+  FusedCartArgs a;
+  FusedArgs& f = a.f;
+  f.rowptr = c->rowptr; f.col = c->col; f.perm = c->perm; f.bin_start = c->bin_start;
+  f.Xp = (const float*)c->Xp; f.ldp = c->ldp; f.S = c->S * c->F; f.table = nullptr; f.ldt = 0;
+  f.bias = (const float*)c->bias; f.out_scale = (float)c->out_scale; f.has_mass = c->has_mass; f.mass_fn = c->mass_fn;
+  f.mass_scale = (float)c->mass_scale;
+  f.Wq = Wq; f.ldw = ldw; f.lin_bias = lin_bias; f.Yin = Yin; f.ldyin = ldyin; f.yin_by_node = yin_by_node ? 1 : 0; f.Hout = Hout;
+  f.act = act; f.slope = slope; f.Y = Y; f.ldy = ldy;
+  f.Kp = (c->has_mass + f.S + 7) & ~7;
+  f.ldh = f.Kp | 1;
+  f.tile_floats = kFusedRows * (f.ldh > kLdT ? f.ldh : kLdT);
+  a.slices = c->S; a.F = c->F; a.ctable = c->unit_table; a.ldct = c->ldt;
+  k_conv_fused_cart<4><<<(unsigned)tiles, 256, lds, stream>>>(a);
   FSW_LAUNCH_CHECK();
   return 0;
 }

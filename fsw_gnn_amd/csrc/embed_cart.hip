@@ -54,8 +54,8 @@ struct CartTuned {
   float mass_scale;
 };
 
-// VEC: four frequencies per step -- 16-byte coefficient loads (wave-uniform) and 16-byte output stores (F % 4 == 0, no mass column
-// in front of the run, 16-byte aligned rows: launch condition on the host)
+// VEC: four frequencies per step -- 16-byte coefficient loads (wave-uniform) and 16-byte output stores (F % 4 == 0, column has_mass of
+// every row 16-byte aligned: launch condition on the host)
 template <int D, bool VEC>
 __device__ __forceinline__ void cart_reg_unit(const CartTuned& a, int p, int pe) {
   const int items = (pe - p) * a.S;
@@ -341,8 +341,9 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   int64_t tiles = 0;
   for (int d = 1; d <= FSW_REG_MAX_DEG; ++d) tiles += ceil_div(bs[d + 1] - bs[d], kCartRows);
   if (tiles > 0) {
-    const bool vec = c->F % 4 == 0 && c->ldt % 4 == 0 && c->has_mass == 0 && c->ldo % 4 == 0 && (uintptr_t)c->out % 16 == 0 &&
-                     (uintptr_t)c->unit_table % 16 == 0 && (!c->bias || (uintptr_t)c->bias % 16 == 0);
+    // 16-byte stores and bias loads start at column has_mass of a row: what has to be aligned is that address, not the row's
+    const bool vec = c->F % 4 == 0 && c->ldt % 4 == 0 && c->ldo % 4 == 0 && (uintptr_t)((const float*)c->out + c->has_mass) % 16 == 0 &&
+                     (uintptr_t)c->unit_table % 16 == 0 && (!c->bias || (uintptr_t)((const float*)c->bias + c->has_mass) % 16 == 0);
     if (unit_fast && vec) k_cart_reg<true, true><<<(unsigned)tiles, 256, 0, stream>>>(t);
     else if (unit_fast) k_cart_reg<true, false><<<(unsigned)tiles, 256, 0, stream>>>(t);
     else k_cart_reg<false, false><<<(unsigned)tiles, 256, 0, stream>>>(t);

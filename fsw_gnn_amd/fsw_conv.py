@@ -55,7 +55,7 @@ class FSW_conv(_Base):
                  dropout_final=0, dropout_hidden=0,
                  self_loop_weight=0, edge_weighting='unit',
                  device=None, dtype=torch.float32,
-                 config=None):
+                 config=None, embed_slices=None, embed_freqs=None):
         if _HAVE_PYG:
             super().__init__(aggr=None)
         else:
@@ -76,7 +76,20 @@ class FSW_conv(_Base):
                     learnable_vertex_degree_encoding_scale, homog_degree_encoding, vertex_degree_pad_thresh,
                     concat_self, message_weight_vs_self, bias, mlp_layers, mlp_hidden_dim, mlp_activation_final,
                     mlp_activation_hidden, mlp_init, batchNorm_final, batchNorm_hidden, dropout_final, dropout_hidden,
-                    self_loop_weight, edge_weighting, device, dtype):
+                    self_loop_weight, edge_weighting, device, dtype, embed_slices=None, embed_freqs=None):
+        # Cartesian embedding (an extension beyond the reference): embed_slices slices, each read out at embed_freqs
+        # frequencies -- FSW_embedding(nSlices, nFreqs, collapse_freqs=True) instead of embed_dim (slice, frequency) pairs
+        cartesian = embed_slices is not None or embed_freqs is not None
+        if cartesian:
+            assert embed_slices is not None and embed_freqs is not None, 'embed_slices and embed_freqs must be given together'
+            assert int(embed_slices) >= 1 and int(embed_freqs) >= 1, 'embed_slices and embed_freqs must be positive'
+            embed_slices, embed_freqs = int(embed_slices), int(embed_freqs)
+            cart_dim = embed_slices * embed_freqs + (1 if encode_vertex_degrees else 0)
+            assert embed_dim is None or embed_dim == cart_dim, \
+                'embed_dim must be None or embed_slices * embed_freqs (+ 1 with encode_vertex_degrees) = %d' % cart_dim
+            assert not (mlp_layers == 0 and concat_self is False) or cart_dim == out_channels, \
+                'mlp_layers=0 without concat_self returns the embedding itself: out_channels must equal %d' % cart_dim
+            embed_dim = cart_dim
         assert edge_weighting in {'unit', 'gcn'}, 'invalid value passed in argument <edge_weighting>'
         assert vertex_degree_encoding_function in {'identity', 'sqrt', 'log'}, \
             'invalid value passed in argument <vertex_degree_encoding_function>'
@@ -135,7 +148,8 @@ class FSW_conv(_Base):
         # defined by the reference and never used in its forward (fsw_conv.py:312); kept for state_dict parity
         self.size_coeff = torch.nn.Parameter(torch.ones(1, device=device, dtype=dtype) / np.sqrt(embed_dim),
                                              requires_grad=learnable_embedding)
-        self.fsw_embed = FSW_embedding(d_in=in_channels, d_out=embed_dim, d_edge=edgefeat_dim,
+        size = dict(nSlices=embed_slices, nFreqs=embed_freqs, collapse_freqs=True) if cartesian else dict(d_out=embed_dim)
+        self.fsw_embed = FSW_embedding(d_in=in_channels, d_edge=edgefeat_dim, **size,
                                        learnable_slices=learnable_embedding, learnable_freqs=learnable_embedding,
                                        learnable_total_mass_encoding_scale=learnable_vertex_degree_encoding_scale,
                                        encode_total_mass=encode_vertex_degrees,
@@ -184,7 +198,8 @@ class FSW_conv(_Base):
     def _build_graph_uncached(self, edge_index, num_vertices, chunk_rows):
         """build_graph without edge features: a fresh CSR."""
         src, dst, w, _ = self._weighted_edges(edge_index, num_vertices)
-        return build_csr(dst, src, w, num_vertices, num_vertices, want_invperm=self._fusable(), chunk_rows=chunk_rows,
+        return build_csr(dst, src, w, num_vertices, num_vertices, want_invperm=self._fusable() and not self.fsw_embed.cartesian_mode,
+                         chunk_rows=chunk_rows,
                          hint=self._build_hint())
 
     def _weighted_edges(self, edge_index, num_vertices, ef=None):
@@ -248,6 +263,8 @@ class FSW_conv(_Base):
         sp = getattr(self, '_slice_parallel', None)
         if sp is not None:
             return self._forward_slice_parallel(sp, x, vertex_features, edge_index, edge_features, needs_grad)
+        if emb_mod.cartesian_mode:
+            return self._forward_cartesian(x, vertex_features, edge_index, needs_grad)
         graph = self.build_graph(edge_index, n, edge_features if self.edgefeat_dim > 0 else None)
         E = self.embed_dim
         scale = self._message_scale
@@ -300,6 +317,72 @@ class FSW_conv(_Base):
         else:
             emb_mod.embed_into(x, graph, buf, out_scale=scale, x_copy=xc)   # X stored by the projection kernel
         return self._tail_buffer(buf)
+
+    def _forward_cartesian(self, x, vertex_features, edge_index, needs_grad):
+        """float32 layer with a Cartesian embedding (embed_slices x embed_freqs): training through _CartEmbedFn and the usual tail;
+        inference through ONE kernel for the embedding and the first Linear layer (csrc/conv_fused.hip: k_conv_fused_cart) when the
+        configuration is fusable and no row has more than REG_MAX_DEG neighbours, else embed_cartesian_into + the torch tail.
+        Finishing only the long rows next to the fused kernel (_finish_long_rows) is not done here: DESIGN.md."""
+        emb_mod = self.fsw_embed
+        n = x.shape[0]
+        graph = self.build_graph(edge_index, n)
+        if needs_grad:
+            return self._tail(emb_mod.embed_cartesian_autograd(x, graph), vertex_features)
+        scale = self._message_scale
+        prepared = emb_mod.prepare_cartesian(x, graph)
+        bsh = graph.bin_start_host[0]
+        if self._fusable() and int(bsh[_lib.NUM_BINS]) == int(bsh[_lib.BIN_MID0]):     # no row above REG_MAX_DEG
+            lin = self.mlp[0]
+            wq, _ = self._fused_weight(want_w2=False)
+            yin = None
+            if self.concat_self:      # x . W2^T + b in node order, read by node id
+                w2 = lin.weight.detach()[:, self.embed_dim:]
+                yin = torch.addmm(lin.bias.detach(), x, w2.t()) if lin.bias is not None else x @ w2.t()
+            y = torch.empty((n, lin.out_features), dtype=x.dtype, device=x.device)
+            return self._mlp_from(y, self._fused_cart_linear(graph, prepared, scale, wq, yin, y))
+        if self._split_first_linear():
+            return self._tail_split(self._cart_embed_buffer(x, graph, prepared, 0, scale), x)
+        buf = self._cart_embed_buffer(x, graph, prepared, self.in_channels if self.concat_self else 0, scale)
+        if self.concat_self:
+            buf[:, self.embed_dim:].copy_(x)
+        return self._tail_buffer(buf)
+
+    def _cart_embed_buffer(self, x, graph, prepared, extra_cols, scale):
+        """[num_rows, embed_dim + extra_cols] view whose left embed_dim columns hold scale * E(x, graph) (inference, float32).  The
+        view starts 3 floats into the rows of a 16-byte aligned buffer when the layer has the mass column, so that the S F block
+        behind it is 16-byte aligned and the register-path kernel takes its 16-byte stores; the tail never reads the pad floats."""
+        emb_mod = self.fsw_embed
+        has_mass, E = emb_mod.total_mass_encoding_dim, self.embed_dim
+        pad = (-has_mass) % 4
+        ld = (pad + E + extra_cols + 3) // 4 * 4
+        buf = torch.empty((graph.num_rows, ld), dtype=x.dtype, device=x.device)[:, pad:pad + E + extra_cols]
+        bias = None
+        if emb_mod.enable_bias:
+            bias = torch.cat([emb_mod.bias.new_zeros(pad), emb_mod.bias.detach().reshape(-1)])[pad:]      # aligned like the rows
+        plain = emb_mod.plain_mass
+        emb_mod.embed_cartesian_into(x, graph, buf, bias if plain else None, out_scale=scale, prepared=prepared)
+        if not plain:
+            emb_mod._homog_epilogue(buf, scale, bias, in_place=True)
+        return buf
+
+    def _fused_cart_linear(self, graph, prepared, scale, wq, yin, y):
+        """fsw_conv_fused_cart_f32 on a prepared Cartesian projection; returns the first module of the MLP left to torch."""
+        L = _lib.lib()
+        emb = self.fsw_embed
+        lin = self.mlp[0]
+        act, slope, next_module = self._fused_activation()
+        fr = emb.freqs.detach().contiguous()
+        bias = emb.bias.detach().reshape(-1) if emb.enable_bias else None
+        a = emb._cart_tuned_args(graph, prepared["stats"], prepared["Xp"], prepared["ldp"], fr, emb.nSlices, prepared["table"], None,
+                                 scale, emb.total_mass_encoding_dim)
+        a.bias = bias.data_ptr() if bias is not None else None
+        rc = L.fsw_conv_fused_cart_f32(ctypes.byref(a), wq.data_ptr(), wq.shape[1],
+                                       lin.bias.data_ptr() if lin.bias is not None else None, lin.out_features,
+                                       yin.data_ptr() if yin is not None else None, yin.stride(0) if yin is not None else 0,
+                                       1 if yin is not None else 0, act, slope, y.data_ptr(), y.stride(0),
+                                       torch.cuda.current_stream(y.device).cuda_stream)
+        _lib.check(rc, "fsw_conv_fused_cart_f32")
+        return next_module
 
     def adjacency_coo(self, edge_index, edge_features, num_vertices, dtype):
         """Coalesced COO adjacency adj[recipient, sender] and edge-feature tensor exactly as the reference builds them
@@ -517,6 +600,8 @@ class FSW_conv(_Base):
             return False
         if not emb.plain_mass:
             return False
+        if emb.cartesian_mode:
+            return int(_lib.lib().fsw_conv_fused_cart_lds_bytes(emb.nSlices, emb.nFreqs, emb.total_mass_encoding_dim)) <= 64 * 1024
         width = emb.nSlices if num_slices is None else int(num_slices)
         return int(_lib.lib().fsw_conv_fused_lds_bytes(width, emb.total_mass_encoding_dim)) <= 64 * 1024
 
@@ -586,6 +671,8 @@ class FSW_conv(_Base):
         embedding that slice sharding has to move).  Every row is computed by the same kernel as on one GPU (the x . W2^T
         term by a BLAS GEMM instead of the projection kernel: agreement to 1e-7).
         Needs the configuration of the fused kernel (unit weights, first MLP module a Linear layer)."""
+        if enabled and self.fsw_embed.cartesian_mode:
+            raise NotImplementedError("fsw_gnn_amd: a Cartesian layer (embed_slices / embed_freqs) with node-parallel is not implemented")
         if enabled and not self._fusable():
             raise NotImplementedError("fsw_gnn_amd: node-parallel needs the fused configuration (csrc/conv_fused.hip); use enable_slice_parallel")
         self._node_parallel = bool(enabled)
@@ -655,6 +742,9 @@ class FSW_conv(_Base):
                 returns (rows [chunks, chunk_rows / world, out], first_row [chunks]) -- this rank's finished rows.
         stats   optional dict that every forward fills with the form taken and the bytes each rank sent."""
         assert mode in ('auto', 'gather', 'consumer', 'exchange') and output in ('replicated', 'sharded')
+        if enabled and self.fsw_embed.cartesian_mode:
+            raise NotImplementedError("fsw_gnn_amd: a Cartesian layer (embed_slices / embed_freqs) with enable_slice_parallel is not "
+                                      "implemented (dist.py shards the slice axis of the diagonal embedding)")
         self._slice_parallel = dict(group=group, mode=mode, chunks=chunks, output=output, stats=stats) if enabled else None
         return self
 
@@ -696,7 +786,15 @@ class FSW_readout(FSW_conv):
             return self._mlp_or_dim_reduct(emb_mod(vertex_features, W=adj, graph_mode=True))
         graph = build_csr(graph_index.contiguous(), src, None, batch_size, num_vertices)
         needs_grad = torch.is_grad_enabled() and (vertex_features.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if needs_grad:
+        if emb_mod.cartesian_mode:
+            # the same two embedding calls as FSW_conv's: segments of up to 2048 vertices on the wavefront class, longer ones on the
+            # generic kernel (FSW_embedding does the same)
+            if needs_grad:
+                emb = emb_mod.embed_cartesian_autograd(vertex_features.contiguous(), graph)
+            else:
+                x = vertex_features.contiguous()
+                emb = self._cart_embed_buffer(x, graph, emb_mod.prepare_cartesian(x, graph), 0, 1.0)
+        elif needs_grad:
             # training: the same differentiable embedding as FSW_conv (the reference readout is differentiable through
             # self.fsw_embed, fsw_conv.py:503-515); readout segments are long rows, covered by the long-row backward kernels
             emb = emb_mod.embed_autograd(vertex_features.contiguous(), graph)

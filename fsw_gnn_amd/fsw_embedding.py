@@ -927,17 +927,22 @@ class FSW_embedding(nn.Module):
             return self._forward_generic(Xf.contiguous(), rec, snd, wvals, None, num_rows, bias)
         graph = build_csr(rec, snd, wvals.detach().contiguous() if wvals is not None else None, num_rows, Xf.shape[0])
         if train:
-            # 'homog' / 'homog_alt': the 'plain' embedding without bias from the kernels, then the epilogue out of place so that
-            # autograd differentiates it (as embed_autograd does)
-            scale = self.total_mass_encoding_scale if self.encode_total_mass else None
-            P = _CartEmbedFn.apply(Xf.contiguous(), self.projVecs, self.freqs, self.bias if (plain and self.enable_bias) else None,
-                                   scale, self, graph, 1.0)
-            return P if plain else self._homog_epilogue(P, 1.0, bias)
+            return self.embed_cartesian_autograd(Xf.contiguous(), graph)
         with torch.no_grad():
             out = torch.empty((num_rows, self.d_out), dtype=dt, device=dev)
             self.embed_cartesian_into(Xf.contiguous(), graph, out, bias.detach() if (bias is not None and plain) else None,
                                       serialize_num_slices)
             return out if plain else self._homog_epilogue(out, 1.0, bias.detach() if bias is not None else None)
+
+    def embed_cartesian_autograd(self, X, graph, out_scale=1.0):
+        """Differentiable float32 Cartesian embedding of a CSR graph, [num_rows, d_out] collapsed (training path of forward() and of
+        FSW_conv / FSW_readout with embed_slices / embed_freqs): see _CartEmbedFn.  'homog' / 'homog_alt': the 'plain' embedding
+        without bias from the kernels, then the epilogue out of place so that autograd differentiates it (as embed_autograd does)."""
+        scale = self.total_mass_encoding_scale if self.encode_total_mass else None
+        plain = self.plain_mass
+        P = _CartEmbedFn.apply(X, self.projVecs, self.freqs, self.bias if (plain and self.enable_bias) else None, scale, self, graph,
+                               out_scale)
+        return P if plain else self._homog_epilogue(P, out_scale, self.bias.reshape(-1) if self.enable_bias else None)
 
     def _cart_unit_table(self, graph, fr):
         """Unit coefficient table [rows, F] of the F frequencies (unit weights with tau <= 1), else None."""

@@ -361,6 +361,9 @@ int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double
  *                         unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1, and scratch of
  *                         fsw_embed_cart_generic_scratch_bytes(max_degree, rows above FSW_LDS_MAX_DEG) bytes when
  *                         max_degree >= FSW_LDS_MAX_DEG (those rows run on the generic kernel of fsw_embed_cart_generic).
+ *                         Rows of 1 .. FSW_REG_MAX_DEG unit-weight neighbours are stored 16 bytes at a time when F % 4 == 0,
+ *                         ldo % 4 == 0, ldt % 4 == 0 and out + has_mass, bias + has_mass and unit_table are 16-byte aligned (a
+ *                         caller with a mass column gets there by starting its rows 3 floats into an aligned buffer).
  * fsw_embed_cart_generic  the kernel of fsw_embed_generic with every sorted slice read out at all F frequencies: any degree, float32 or
  *                         float64 storage (value_dtype), float64 arithmetic, on a plain CSR (perm, bin_start ignored; no edge term);
  *                         forward (g == NULL) or backward (g != NULL): for the output gradient g [num_rows, ldg]
@@ -416,6 +419,19 @@ int fsw_embed_cart_f32(const fsw_cart_args* args, fsw_stream_t stream);
  * unit_dtable: fsw_unit_dcoeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1 (with args->unit_table as in the forward).
  * scratch: as for fsw_embed_cart_f32 (rows above the wavefront class run on the generic kernel in backward mode). */
 int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* args, const float* unit_dtable, int64_t lddt, fsw_stream_t stream);
+/* FSW_conv with a Cartesian embedding, fast path (csrc/conv_fused.hip: k_conv_fused_cart): fsw_conv_fused_f32 for an embedding row
+ * [mass | S runs of F outputs], K = has_mass + S F.  One workgroup per 32 rows of one in-degree: every (row, slice) line is gathered
+ * from Xp and sorted once, its F outputs go to the LDS tile (never to HBM), then the tile is multiplied by W1^T and finished exactly
+ * as in fsw_conv_fused_f32 (same Wq layout with K = has_mass + S F, same Yin / yin_by_node / lin_bias / act / slope / Y arguments).
+ * args: as for fsw_embed_cart_f32 (Xp of fsw_project_f32 at ldp >= S, unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG)
+ * with ldt >= F, bias NULL or [has_mass + S F], out_scale, mass_fn, mass_scale, perm, bin_start, bin_start_host); out / ldo / g /
+ * scratch are ignored.  Preconditions: w == NULL, tau <= 1, fsw_conv_fused_cart_lds_bytes(S, F, has_mass) <= 64 KiB and NO row above
+ * FSW_REG_MAX_DEG neighbours (checked against bin_start_host: the call fails instead of leaving rows of Y unwritten; the caller
+ * runs fsw_embed_cart_f32 + its own GEMM on such graphs).                                                                      */
+size_t fsw_conv_fused_cart_lds_bytes(int S, int F, int has_mass);
+int fsw_conv_fused_cart_f32(const fsw_cart_args* args, const float* Wq, int64_t ldw, const float* lin_bias, int Hout,
+                            const float* Yin, int64_t ldyin, int yin_by_node, int act, float slope, float* Y, int64_t ldy,
+                            fsw_stream_t stream);
 
 /* ---- stand-alone segmented cumulative sum --------------------------------------------------------
  * Replaces segcumsum / segcumsum_cuda (reference fsw_embedding.py:2795-3012): inclusive scan of

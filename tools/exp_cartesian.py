@@ -17,7 +17,16 @@ configuration:
   pc     a point-cloud batch of 256 clouds x 1024 points, d_in 3, S = 64, F = 16, W = 'uniform'
 A package with the tuned backward (fsw_embedding._CartEmbedFn) takes it; --generic, or a package without it, takes the generic
 Cartesian kernel for forward and backward (what every autograd call of Cartesian mode ran on before the tuned backward):
-    python tools/exp_cartesian.py --train [--workload graph,pc] [--steps 10] [--warmup 2] [--generic]"""
+    python tools/exp_cartesian.py --train [--workload graph,pc] [--steps 10] [--warmup 2] [--generic]
+
+--conv: the whole FSW_conv layer on the config-3 graph, in = out = 128, one Linear layer + LeakyReLU, no_grad forward including
+the CSR build (what bench.py times), one line per form and run so that runs of different forms can alternate:
+  diag     the diagonal layer, embed_dim = S F + 1 (257 slices; runs on a package without the Cartesian layer too)
+  unfused  FSW_conv(embed_slices=S, embed_freqs=F) with fuse_linear = False: embed_cartesian_into + two GEMMs
+  fused    the same layer on k_conv_fused_cart (csrc/conv_fused.hip)
+    python tools/exp_cartesian.py --conv --forms unfused,fused --runs 5 [--reps 20]
+    python tools/exp_cartesian.py --conv --train --forms diag,cart [--steps 10]      one training step (forward + backward)
+    rocprofv3 --kernel-trace --stats -d DIR -o conv -- python tools/exp_cartesian.py --conv --forms fused --runs 1"""
 import argparse
 import os
 import sys
@@ -39,6 +48,9 @@ ap.add_argument("--workload", default="graph,pc", help="--train: subset of graph
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--generic", action="store_true", help="--train: the generic Cartesian kernel for forward and backward")
+ap.add_argument("--conv", action="store_true", help="time the FSW_conv layer (diagonal / Cartesian unfused / Cartesian fused)")
+ap.add_argument("--forms", default="unfused,fused", help="--conv: forms to time, alternating over the runs (--train: diag, cart)")
+ap.add_argument("--runs", type=int, default=5, help="--conv: runs of every form")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 
@@ -103,6 +115,47 @@ def train_leg():
         print("train pc: %d clouds x %d points d_in=3 S=64 F=16 W=uniform, %s: %.3f ms/step" % (B, npts, path, step_ms(step)), flush=True)
 
 
+def conv_leg():
+    from fsw_gnn_amd import FSW_conv
+    n, E, d = bench.N_NODES, bench.N_EDGES, bench.D_FEAT
+    S, F = args.slices, args.freqs
+    x, ei = bench.make_inputs(n, E, dev)
+    forms = args.forms.split(",")
+    layers = {}
+    for form in forms:
+        torch.manual_seed(7)
+        if form == "diag":
+            layers[form] = FSW_conv(d, d, embed_dim=S * F + 1, learnable_embedding=args.train, device=dev)
+        else:
+            layers[form] = FSW_conv(d, d, embed_slices=S, embed_freqs=F, learnable_embedding=args.train, device=dev)
+            if form == "unfused":
+                layers[form].fuse_linear = False
+    print("conv, config 3: n=%d E=%d in=out=%d S=%d F=%d (K = %d)%s" % (n, E, d, S, F, S * F + 1, ", training step" if args.train else ""))
+    if args.train:
+        xg = x.clone().requires_grad_(True)
+        G = torch.randn((n, d), device=dev)
+    for run in range(args.runs):
+        for form in forms:
+            layer = layers[form]
+            if args.train:
+                def step():
+                    layer.zero_grad(set_to_none=True)
+                    xg.grad = None
+                    layer(xg, ei).backward(G)
+                for _ in range(args.warmup if run == 0 else 1):
+                    step()
+                ms = bench.timed_ms(step, args.steps, dev)
+            else:
+                with torch.no_grad():
+                    for _ in range(args.warmup if run == 0 else 1):
+                        layer(x, ei)
+                    ms = bench.timed_ms(lambda: layer(x, ei), args.reps, dev)
+            print("run %d  %-8s %8.3f ms" % (run, form, ms), flush=True)
+
+
+if args.conv:
+    conv_leg()
+    sys.exit(0)
 if args.train:
     train_leg()
     sys.exit(0)
