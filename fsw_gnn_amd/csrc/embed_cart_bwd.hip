@@ -14,7 +14,10 @@
 //   33 <= L <= 2048  one wavefront per (row, slice), the line sorted across it as 64-bit (key, index) words (wave_sort.h); every
 //                    lane keeps its M sorted elements and accumulates their gradients over the frequency loop (g_f and xi_f
 //                    wave-uniform); the lower bound of a lane's first element comes from its neighbour lane.
-//   longer lines     the generic kernel in backward mode (k_embed_generic, embed_generic.hip), as in the forward.
+//   2049 <= D <= 32768, unit weights with tau <= 1: one wavefront per (row, slice) in a scratch line of packed words
+//                    (embed_cart_hub_bwd.hip: k_cart_bwd_long), 12 bytes of scratch per element of the padded line and wavefront.
+//   longer lines     (general weights above 2048 elements, any row above 32768) the generic kernel in backward mode
+//                    (k_embed_generic, embed_generic.hip), as in the forward.
 // gfreq: the register class sums a workgroup's partials in LDS, the wavefront class across the wavefront; one float atomic per
 // (workgroup resp. wavefront, frequency).
 #include <algorithm>
@@ -422,6 +425,8 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
     }
   });
   if (rc) return rc;
-  // longer lines (D > 2048; general weights: D + 1 > 2048): the generic kernel in backward mode
-  return launch_cart_long_rows(c, extra, stream);
+  // unit weights, 2049 .. 32768 neighbours: one wavefront per line in a scratch line (embed_cart_hub_bwd.hip)
+  if (unit_fast && (rc = launch_cart_hub_bwd(c, stream))) return rc;
+  // what is left (general weights: D + 1 > 2048; unit weights: D > 32768): the generic kernel in backward mode
+  return launch_cart_long_rows(c, extra, unit_fast, stream);
 }

@@ -282,40 +282,7 @@ static int launch_quad_bwd(const fsw_embed_args& a, int bin_lo, int bin_hi, int6
 
 // ---- rows above FSW_LDS_MAX_DEG ------------------------------------------------------------------------------------------
 // fences below: workgroup scope orders a wave's scratch stores before its own later loads (same CU, same L1; see embed_wsort.hip)
-constexpr int kSweepDepthB = 4;
-
-__device__ __forceinline__ void sweep_pairs_b(unsigned long long* __restrict__ se, int Dp, int size, int st, bool flip) {
-  const int npairs = Dp >> 1;
-  const int half = size >> 1;
-  for (int i0 = lane_id(); i0 < npairs; i0 += kWave * kSweepDepthB) {
-    int ia[kSweepDepthB], ib[kSweepDepthB];
-    unsigned long long a[kSweepDepthB], b[kSweepDepthB];
-#pragma unroll
-    for (int u = 0; u < kSweepDepthB; ++u) {
-      const int idx = i0 + u * kWave;
-      if (flip) {
-        const int blk = idx / half, off = idx - blk * half;
-        ia[u] = blk * size + off;
-        ib[u] = blk * size + size - 1 - off;
-      } else {
-        const int blk = idx / st, off = idx - blk * st;
-        ia[u] = blk * 2 * st + off;
-        ib[u] = ia[u] + st;
-      }
-      a[u] = se[ia[u]];
-      b[u] = se[ib[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < kSweepDepthB; ++u) {
-      if (b[u] < a[u]) {   // packed words: by key, equal keys by element index
-        se[ia[u]] = b[u];
-        se[ib[u]] = a[u];
-      }
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-}
-
+// (sweep_pairs_b, the element-wise exchanges of a merge level over the scratch line: wave_sort.h)
 template <int M, bool WEIGHTED>
 __global__ void __launch_bounds__(256) k_embed_wsort_global_bwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                                 const float* __restrict__ w, const int32_t* __restrict__ perm,

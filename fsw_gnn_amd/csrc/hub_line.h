@@ -1,0 +1,105 @@
+// Building blocks of the kernels that keep ONE (row, slice) line of a hub row (FSW_LDS_MAX_DEG < in-degree) in the registers of the
+// NW wavefronts of a workgroup: the striped gather of a wavefront's chunk, the register exchange between wavefronts through LDS, the
+// bitonic merge levels above one chunk and the unit-weight readout of a lane's keys.  Shared by the diagonal kernels of
+// embed_hub.hip (k_embed_hub, k_embed_hub_q4, k_embed_giant) and the Cartesian one of embed_cart_hub.hip (k_cart_hub).  gfx950.
+#pragma once
+#include "fsw_common.h"
+#include "wave_sort.h"
+
+namespace fsw {
+
+#ifndef FSW_HUB_ABL
+#define FSW_HUB_ABL 0   // timing experiments (tools/exp_hub.sh): 1 no gather, 2 no wave sort, 4 no cross-wave merge, 8 no readout
+#endif
+
+// register exchange between the wavefronts of a workgroup through xbuf [NW][CAP]: this wavefront keeps, element by
+// element, the smaller (lower) or larger key of (its own, wavefront `partner`'s -- same element, or mirrored)
+template <int M>
+__device__ __forceinline__ void wave_exchange(WaveLine<M, false>& ln, float* __restrict__ xbuf, int w, int lane, int partner,
+                                              bool mirrored, bool lower) {
+  constexpr int CAP = M * kWave;
+  // one base register per side and immediate offsets j * 256 B: the asm statements keep the compiler from folding the lane
+  // term into 32 separate per-element addresses (v_bitop3 of lane ^ constant), which it then hoists out of loops and spills.
+  // The OFFSET is laundered, not the pointer: an opaque pointer loses its LDS address space and every access became a
+  // flat_load / flat_store (72 of each in k_embed_hub<4, 24>: the flat path counts on vmcnt AND lgkmcnt, so each exchange also
+  // waited for the wavefront's outstanding gathers)
+  int moff = w * CAP + lane;
+  asm volatile("" : "+v"(moff));
+  float* mine = xbuf + moff;
+#pragma unroll
+  for (int j = 0; j < M; ++j) mine[j * kWave] = ln.k[j];
+  __syncthreads();
+  int toff = partner * CAP + (mirrored ? kWave - 1 - lane : lane);
+  asm volatile("" : "+v"(toff));
+  const float* theirs = xbuf + toff;
+  const float lim = lower ? -__builtin_inff() : __builtin_inff();   // wave-uniform: min below the partner, max above it
+#pragma unroll
+  for (int j = 0; j < M; ++j) ln.k[j] = minmax_by_limit(ln.k[j], theirs[(mirrored ? M - 1 - j : j) * kWave], lim);
+  __syncthreads();   // everybody has read: the buffer may be overwritten by the next exchange
+}
+
+// NW sorted chunks (one per wavefront, after WaveLine::sort) -> the workgroup's NW * CAP keys sorted; element (lane, j) of
+// wavefront w then has rank w * CAP + lane * M + j
+template <int NW, int M>
+__device__ __forceinline__ void workgroup_merge_levels(WaveLine<M, false>& ln, float* __restrict__ xbuf, int w, int lane) {
+#pragma unroll
+  for (int size = 2; size <= ((FSW_HUB_ABL & 4) ? 0 : NW); size <<= 1) {
+    wave_exchange<M>(ln, xbuf, w, lane, w ^ (size - 1), true, (w & (size >> 1)) == 0);        // element E against E ^ (size * CAP - 1)
+    for (int st = size >> 2; st >= 1; st >>= 1) wave_exchange<M>(ln, xbuf, w, lane, w ^ st, false, (w & st) == 0);
+    ln.merge_chunk();
+  }
+}
+
+// the workgroup's NW * CAP keys form a bitonic sequence whose halves were separated elsewhere: finish the merge
+template <int NW, int M>
+__device__ __forceinline__ void workgroup_merge_block(WaveLine<M, false>& ln, float* __restrict__ xbuf, int w, int lane) {
+#pragma unroll
+  for (int st = NW >> 1; st >= 1; st >>= 1) wave_exchange<M>(ln, xbuf, w, lane, w ^ st, false, (w & st) == 0);
+  ln.merge_chunk();
+}
+
+// unit-weight readout of the lane's M keys of ranks r0 .. r0 + M - 1 in a neighbourhood of D: coefficients
+// (1 + xi) [sin(2 pi xi (r + 1) / D) - sin(2 pi xi r / D)] / (pi xi) (reference fsw_embedding.py:1047-1075, 1109 with
+// weights 1 / D) = B cos(2 pi xi (r + 1/2) / D) by the one-FMA float64 recurrence of UnitCoef (fsw_common.h) started at the
+// lane's first rank.  Returns the lane's partial sum.
+template <int M, class Line>
+__device__ __forceinline__ float unit_readout(const Line& ln, int r0, int D, float xif) {
+  const double xi = (double)xif;
+  const double inv = 1.0 / (double)D;
+  float acc = 0.f;
+  if (xif < 1e-30f) {                       // xi == 0: Delta_t = 2 w_t
+#pragma unroll
+    for (int j = 0; j < M; ++j) acc += (r0 + j < D) ? ln.k[j] : 0.f;
+    return acc * 2.f * (float)inv;
+  }
+  if constexpr (FSW_HUB_ABL & 8) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) acc += (r0 + j < D) ? ln.k[j] : 0.f;
+    return acc;
+  }
+  UnitCoef uc;
+  uc.start(xi, D, r0);
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    const float cj = uc.next();
+    acc += (r0 + j < D) ? cj * ln.k[j] : 0.f;
+  }
+  return acc * uc.B;
+}
+
+// gather elements t0 + j * 64 + lane (j < M; striped: lane-contiguous col reads -- the chunk is sorted next) of slice k
+template <int M>
+__device__ __forceinline__ void gather_chunk(WaveLine<M, false>& ln, const int32_t* __restrict__ colrow, int t0, int D,
+                                             const float* __restrict__ Xp, int64_t ldp, int k, int lane) {
+  int c[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    const int t = t0 + j * kWave + lane;
+    c[j] = t < D ? colrow[t] : -1;
+  }
+#pragma unroll
+  for (int j = 0; j < M; ++j)
+    ln.k[j] = c[j] >= 0 ? ((FSW_HUB_ABL & 1) ? (float)((c[j] * 2654435761u) >> 8) : Xp[(int64_t)c[j] * ldp + k]) : __builtin_inff();
+}
+
+}  // namespace fsw

@@ -234,4 +234,41 @@ struct WaveLine64 {
   __device__ __forceinline__ int index(int j) const { return (int)(unsigned int)e[j]; }
 };
 
+// A line longer than one chunk lives in a scratch line of packed words in global memory (one wavefront per line): one exchange
+// step of a merge level above the chunk size -- the flip (element i against i ^ (size - 1)) or a half-cleaner of stride st -- over
+// the Dp words of the line.  The workgroup-scope fence orders the wavefront's stores before its own later loads (same CU, same L1).
+constexpr int kSweepDepthB = 4;
+
+__device__ __forceinline__ void sweep_pairs_b(unsigned long long* __restrict__ se, int Dp, int size, int st, bool flip) {
+  const int npairs = Dp >> 1;
+  const int half = size >> 1;
+  for (int i0 = lane_id(); i0 < npairs; i0 += kWave * kSweepDepthB) {
+    int ia[kSweepDepthB], ib[kSweepDepthB];
+    unsigned long long a[kSweepDepthB], b[kSweepDepthB];
+#pragma unroll
+    for (int u = 0; u < kSweepDepthB; ++u) {
+      const int idx = i0 + u * kWave;
+      if (flip) {
+        const int blk = idx / half, off = idx - blk * half;
+        ia[u] = blk * size + off;
+        ib[u] = blk * size + size - 1 - off;
+      } else {
+        const int blk = idx / st, off = idx - blk * st;
+        ia[u] = blk * 2 * st + off;
+        ib[u] = ia[u] + st;
+      }
+      a[u] = se[ia[u]];
+      b[u] = se[ib[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < kSweepDepthB; ++u) {
+      if (b[u] < a[u]) {   // packed words: by key, equal keys by element index
+        se[ia[u]] = b[u];
+        se[ib[u]] = a[u];
+      }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+}
+
 }  // namespace fsw

@@ -787,8 +787,8 @@ class FSW_readout(FSW_conv):
         graph = build_csr(graph_index.contiguous(), src, None, batch_size, num_vertices)
         needs_grad = torch.is_grad_enabled() and (vertex_features.requires_grad or any(p.requires_grad for p in self.parameters()))
         if emb_mod.cartesian_mode:
-            # the same two embedding calls as FSW_conv's: segments of up to 2048 vertices on the wavefront class, longer ones on the
-            # generic kernel (FSW_embedding does the same)
+            # the same two embedding calls as FSW_conv's: segments of up to 2048 vertices on the wavefront class, up to 32768 on the
+            # hub kernels, longer ones on the generic kernel (FSW_embedding does the same)
             if needs_grad:
                 emb = emb_mod.embed_cartesian_autograd(vertex_features.contiguous(), graph)
             else:

@@ -357,10 +357,15 @@ int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double
  *   out[r * ldo]                      = out_scale * (f(m_r) * mass_scale + bias[0])                     if has_mass
  * where p_(t) sorts Xp[col[e], s] over the row's entries (+ the pad element) and Delta_t is the readout of fsw_embed_generic.
  * fsw_embed_cart_backward_keys_f32 (below) is the tuned float32 backward of fsw_embed_cart_f32 for keys and frequencies.
- * fsw_embed_cart_f32      tuned float32 forward on a graph of fsw_graph_build: needs perm, bin_start and bin_start_host,
- *                         unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1, and scratch of
- *                         fsw_embed_cart_generic_scratch_bytes(max_degree, rows above FSW_LDS_MAX_DEG) bytes when
- *                         max_degree >= FSW_LDS_MAX_DEG (those rows run on the generic kernel of fsw_embed_cart_generic).
+ * fsw_embed_cart_f32      tuned float32 forward on a graph of fsw_graph_build: needs perm, bin_start and bin_start_host and
+ *                         unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1.
+ *                         Scratch, forward: only the rows that run on the generic kernel of fsw_embed_cart_generic need it --
+ *                           w == NULL and tau <= 1: rows above FSW_HUB_MAX_DEG (rows of FSW_LDS_MAX_DEG + 1 .. FSW_HUB_MAX_DEG
+ *                             neighbours keep their lines in registers, csrc/embed_cart_hub.hip); scratch may be NULL when
+ *                             max_degree <= FSW_HUB_MAX_DEG;
+ *                           otherwise: rows of FSW_LDS_MAX_DEG neighbours and above (the pad element makes a line of D + 1);
+ *                         fsw_embed_cart_generic_scratch_bytes(max_degree, number of those rows) bytes: 36 bytes per element of a
+ *                         line of the next power of two >= max_degree + 1 and workgroup.
  *                         Rows of 1 .. FSW_REG_MAX_DEG unit-weight neighbours are stored 16 bytes at a time when F % 4 == 0,
  *                         ldo % 4 == 0, ldt % 4 == 0 and out + has_mass, bias + has_mass and unit_table are 16-byte aligned (a
  *                         caller with a mass column gets there by starting its rows 3 floats into an aligned buffer).
@@ -417,8 +422,17 @@ int fsw_embed_cart_f32(const fsw_cart_args* args, fsw_stream_t stream);
  * Adds    args->gfreq[f]         += out_scale * sum_{r,s} g[r, has_mass + s F + f] * d out[r,s,f] / d xi_f  (nullable; caller zeroes)
  * args->gw must be NULL (gradients w.r.t. the weights stay on fsw_embed_cart_generic).
  * unit_dtable: fsw_unit_dcoeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1 (with args->unit_table as in the forward).
- * scratch: as for fsw_embed_cart_f32 (rows above the wavefront class run on the generic kernel in backward mode). */
+ * Scratch, backward: w == NULL and tau <= 1: needed as soon as max_degree > FSW_LDS_MAX_DEG.  A row of FSW_LDS_MAX_DEG + 1 ..
+ *   FSW_HUB_MAX_DEG neighbours is sorted by one wavefront per (row, slice) in a scratch line of 12 bytes per element of the next
+ *   power of two >= the longest row of its degree bin (csrc/embed_cart_hub_bwd.hip); the launch uses as many wavefronts as the
+ *   buffer holds lines (at most 2048) and needs one.  fsw_embed_cart_backward_scratch_bytes(max_degree, rows above
+ *   FSW_LDS_MAX_DEG, S) returns the recommended size (room for min(2048, rows * S) wavefronts, capped at 2 GiB; 0 when
+ *   max_degree <= FSW_LDS_MAX_DEG; with rows above FSW_HUB_MAX_DEG at least what the generic kernel needs for them).  A buffer of
+ *   fsw_embed_cart_generic_scratch_bytes(max_degree, rows >= 1) bytes also suffices (three lines or more).
+ *   Otherwise (general weights, tau > 1): as for fsw_embed_cart_f32 -- those rows run on the generic kernel in backward mode.
+ * The buffer must be 16-byte aligned. */
 int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* args, const float* unit_dtable, int64_t lddt, fsw_stream_t stream);
+size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S);
 /* FSW_conv with a Cartesian embedding, fast path (csrc/conv_fused.hip: k_conv_fused_cart): fsw_conv_fused_f32 for an embedding row
  * [mass | S runs of F outputs], K = has_mass + S F.  One workgroup per 32 rows of one in-degree: every (row, slice) line is gathered
  * from Xp and sorted once, its F outputs go to the LDS tile (never to HBM), then the tile is multiplied by W1^T and finished exactly

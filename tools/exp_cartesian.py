@@ -26,7 +26,19 @@ the CSR build (what bench.py times), one line per form and run so that runs of d
   fused    the same layer on k_conv_fused_cart (csrc/conv_fused.hip)
     python tools/exp_cartesian.py --conv --forms unfused,fused --runs 5 [--reps 20]
     python tools/exp_cartesian.py --conv --train --forms diag,cart [--steps 10]      one training step (forward + backward)
-    rocprofv3 --kernel-trace --stats -d DIR -o conv -- python tools/exp_cartesian.py --conv --forms fused --runs 1"""
+    rocprofv3 --kernel-trace --stats -d DIR -o conv -- python tools/exp_cartesian.py --conv --forms fused --runs 1
+
+--hub: unit-weight rows of 2049 .. 32768 neighbours (csrc/embed_cart_hub.hip, csrc/embed_cart_hub_bwd.hip), forward (no_grad) and one
+training step (forward + backward) each:
+  readout  FSW_readout(embed_slices=16, embed_freqs=16), one batch of 8 graphs per degree class (2500, 6000, 12000, 24000 vertices)
+           and one mixed batch of 2500 .. 30000 vertices
+  rmat     FSW_embedding(nSlices=16, nFreqs=16) on the RMAT-20 graph of tools/exp_skew.py (1M nodes, 10M unit edges, prebuilt CSR)
+The library is the one FSW_HIP_LIBRARY names (fsw_gnn_amd/_lib.py).  A build from before the hub kernels (no export
+fsw_embed_cart_backward_scratch_bytes: a parent commit built in a copy of the tree and copied to _variants/) is driven by the same
+host code with the scratch its generic kernel needs for every row above 2048 neighbours, so both builds can alternate on one box:
+    python tools/exp_cartesian.py --hub [--workload readout,rmat] --steps 3 --warmup 1
+    FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --hub --steps 3 --warmup 1
+    rocprofv3 --kernel-trace --stats -d DIR -o hub -- python tools/exp_cartesian.py --hub --workload readout --steps 1"""
 import argparse
 import os
 import sys
@@ -44,13 +56,14 @@ ap.add_argument("--slices", type=int, default=16)
 ap.add_argument("--freqs", type=int, default=16)
 ap.add_argument("--only", default="abc", help="subset of the configurations a, b, c to time")
 ap.add_argument("--train", action="store_true", help="time one training step (forward + backward) instead of the forwards")
-ap.add_argument("--workload", default="graph,pc", help="--train: subset of graph, graph_w, pc")
+ap.add_argument("--workload", default="graph,pc", help="--train: subset of graph, graph_w, pc; --hub: subset of readout, rmat (default both)")
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--generic", action="store_true", help="--train: the generic Cartesian kernel for forward and backward")
 ap.add_argument("--conv", action="store_true", help="time the FSW_conv layer (diagonal / Cartesian unfused / Cartesian fused)")
 ap.add_argument("--forms", default="unfused,fused", help="--conv: forms to time, alternating over the runs (--train: diag, cart)")
 ap.add_argument("--runs", type=int, default=5, help="--conv: runs of every form")
+ap.add_argument("--hub", action="store_true", help="time the unit-weight hub rows (2049 .. 32768 neighbours), forward and training step")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 
@@ -153,6 +166,86 @@ def conv_leg():
             print("run %d  %-8s %8.3f ms" % (run, form, ms), flush=True)
 
 
+def hub_leg():
+    from fsw_gnn_amd import FSW_readout, synth
+    has_hub = hasattr(__import__("ctypes").CDLL(_lib.LIB_PATH), "fsw_embed_cart_backward_scratch_bytes")
+    if not has_hub:
+        # a build from before the hub kernels: no such export, and every row above 2048 neighbours runs on the generic kernel, which
+        # needs its scratch in both directions
+        del _lib._SIGNATURES["fsw_embed_cart_backward_scratch_bytes"]
+
+        def generic_scratch(self, graph, st):
+            if st[_lib.STAT_MAX_DEGREE] < _lib.LDS_MAX_DEG:
+                return None
+            bsh = graph.bin_start_host[0]
+            long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[_lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS - 1])
+            return torch.empty(int(_lib.lib().fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
+                               dtype=torch.uint8, device=graph.rowptr.device)
+
+        FSW_embedding._cart_scratch = generic_scratch
+        FSW_embedding._cart_backward_scratch = lambda self, graph, st, forward_scratch: forward_scratch
+    print("library %s: %s" % (_lib.LIB_PATH, "hub kernels" if has_hub else "generic kernel on the rows above 2048 neighbours"), flush=True)
+    S, F = args.slices, args.freqs
+    steps, warmup = args.steps, args.warmup
+    workload = "readout,rmat" if args.workload == ap.get_default("workload") else args.workload
+
+    def time_pair(name, forward, step):
+        with torch.no_grad():
+            for _ in range(warmup):
+                forward()
+            fwd = bench.timed_ms(forward, steps, dev)
+        for _ in range(warmup):
+            step()
+        print("%-44s forward %10.3f ms   training step %10.3f ms" % (name, fwd, bench.timed_ms(step, steps, dev)), flush=True)
+
+    if "readout" in workload:
+        in_ch, out_ch = 32, 32
+        torch.manual_seed(7)
+        layer = FSW_readout(in_ch, out_ch, embed_slices=S, embed_freqs=F, learnable_embedding=True, device=dev)
+        batches = [("2049..4096", [2500] * 8), ("4097..8192", [6000] * 8), ("8193..16384", [12000] * 8), ("16385..32768", [24000] * 8),
+                   ("mixed", [2500, 5000, 9000, 12000, 16000, 20000, 25000, 30000])]
+        for name, sizes in batches:
+            gi = torch.cat([torch.full((m,), g, dtype=torch.int64) for g, m in enumerate(sizes)]).to(dev)
+            x = torch.randn((gi.numel(), in_ch), device=dev)
+            xg = x.clone().requires_grad_(True)
+            G = torch.randn((len(sizes), out_ch), device=dev)
+
+            def step():
+                layer.zero_grad(set_to_none=True)
+                xg.grad = None
+                layer(xg, gi, len(sizes)).backward(G)
+
+            time_pair("readout S=%d F=%d, 8 graphs, %s" % (S, F, name), lambda: layer(x, gi, len(sizes)), step)
+    if "rmat" in workload:
+        scale, E, d = 20, 10_000_000, 128
+        n = 1 << scale
+        ei = torch.from_numpy(synth.rmat_graph(scale, E, 7)).to(dev)
+        graph = build_csr(ei[1].contiguous(), ei[0].contiguous(), None, n, n)
+        st = graph.read_stats()
+        bins = graph.bin_start_host[0]
+        hub0 = _lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS
+        print("RMAT-%d: n=%d E=%d max degree %d, rows per hub bin %s, above: %d" % (
+            scale, n, E, st[_lib.STAT_MAX_DEGREE], [int(bins[b + 1] - bins[b]) for b in range(hub0, hub0 + _lib.NUM_HUB_BINS)],
+            int(bins[_lib.NUM_BINS] - bins[_lib.NUM_BINS - 1])), flush=True)
+        torch.manual_seed(7)
+        mod = FSW_embedding(d_in=d, nSlices=S, nFreqs=F, collapse_freqs=True, enable_bias=False, learnable_slices=True,
+                            learnable_freqs=True, freqs_init='spread', device=dev)
+        x = torch.randn((n, d), device=dev)
+        xg = x.clone().requires_grad_(True)
+        out = torch.empty((n, S * F), device=dev)
+        G = torch.randn((n, S * F), device=dev)
+
+        def step():
+            mod.zero_grad(set_to_none=True)
+            xg.grad = None
+            mod.embed_cartesian_autograd(xg, graph).backward(G)
+
+        time_pair("embedding S=%d F=%d, RMAT-%d" % (S, F, scale), lambda: mod.embed_cartesian_into(x, graph, out), step)
+
+
+if args.hub:
+    hub_leg()
+    sys.exit(0)
 if args.conv:
     conv_leg()
     sys.exit(0)
