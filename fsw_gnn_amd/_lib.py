@@ -18,6 +18,7 @@ MID_SIZES = (40, 48, 64, 80, 96, 128, 160, 192, 256)   # FSW_MID_SIZES: padded r
 NUM_LDS_BINS = 3                                          # FSW_NUM_LDS_BINS: degrees <= 512, 1024, 2048
 NUM_HUB_BINS = 4                                          # FSW_NUM_HUB_BINS: degrees <= 4096, 8192, 16384, 32768
 HUB_MAX_DEG = 32768
+CART_W_MAX_LINE = 16384       # FSW_CART_W_MAX_LINE: Cartesian mode, general weights, longest line (D + 1) of the tuned classes
 BIN_MID0 = REG_MAX_DEG + 1      # first bin above the register path (include/fsw_hip.h: FSW_BIN_MID0)
 NUM_BINS = REG_MAX_DEG + 1 + len(MID_SIZES) + NUM_LDS_BINS + NUM_HUB_BINS + 1
 NUM_STATS = 8
@@ -104,6 +105,7 @@ _SIGNATURES = {
     "fsw_embed_cart_f32": (ctypes.c_int, [ctypes.POINTER(CartArgs), c_vp]),
     "fsw_embed_cart_backward_keys_f32": (ctypes.c_int, [ctypes.POINTER(CartArgs), c_vp, c_i64, c_vp]),
     "fsw_embed_cart_backward_scratch_bytes": (c_sz, [c_i64, c_i64, c_i32]),
+    "fsw_embed_cart_weighted_backward_scratch_bytes": (c_sz, [c_i64, c_i64, c_i32]),
     "fsw_conv_fused_cart_lds_bytes": (c_sz, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "fsw_conv_fused_cart_f32": (ctypes.c_int, [ctypes.POINTER(CartArgs), c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_i64, ctypes.c_int,
                                                ctypes.c_int, c_f32, c_vp, c_i64, c_vp]),

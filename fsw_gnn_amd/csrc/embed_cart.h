@@ -1,4 +1,5 @@
-// What the forward (embed_cart.hip, embed_cart_hub.hip) and the tuned backward (embed_cart_bwd.hip, embed_cart_hub_bwd.hip) of Cartesian mode share: the degree classes, the
+// What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip) and the tuned backward (embed_cart_bwd.hip,
+// embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip) of Cartesian mode share: the degree classes, the
 // constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
 #pragma once
 #include <algorithm>
@@ -50,13 +51,18 @@ int for_each_wave_group(const int32_t* bs, int extra, Fn fn) {
 int launch_cart_hub(const fsw_cart_args* c, hipStream_t stream);        // forward, no scratch
 int launch_cart_hub_bwd(const fsw_cart_args* c, hipStream_t stream);    // backward, c->scratch: fsw_embed_cart_backward_scratch_bytes
 
-// Lines the tuned classes do not take (float32 storage): the generic kernel, forward or, with c->g, backward.  hub_done == false: the
-// lines above kCartMaxLine elements, on the rows of the last LDS bin and above; hub_done == true (unit weights with tau <= 1, whose
-// hub bins have kernels of their own): only the rows of FSW_BIN_GLOBAL.
-inline int launch_cart_long_rows(const fsw_cart_args* c, int extra, bool hub_done, hipStream_t stream) {
-  const int min_long = hub_done ? FSW_HUB_MAX_DEG + 1 : kCartMaxLine + 1 - extra;
+// embed_cart_hub_w.hip / embed_cart_hub_w_bwd.hip: general weights (w != NULL or tau > 1), the lines of kCartMaxLine + 1 ..
+// FSW_CART_W_MAX_LINE elements (FSW_LDS_MAX_DEG <= D < FSW_CART_W_MAX_LINE: the last LDS bin and the first three hub bins)
+int launch_cart_hub_w(const fsw_cart_args* c, hipStream_t stream);      // forward, no scratch
+int launch_cart_hub_w_bwd(const fsw_cart_args* c, hipStream_t stream);  // backward, c->scratch: fsw_embed_cart_weighted_backward_scratch_bytes
+
+// Lines the tuned classes do not take (float32 storage): the generic kernel, forward or, with c->g, backward.  unit_fast == false
+// (general weights; extra = 1, the pad element): the lines above FSW_CART_W_MAX_LINE elements, on the rows of the third hub bin (which
+// holds D = FSW_CART_W_MAX_LINE) and above; unit_fast == true (unit weights with tau <= 1; extra = 0): only the rows of FSW_BIN_GLOBAL.
+inline int launch_cart_long_rows(const fsw_cart_args* c, int extra, bool unit_fast, hipStream_t stream) {
+  const int min_long = unit_fast ? FSW_HUB_MAX_DEG + 1 : FSW_CART_W_MAX_LINE + 1 - extra;
   const int32_t* bs = c->bin_start_host;
-  const int p0 = hub_done ? bs[FSW_BIN_GLOBAL] : bs[FSW_BIN_LDS0 + FSW_NUM_LDS_BINS - 1];
+  const int p0 = unit_fast ? bs[FSW_BIN_GLOBAL] : bs[FSW_BIN_HUB0 + 2];
   const int64_t rows = (int64_t)bs[FSW_NUM_BINS] - p0;
   if (c->max_degree < min_long || rows <= 0) return 0;
   return launch_embed_generic(generic_args(*c, true, c->F), 0, c->perm + p0, rows, min_long, stream);

@@ -15,7 +15,9 @@
 //                    frequency f, Q = 64 / NF -- so that F < 64 does not leave most lanes idle; LDS reads are broadcasts.
 //   2049 <= D <= 32768, unit weights with tau <= 1: one workgroup of 2 .. 16 wavefronts per (row, slice), the line in their registers
 //                    (embed_cart_hub.hip: k_cart_hub, the hub machinery of the diagonal kernels), no scratch.
-//   longer lines     (general weights above 2048 elements, any row above 32768) the generic kernel in its Cartesian readout
+//   2049 <= L <= 16384, general weights: one workgroup of 2, 4 or 8 wavefronts per (row, slice), keys and weights in their registers
+//                    (embed_cart_hub_w.hip: k_cart_hub_w), no scratch.
+//   longer lines     (general weights above 16384 elements, any row above 32768) the generic kernel in its Cartesian readout
 //                    (k_embed_generic, embed_generic.hip; correct, not tuned: DESIGN.md).
 // Readout, by summation by parts of the reference's Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t)):
 //   out = (1 + xi) / (pi xi) sum_t sin(2 pi xi c_t) (p_(t) - p_(t+1)),  p_(L) = 0;   xi = 0:  out = sum_t 2 c_t (p_(t) - p_(t+1)).
@@ -367,6 +369,8 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   if (rc) return rc;
   // unit weights, 2049 .. 32768 neighbours: one workgroup of 2 .. 16 wavefronts per line (embed_cart_hub.hip)
   if (unit_fast && (rc = launch_cart_hub(c, stream))) return rc;
-  // what is left (general weights: D + 1 > 2048; unit weights: D > 32768): the generic kernel
+  // general weights, lines of 2049 .. 16384 elements: one workgroup of 2, 4 or 8 wavefronts per line (embed_cart_hub_w.hip)
+  if (!unit_fast && (rc = launch_cart_hub_w(c, stream))) return rc;
+  // what is left (general weights: D + 1 > 16384; unit weights: D > 32768): the generic kernel
   return launch_cart_long_rows(c, extra, unit_fast, stream);
 }

@@ -16,7 +16,9 @@
 //                    wave-uniform); the lower bound of a lane's first element comes from its neighbour lane.
 //   2049 <= D <= 32768, unit weights with tau <= 1: one wavefront per (row, slice) in a scratch line of packed words
 //                    (embed_cart_hub_bwd.hip: k_cart_bwd_long), 12 bytes of scratch per element of the padded line and wavefront.
-//   longer lines     (general weights above 2048 elements, any row above 32768) the generic kernel in backward mode
+//   2049 <= L <= 16384, general weights: one wavefront per (row, slice) in a scratch line of packed words, the weights re-read by
+//                    entry index (embed_cart_hub_w_bwd.hip: k_cart_bwd_long_w), 12 bytes of scratch per element of the padded line.
+//   longer lines     (general weights above 16384 elements, any row above 32768) the generic kernel in backward mode
 //                    (k_embed_generic, embed_generic.hip), as in the forward.
 // gfreq: the register class sums a workgroup's partials in LDS, the wavefront class across the wavefront; one float atomic per
 // (workgroup resp. wavefront, frequency).
@@ -427,6 +429,8 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
   if (rc) return rc;
   // unit weights, 2049 .. 32768 neighbours: one wavefront per line in a scratch line (embed_cart_hub_bwd.hip)
   if (unit_fast && (rc = launch_cart_hub_bwd(c, stream))) return rc;
-  // what is left (general weights: D + 1 > 2048; unit weights: D > 32768): the generic kernel in backward mode
+  // general weights, lines of 2049 .. 16384 elements: one wavefront per line in a scratch line (embed_cart_hub_w_bwd.hip)
+  if (!unit_fast && (rc = launch_cart_hub_w_bwd(c, stream))) return rc;
+  // what is left (general weights: D + 1 > 16384; unit weights: D > 32768): the generic kernel in backward mode
   return launch_cart_long_rows(c, extra, unit_fast, stream);
 }

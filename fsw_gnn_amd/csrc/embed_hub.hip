@@ -649,35 +649,6 @@ static int launch_rowlines(const fsw_embed_args& a, int bin, int64_t rows_upper,
 // the unit kernels.  Readout as in k_embed_wsort: float64 cumulative weight (lane sum -> wave scan -> wavefront offsets), phase
 // reduced in float64, sine in float32, coefficient = difference of consecutive sines.
 
-template <int M>
-__device__ __forceinline__ void wave_exchange_w(WaveLine<M, true>& ln, float* __restrict__ xk, float* __restrict__ xw, int w, int lane,
-                                                int partner, bool mirrored, bool lower) {
-  constexpr int CAP = M * kWave;
-  int moff = w * CAP + lane;                               // the offset is laundered, not the pointers (see wave_exchange)
-  asm volatile("" : "+v"(moff));
-  float* mk = xk + moff;
-  float* mw = xw + moff;
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    mk[j * kWave] = ln.k[j];
-    mw[j * kWave] = ln.w[j];
-  }
-  __syncthreads();
-  int off = partner * CAP + (mirrored ? kWave - 1 - lane : lane);
-  asm volatile("" : "+v"(off));
-  const float* tk = xk + off;
-  const float* tw = xw + off;
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    const int jj = (mirrored ? M - 1 - j : j) * kWave;
-    const float ok = tk[jj], ow = tw[jj];
-    const bool take = lower ? (ok < ln.k[j]) : (ok > ln.k[j]);   // ties: both wavefronts keep their own element
-    ln.k[j] = take ? ok : ln.k[j];
-    ln.w[j] = take ? ow : ln.w[j];
-  }
-  __syncthreads();
-}
-
 template <int NW, int M>
 __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k_embed_hub_w(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ wgt, const int32_t* __restrict__ perm,

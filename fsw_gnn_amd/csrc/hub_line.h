@@ -1,7 +1,8 @@
 // Building blocks of the kernels that keep ONE (row, slice) line of a hub row (FSW_LDS_MAX_DEG < in-degree) in the registers of the
 // NW wavefronts of a workgroup: the striped gather of a wavefront's chunk, the register exchange between wavefronts through LDS, the
 // bitonic merge levels above one chunk and the unit-weight readout of a lane's keys.  Shared by the diagonal kernels of
-// embed_hub.hip (k_embed_hub, k_embed_hub_q4, k_embed_giant) and the Cartesian one of embed_cart_hub.hip (k_cart_hub).  gfx950.
+// embed_hub.hip (k_embed_hub, k_embed_hub_q4, k_embed_giant; general weights: k_embed_hub_w, k_embed_mergepath_w) and the Cartesian
+// ones of embed_cart_hub.hip (k_cart_hub) and embed_cart_hub_w.hip (k_cart_hub_w).  gfx950.
 #pragma once
 #include "fsw_common.h"
 #include "wave_sort.h"
@@ -36,6 +37,37 @@ __device__ __forceinline__ void wave_exchange(WaveLine<M, false>& ln, float* __r
 #pragma unroll
   for (int j = 0; j < M; ++j) ln.k[j] = minmax_by_limit(ln.k[j], theirs[(mirrored ? M - 1 - j : j) * kWave], lim);
   __syncthreads();   // everybody has read: the buffer may be overwritten by the next exchange
+}
+
+// the same exchange for a (key, weight) line through xk | xw [NW][CAP] each: the weight follows its key (embed_hub.hip: k_embed_hub_w,
+// k_embed_mergepath_w; embed_cart_hub_w.hip: k_cart_hub_w)
+template <int M>
+__device__ __forceinline__ void wave_exchange_w(WaveLine<M, true>& ln, float* __restrict__ xk, float* __restrict__ xw, int w, int lane,
+                                                int partner, bool mirrored, bool lower) {
+  constexpr int CAP = M * kWave;
+  int moff = w * CAP + lane;                               // the offset is laundered, not the pointers (see wave_exchange)
+  asm volatile("" : "+v"(moff));
+  float* mk = xk + moff;
+  float* mw = xw + moff;
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    mk[j * kWave] = ln.k[j];
+    mw[j * kWave] = ln.w[j];
+  }
+  __syncthreads();
+  int off = partner * CAP + (mirrored ? kWave - 1 - lane : lane);
+  asm volatile("" : "+v"(off));
+  const float* tk = xk + off;
+  const float* tw = xw + off;
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    const int jj = (mirrored ? M - 1 - j : j) * kWave;
+    const float ok = tk[jj], ow = tw[jj];
+    const bool take = lower ? (ok < ln.k[j]) : (ok > ln.k[j]);   // ties: both wavefronts keep their own element
+    ln.k[j] = take ? ok : ln.k[j];
+    ln.w[j] = take ? ow : ln.w[j];
+  }
+  __syncthreads();
 }
 
 // NW sorted chunks (one per wavefront, after WaveLine::sort) -> the workgroup's NW * CAP keys sorted; element (lane, j) of

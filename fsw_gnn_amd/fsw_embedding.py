@@ -961,22 +961,30 @@ class FSW_embedding(nn.Module):
 
     def _cart_scratch(self, graph, st):
         """Forward scratch: only for the rows that still run on the generic kernel (None without such rows) -- unit weights with
-        tau <= 1: the rows above 32768 neighbours; otherwise the rows of 2048 neighbours and more."""
+        tau <= 1: the rows above 32768 neighbours; otherwise the rows of 16384 neighbours and more (the third hub bin and above)."""
         unit = self._unit_fast(graph)
-        if st[_lib.STAT_MAX_DEGREE] < (_lib.HUB_MAX_DEG + 1 if unit else _lib.LDS_MAX_DEG):
+        if st[_lib.STAT_MAX_DEGREE] < (_lib.HUB_MAX_DEG + 1 if unit else _lib.CART_W_MAX_LINE):
             return None
         bsh = graph.bin_start_host[0]
-        first = _lib.NUM_BINS - 1 if unit else _lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS - 1
+        first = _lib.NUM_BINS - 1 if unit else _lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS + 2
         long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[first])
         return torch.empty(int(_lib.lib().fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
                            dtype=torch.uint8, device=graph.rowptr.device)
 
     def _cart_backward_scratch(self, graph, st, forward_scratch):
-        """Backward scratch: the forward's, unless the graph has unit-weight hub rows (2049 .. 32768 neighbours) -- their backward
-        kernel sorts every line in a scratch line; the buffer then also serves the generic kernel on the rows above 32768."""
+        """Backward scratch: the forward's, unless the graph has unit-weight hub rows (2049 .. 32768 neighbours) or general-weight
+        rows of 2048 .. 16383 neighbours -- their backward kernels sort every line in a scratch line; the buffer then also serves the
+        generic kernel on the longer rows."""
         bsh = graph.bin_start_host[0]
         hub0 = _lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS
-        if not self._unit_fast(graph) or int(bsh[_lib.NUM_BINS - 1]) == int(bsh[hub0]):
+        if not self._unit_fast(graph):
+            if st[_lib.STAT_MAX_DEGREE] < _lib.LDS_MAX_DEG:
+                return forward_scratch
+            long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[hub0 - 1])     # a row of exactly 2048 neighbours is in the last LDS bin
+            return torch.empty(int(_lib.lib().fsw_embed_cart_weighted_backward_scratch_bytes(st[_lib.STAT_MAX_DEGREE], long_rows,
+                                                                                          self.nSlices)),
+                               dtype=torch.uint8, device=graph.rowptr.device)
+        if int(bsh[_lib.NUM_BINS - 1]) == int(bsh[hub0]):
             return forward_scratch
         long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[hub0])
         return torch.empty(int(_lib.lib().fsw_embed_cart_backward_scratch_bytes(st[_lib.STAT_MAX_DEGREE], long_rows, self.nSlices)),

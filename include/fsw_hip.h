@@ -58,6 +58,7 @@ typedef void* fsw_stream_t; /* a hipStream_t (torch.cuda.current_stream().cuda_s
 #define FSW_MID_MAX_DEG_WEIGHTED 128
 #define FSW_LDS_MAX_DEG 2048
 #define FSW_HUB_MAX_DEG 32768
+#define FSW_CART_W_MAX_LINE 16384 /* Cartesian mode, general weights: longest line (D + 1 elements) of the tuned classes */
 #define FSW_BIN_MID0 (FSW_REG_MAX_DEG + 1)
 #define FSW_NUM_LDS_BINS 3
 #define FSW_BIN_LDS0 (FSW_BIN_MID0 + FSW_NUM_MID_BINS)
@@ -363,7 +364,9 @@ int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double
  *                           w == NULL and tau <= 1: rows above FSW_HUB_MAX_DEG (rows of FSW_LDS_MAX_DEG + 1 .. FSW_HUB_MAX_DEG
  *                             neighbours keep their lines in registers, csrc/embed_cart_hub.hip); scratch may be NULL when
  *                             max_degree <= FSW_HUB_MAX_DEG;
- *                           otherwise: rows of FSW_LDS_MAX_DEG neighbours and above (the pad element makes a line of D + 1);
+ *                           otherwise (w != NULL or tau > 1): rows of FSW_CART_W_MAX_LINE neighbours and above (the pad element
+ *                             makes a line of D + 1; lines of up to FSW_CART_W_MAX_LINE elements keep keys and weights in
+ *                             registers, csrc/embed_cart_hub_w.hip); scratch may be NULL when max_degree < FSW_CART_W_MAX_LINE;
  *                         fsw_embed_cart_generic_scratch_bytes(max_degree, number of those rows) bytes: 36 bytes per element of a
  *                         line of the next power of two >= max_degree + 1 and workgroup.
  *                         Rows of 1 .. FSW_REG_MAX_DEG unit-weight neighbours are stored 16 bytes at a time when F % 4 == 0,
@@ -429,10 +432,19 @@ int fsw_embed_cart_f32(const fsw_cart_args* args, fsw_stream_t stream);
  *   FSW_LDS_MAX_DEG, S) returns the recommended size (room for min(2048, rows * S) wavefronts, capped at 2 GiB; 0 when
  *   max_degree <= FSW_LDS_MAX_DEG; with rows above FSW_HUB_MAX_DEG at least what the generic kernel needs for them).  A buffer of
  *   fsw_embed_cart_generic_scratch_bytes(max_degree, rows >= 1) bytes also suffices (three lines or more).
- *   Otherwise (general weights, tau > 1): as for fsw_embed_cart_f32 -- those rows run on the generic kernel in backward mode.
+ *   Otherwise (w != NULL or tau > 1): needed as soon as max_degree >= FSW_LDS_MAX_DEG.  A row of FSW_LDS_MAX_DEG ..
+ *   FSW_CART_W_MAX_LINE - 1 neighbours is sorted by one wavefront per (row, slice) in a scratch line of 12 bytes per element of the
+ *   next power of two >= the longest line (D + 1) of its degree bin (csrc/embed_cart_hub_w_bwd.hip); as many wavefronts as the
+ *   buffer holds lines (at most 2048), at least one.  fsw_embed_cart_weighted_backward_scratch_bytes(max_degree, rows of
+ *   FSW_LDS_MAX_DEG neighbours and more, S) returns the recommended size: min(2048, rows * S) lines of
+ *   12 * pow2ceil(min(max_degree, FSW_CART_W_MAX_LINE - 1) + 1) bytes, capped at 2 GiB; 0 when max_degree < FSW_LDS_MAX_DEG; with
+ *   rows of FSW_CART_W_MAX_LINE neighbours and more (they run on the generic kernel in backward mode out of the same buffer) at
+ *   least fsw_embed_cart_generic_scratch_bytes(max_degree, rows).  A buffer of fsw_embed_cart_generic_scratch_bytes(max_degree,
+ *   rows >= 1) bytes also suffices (three lines or more) and gives bit-identical gkey.
  * The buffer must be 16-byte aligned. */
 int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* args, const float* unit_dtable, int64_t lddt, fsw_stream_t stream);
 size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S);
+size_t fsw_embed_cart_weighted_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S);
 /* FSW_conv with a Cartesian embedding, fast path (csrc/conv_fused.hip: k_conv_fused_cart): fsw_conv_fused_f32 for an embedding row
  * [mass | S runs of F outputs], K = has_mass + S F.  One workgroup per 32 rows of one in-degree: every (row, slice) line is gathered
  * from Xp and sorted once, its F outputs go to the LDS tile (never to HBM), then the tile is multiplied by W1^T and finished exactly

@@ -38,7 +38,15 @@ fsw_embed_cart_backward_scratch_bytes: a parent commit built in a copy of the tr
 host code with the scratch its generic kernel needs for every row above 2048 neighbours, so both builds can alternate on one box:
     python tools/exp_cartesian.py --hub [--workload readout,rmat] --steps 3 --warmup 1
     FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --hub --steps 3 --warmup 1
-    rocprofv3 --kernel-trace --stats -d DIR -o hub -- python tools/exp_cartesian.py --hub --workload readout --steps 1"""
+    rocprofv3 --kernel-trace --stats -d DIR -o hub -- python tools/exp_cartesian.py --hub --workload readout --steps 1
+--hub --weights uniform|random [--tau T]: the same batches with general weights -- a weight per vertex, 1 / (vertices of its graph) or
+random in (0.05, 1) -- through FSW_embedding(nSlices=16, nFreqs=16) on the readout-shaped CSR graph: lines of 2049 .. 16384 elements run
+on csrc/embed_cart_hub_w.hip / csrc/embed_cart_hub_w_bwd.hip, the batch of 24000 vertices on the generic kernel in every build
+(--weights unit --tau 3 takes the same kernels with w = NULL); and, workload pc4096, a point-cloud batch of 64 clouds x 4096 points,
+d_in 3, S = 64, F = 16, W = 'uniform', through the public forward.  A build from before these classes (no export
+fsw_embed_cart_weighted_backward_scratch_bytes) is driven with the generic kernel's scratch for every row of 2048 neighbours and more:
+    python tools/exp_cartesian.py --hub --weights uniform [--workload readout,pc4096] --steps 3 --warmup 1
+    FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --hub --weights uniform --steps 3 --warmup 1"""
 import argparse
 import os
 import sys
@@ -56,7 +64,8 @@ ap.add_argument("--slices", type=int, default=16)
 ap.add_argument("--freqs", type=int, default=16)
 ap.add_argument("--only", default="abc", help="subset of the configurations a, b, c to time")
 ap.add_argument("--train", action="store_true", help="time one training step (forward + backward) instead of the forwards")
-ap.add_argument("--workload", default="graph,pc", help="--train: subset of graph, graph_w, pc; --hub: subset of readout, rmat (default both)")
+ap.add_argument("--workload", default="graph,pc", help="--train: subset of graph, graph_w, pc; --hub: subset of readout, rmat (default both); "
+                "--hub with general weights: subset of readout, pc4096 (default both)")
 ap.add_argument("--steps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--generic", action="store_true", help="--train: the generic Cartesian kernel for forward and backward")
@@ -64,6 +73,9 @@ ap.add_argument("--conv", action="store_true", help="time the FSW_conv layer (di
 ap.add_argument("--forms", default="unfused,fused", help="--conv: forms to time, alternating over the runs (--train: diag, cart)")
 ap.add_argument("--runs", type=int, default=5, help="--conv: runs of every form")
 ap.add_argument("--hub", action="store_true", help="time the unit-weight hub rows (2049 .. 32768 neighbours), forward and training step")
+ap.add_argument("--weights", choices=("unit", "uniform", "random"), default="unit",
+                help="--hub: unit weights (the unit hub kernels), or a weight per vertex: 1 / size of its graph, or random in (0.05, 1)")
+ap.add_argument("--tau", type=float, default=1.0, help="--hub: total_mass_pad_thresh of the embedding (> 1: general-weight kernels with w = NULL)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 
@@ -168,26 +180,39 @@ def conv_leg():
 
 def hub_leg():
     from fsw_gnn_amd import FSW_readout, synth
-    has_hub = hasattr(__import__("ctypes").CDLL(_lib.LIB_PATH), "fsw_embed_cart_backward_scratch_bytes")
+    handle = __import__("ctypes").CDLL(_lib.LIB_PATH)
+    has_hub = hasattr(handle, "fsw_embed_cart_backward_scratch_bytes")
+    has_hub_w = hasattr(handle, "fsw_embed_cart_weighted_backward_scratch_bytes")
+    general = args.weights != "unit" or args.tau > 1.0
+
+    def generic_scratch(self, graph, st):
+        if st[_lib.STAT_MAX_DEGREE] < _lib.LDS_MAX_DEG:
+            return None
+        bsh = graph.bin_start_host[0]
+        long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[_lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS - 1])
+        return torch.empty(int(_lib.lib().fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
+                           dtype=torch.uint8, device=graph.rowptr.device)
+
+    if not has_hub_w:
+        # a build from before the general-weight classes: no such export, and every general-weight row of 2048 neighbours and more runs
+        # on the generic kernel, which needs its scratch in both directions
+        del _lib._SIGNATURES["fsw_embed_cart_weighted_backward_scratch_bytes"]
+        tuned_scratch, tuned_backward_scratch = FSW_embedding._cart_scratch, FSW_embedding._cart_backward_scratch
+        FSW_embedding._cart_scratch = lambda self, graph, st: (
+            tuned_scratch(self, graph, st) if self._unit_fast(graph) else generic_scratch(self, graph, st))
+        FSW_embedding._cart_backward_scratch = lambda self, graph, st, forward_scratch: (
+            tuned_backward_scratch(self, graph, st, forward_scratch) if self._unit_fast(graph) else forward_scratch)
     if not has_hub:
-        # a build from before the hub kernels: no such export, and every row above 2048 neighbours runs on the generic kernel, which
-        # needs its scratch in both directions
+        # a build from before the hub kernels: the same for the unit-weight rows above 2048 neighbours
         del _lib._SIGNATURES["fsw_embed_cart_backward_scratch_bytes"]
-
-        def generic_scratch(self, graph, st):
-            if st[_lib.STAT_MAX_DEGREE] < _lib.LDS_MAX_DEG:
-                return None
-            bsh = graph.bin_start_host[0]
-            long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[_lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS - 1])
-            return torch.empty(int(_lib.lib().fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
-                               dtype=torch.uint8, device=graph.rowptr.device)
-
         FSW_embedding._cart_scratch = generic_scratch
         FSW_embedding._cart_backward_scratch = lambda self, graph, st, forward_scratch: forward_scratch
-    print("library %s: %s" % (_lib.LIB_PATH, "hub kernels" if has_hub else "generic kernel on the rows above 2048 neighbours"), flush=True)
+    print("library %s: %s" % (_lib.LIB_PATH, ("general-weight hub kernels" if has_hub_w else "generic kernel on the general-weight rows of "
+                                              "2048 neighbours and more") if general else
+                              ("hub kernels" if has_hub else "generic kernel on the rows above 2048 neighbours")), flush=True)
     S, F = args.slices, args.freqs
     steps, warmup = args.steps, args.warmup
-    workload = "readout,rmat" if args.workload == ap.get_default("workload") else args.workload
+    workload = ("readout,pc4096" if general else "readout,rmat") if args.workload == ap.get_default("workload") else args.workload
 
     def time_pair(name, forward, step):
         with torch.no_grad():
@@ -198,12 +223,15 @@ def hub_leg():
             step()
         print("%-44s forward %10.3f ms   training step %10.3f ms" % (name, fwd, bench.timed_ms(step, steps, dev)), flush=True)
 
+    batches = [("2049..4096", [2500] * 8), ("4097..8192", [6000] * 8), ("8193..16384", [12000] * 8), ("16385..32768", [24000] * 8),
+               ("mixed", [2500, 5000, 9000, 12000, 16000, 20000, 25000, 30000])]
+    if general:
+        weighted_workloads(workload, batches, time_pair)
+        return
     if "readout" in workload:
         in_ch, out_ch = 32, 32
         torch.manual_seed(7)
         layer = FSW_readout(in_ch, out_ch, embed_slices=S, embed_freqs=F, learnable_embedding=True, device=dev)
-        batches = [("2049..4096", [2500] * 8), ("4097..8192", [6000] * 8), ("8193..16384", [12000] * 8), ("16385..32768", [24000] * 8),
-                   ("mixed", [2500, 5000, 9000, 12000, 16000, 20000, 25000, 30000])]
         for name, sizes in batches:
             gi = torch.cat([torch.full((m,), g, dtype=torch.int64) for g, m in enumerate(sizes)]).to(dev)
             x = torch.randn((gi.numel(), in_ch), device=dev)
@@ -241,6 +269,55 @@ def hub_leg():
             mod.embed_cartesian_autograd(xg, graph).backward(G)
 
         time_pair("embedding S=%d F=%d, RMAT-%d" % (S, F, scale), lambda: mod.embed_cartesian_into(x, graph, out), step)
+
+
+def weighted_workloads(workload, batches, time_pair):
+    """--hub with general weights: the readout batches as CSR graphs with a weight per vertex (or w = NULL and tau > 1) through
+    FSW_embedding, and the batch of 4096-point clouds through the public forward."""
+    S, F = args.slices, args.freqs
+    if "readout" in workload:
+        d = 32
+        torch.manual_seed(7)
+        mod = FSW_embedding(d_in=d, nSlices=S, nFreqs=F, collapse_freqs=True, enable_bias=False, learnable_slices=True,
+                            learnable_freqs=True, freqs_init='spread', total_mass_pad_thresh=args.tau, device=dev)
+        for name, sizes in batches:
+            gi = torch.cat([torch.full((m,), g, dtype=torch.int64) for g, m in enumerate(sizes)]).to(dev)
+            nv = gi.numel()
+            if args.weights == "uniform":
+                w = (1.0 / torch.tensor(sizes, dtype=torch.float32, device=dev))[gi].contiguous()
+            elif args.weights == "random":
+                w = (0.05 + 0.95 * torch.rand(nv, generator=torch.Generator().manual_seed(8))).to(dev)
+            else:
+                w = None
+            graph = build_csr(gi.contiguous(), torch.arange(nv, device=dev), w, len(sizes), nv)
+            graph.read_stats()
+            x = torch.randn((nv, d), device=dev)
+            xg = x.clone().requires_grad_(True)
+            out = torch.empty((len(sizes), S * F), device=dev)
+            G = torch.randn((len(sizes), S * F), device=dev)
+
+            def step():
+                mod.zero_grad(set_to_none=True)
+                xg.grad = None
+                mod.embed_cartesian_autograd(xg, graph).backward(G)
+
+            time_pair("embedding S=%d F=%d, %s weights tau %g, 8 graphs, %s" % (S, F, args.weights, args.tau, name),
+                      lambda: mod.embed_cartesian_into(x, graph, out), step)
+    if "pc4096" in workload:
+        B, npts, Spc, Fpc = 64, 4096, 64, 16
+        torch.manual_seed(7)
+        pc = FSW_embedding(d_in=3, nSlices=Spc, nFreqs=Fpc, collapse_freqs=True, enable_bias=False, learnable_slices=True,
+                           learnable_freqs=True, freqs_init='spread', device=dev)
+        X = torch.randn((B, npts, 3), device=dev)
+        Xg = X.clone().requires_grad_(True)
+        G = torch.randn((B, Spc * Fpc), device=dev)
+
+        def step_pc():
+            pc.zero_grad(set_to_none=True)
+            Xg.grad = None
+            pc(Xg, 'uniform').backward(G)
+
+        time_pair("point clouds %d x %d, d_in 3, S=%d F=%d, W='uniform'" % (B, npts, Spc, Fpc), lambda: pc(X, 'uniform'), step_pc)
 
 
 if args.hub:
