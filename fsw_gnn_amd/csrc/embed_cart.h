@@ -9,6 +9,8 @@ namespace fsw {
 
 constexpr int kCartRows = 64;                                 // rows per workgroup tile of the register path
 constexpr int kCartMaxLine = 2048;                            // longest line of the wavefront path
+constexpr int kCartLongM = kCartMaxLine / kWave;              // longer lines: elements per lane of a wavefront's chunk of kCartMaxLine
+constexpr int kFB = 16;                                       // longer lines, forward: frequencies per synchronisation of the readout
 
 // Read-only inputs at wave-uniform addresses (coefficient table, frequencies) are read through the constant address space: the
 // compiler then issues scalar loads (s_load_dwordx4).  Through a generic pointer it must assume that the output stores may alias
@@ -29,7 +31,15 @@ __device__ __forceinline__ ConstAS<T>* as_const(const T* p) { return (ConstAS<T>
 
 // embed_cart.hip
 int cart_check_common(const fsw_cart_args* c);                // the checks every Cartesian entry point starts with
-int bin_upper_degree(int b);                                  // largest in-degree of degree bin b
+
+// largest in-degree of degree bin b (include/fsw_hip.h; the last bin has none)
+constexpr int bin_upper_degree(int b) {
+  constexpr int sizes[FSW_NUM_MID_BINS] = FSW_MID_SIZES;
+  if (b <= FSW_REG_MAX_DEG) return b;
+  if (b < FSW_BIN_LDS0) return sizes[b - FSW_BIN_MID0];
+  if (b < FSW_BIN_GLOBAL) return 512 << (b - FSW_BIN_LDS0);     // the LDS bins and the hub bins double from 512
+  return 1 << 30;
+}
 
 // The degree bins of 33 .. 2048 neighbours (bin_start_host bs) in groups of consecutive bins whose lines (extra = 1: + the pad
 // element of general weights) need the same number Mb of keys per lane of a wavefront: fn(Mb, p0, rows) for the rows
@@ -47,25 +57,100 @@ int for_each_wave_group(const int32_t* bs, int extra, Fn fn) {
   return 0;
 }
 
-// embed_cart_hub.hip / embed_cart_hub_bwd.hip: unit weights with tau <= 1, the rows of the hub bins (FSW_LDS_MAX_DEG < D <= FSW_HUB_MAX_DEG)
-int launch_cart_hub(const fsw_cart_args* c, hipStream_t stream);        // forward, no scratch
-int launch_cart_hub_bwd(const fsw_cart_args* c, hipStream_t stream);    // backward, c->scratch: fsw_embed_cart_backward_scratch_bytes
+// ---- the classes of the rows whose line is longer than kCartMaxLine elements: THE table (DESIGN.md prints it too) ---------------
+// Everything that decides which rows a class takes reads it: the four launchers of embed_cart_hub*.hip, launch_cart_long_rows and
+// the scratch sizes (fsw_embed_cart_scratch_bytes, which the host layer calls).
+struct CartLongClass {
+  int bin_lo, bin_hi;   // the degree bins its rows lie in
+  int dlo, dhi;         // its rows: dlo < D <= dhi
+  int nw;               // forward: one workgroup of nw wavefronts keeps the line in registers, kCartMaxLine elements per wavefront
+  bool bwd_line;        // backward: one wavefront per line in a scratch line of cart_line_elems(longest such row of the bin) elements
+};
+struct CartLongMode {
+  int pad;              // elements of a line next to the D neighbours: the pad element of general weights
+  int num;              // classes
+  CartLongClass cls[FSW_NUM_HUB_BINS];
+  int generic_bin, generic_min_degree;   // rows of generic_min_degree neighbours and more (they begin in generic_bin): the generic kernel
+  constexpr const CartLongClass& last() const { return cls[num - 1]; }
+};
+constexpr int kCartLastLdsBin = FSW_BIN_HUB0 - 1;             // rows of 1025 .. FSW_LDS_MAX_DEG neighbours
+constexpr CartLongMode kCartLong[2] = {
+    // unit weights (w == NULL and tau <= 1): lines of D keys, one class per hub bin
+    {0, 4,
+     {{FSW_BIN_HUB0, FSW_BIN_HUB0, 2048, 4096, 2, true},
+      {FSW_BIN_HUB0 + 1, FSW_BIN_HUB0 + 1, 4096, 8192, 4, true},
+      {FSW_BIN_HUB0 + 2, FSW_BIN_HUB0 + 2, 8192, 16384, 8, true},
+      {FSW_BIN_HUB0 + 3, FSW_BIN_HUB0 + 3, 16384, 32768, 16, true}},
+     FSW_BIN_GLOBAL, 32769},
+    // general weights (w != NULL or tau > 1): lines of D + 1 elements, so every class ends one neighbour below a bin's end
+    {1, 3,
+     {{kCartLastLdsBin, FSW_BIN_HUB0, 2047, 4095, 2, true},
+      {FSW_BIN_HUB0, FSW_BIN_HUB0 + 1, 4095, 8191, 4, true},
+      {FSW_BIN_HUB0 + 1, FSW_BIN_HUB0 + 2, 8191, 16383, 8, true}},
+     FSW_BIN_HUB0 + 2, 16384},
+};
+constexpr const CartLongMode& cart_long_mode(bool unit_fast) { return kCartLong[unit_fast ? 0 : 1]; }
+inline bool cart_unit_fast(const fsw_cart_args* c) { return c->w == nullptr && c->tau <= 1.0; }
 
-// embed_cart_hub_w.hip / embed_cart_hub_w_bwd.hip: general weights (w != NULL or tau > 1), the lines of kCartMaxLine + 1 ..
-// FSW_CART_W_MAX_LINE elements (FSW_LDS_MAX_DEG <= D < FSW_CART_W_MAX_LINE: the last LDS bin and the first three hub bins)
-int launch_cart_hub_w(const fsw_cart_args* c, hipStream_t stream);      // forward, no scratch
-int launch_cart_hub_w_bwd(const fsw_cart_args* c, hipStream_t stream);  // backward, c->scratch: fsw_embed_cart_weighted_backward_scratch_bytes
+constexpr bool cart_long_table_ok(const CartLongMode& m, int max_line) {
+  if (m.cls[0].dlo + m.pad != kCartMaxLine || m.last().dhi + m.pad != max_line) return false;   // from the wavefront path to max_line
+  if (m.generic_min_degree != m.last().dhi + 1) return false;
+  if (bin_upper_degree(m.generic_bin - 1) >= m.generic_min_degree || m.generic_min_degree > bin_upper_degree(m.generic_bin)) return false;
+  for (int i = 0; i < m.num; ++i) {
+    const CartLongClass& k = m.cls[i];
+    if (k.nw != 2 << i || (i > 0 && k.dlo != m.cls[i - 1].dhi)) return false;                   // the launchers index by i
+    if (k.dhi + m.pad != k.nw * kCartMaxLine) return false;                                    // the longest line fills the registers
+    if (bin_upper_degree(k.bin_lo - 1) > k.dlo || k.dlo >= bin_upper_degree(k.bin_lo)) return false;    // D = dlo + 1 is in bin_lo
+    if (bin_upper_degree(k.bin_hi - 1) >= k.dhi || k.dhi > bin_upper_degree(k.bin_hi)) return false;    // D = dhi is in bin_hi
+  }
+  return true;
+}
+static_assert(kCartMaxLine == FSW_LDS_MAX_DEG && bin_upper_degree(FSW_BIN_GLOBAL - 1) == FSW_HUB_MAX_DEG, "the bins of include/fsw_hip.h");
+static_assert(cart_long_table_ok(kCartLong[0], FSW_HUB_MAX_DEG), "unit weights: the classes tile FSW_LDS_MAX_DEG < D <= FSW_HUB_MAX_DEG");
+static_assert(cart_long_table_ok(kCartLong[1], FSW_CART_W_MAX_LINE), "general weights: the classes tile the lines up to FSW_CART_W_MAX_LINE");
 
-// Lines the tuned classes do not take (float32 storage): the generic kernel, forward or, with c->g, backward.  unit_fast == false
-// (general weights; extra = 1, the pad element): the lines above FSW_CART_W_MAX_LINE elements, on the rows of the third hub bin (which
-// holds D = FSW_CART_W_MAX_LINE) and above; unit_fast == true (unit weights with tau <= 1; extra = 0): only the rows of FSW_BIN_GLOBAL.
-inline int launch_cart_long_rows(const fsw_cart_args* c, int extra, bool unit_fast, hipStream_t stream) {
-  const int min_long = unit_fast ? FSW_HUB_MAX_DEG + 1 : FSW_CART_W_MAX_LINE + 1 - extra;
+// elements of the backward's scratch line for rows of up to `degree` neighbours
+inline int64_t cart_line_elems(const CartLongMode& m, int64_t degree) { return (int64_t)pow2ceil((uint32_t)(degree + m.pad)); }
+constexpr int kCartLineBytes = 12;                            // per element: the packed (key, index) word and the key gradient
+constexpr int kCartLineMaxWaves = 2048;                       // resident wavefronts (one scratch line each) a launch uses at most
+
+// forward grid: virtual blocks = (rows rounded up to 8) x slices (hub_line.h: hub_virtual_line), capped at 2^20 workgroups that stride
+inline unsigned cart_hub_grid(int64_t rows, int S) { return (unsigned)std::min<int64_t>(ceil_div(rows, 8) * S * 8, 1ll << 20); }
+
+// backward of the classes with bwd_line: fn(bin, line_elems, nwaves) launches a populated bin that can hold a row of them -- the scratch
+// line sized by the bin's own longest such row, as many wavefronts as c->scratch holds lines (<= kCartLineMaxWaves, <= lines), >= 1
+template <class Fn>
+int for_each_cart_line_bin(const fsw_cart_args* c, const CartLongMode& m, Fn fn) {
   const int32_t* bs = c->bin_start_host;
-  const int p0 = unit_fast ? bs[FSW_BIN_GLOBAL] : bs[FSW_BIN_HUB0 + 2];
-  const int64_t rows = (int64_t)bs[FSW_NUM_BINS] - p0;
-  if (c->max_degree < min_long || rows <= 0) return 0;
-  return launch_embed_generic(generic_args(*c, true, c->F), 0, c->perm + p0, rows, min_long, stream);
+  int done = -1;                                              // the last bin launched: consecutive classes may share one
+  for (int i = 0; i < m.num; ++i) {
+    if (!m.cls[i].bwd_line) continue;
+    for (int bin = std::max(m.cls[i].bin_lo, done + 1); bin <= m.cls[i].bin_hi; done = bin++) {
+      const int64_t rows = (int64_t)bs[bin + 1] - bs[bin];
+      const int64_t bin_max = std::min<int64_t>({c->max_degree, bin_upper_degree(bin), m.last().dhi});
+      if (rows <= 0 || bin_max <= m.cls[i].dlo) continue;
+      FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0,
+                  "fsw_embed_cart_backward_keys_f32: rows of the long classes need a 16-byte aligned scratch buffer (fsw_embed_cart_scratch_bytes)");
+      const int64_t line_elems = cart_line_elems(m, bin_max);
+      const int64_t nwaves = std::min<int64_t>({(int64_t)(c->scratch_bytes / ((size_t)line_elems * kCartLineBytes)), kCartLineMaxWaves, rows * c->S});
+      FSW_REQUIRE(nwaves >= 1, "fsw_embed_cart_backward_keys_f32: scratch buffer too small (need fsw_embed_cart_scratch_bytes)");
+      fn(bin, line_elems, (int)nwaves);
+      FSW_LAUNCH_CHECK();
+    }
+  }
+  return 0;
+}
+
+// embed_cart_hub*.hip: the classes of kCartLong[0] (launch_cart_hub*) and of kCartLong[1] (launch_cart_hub_w*); the forward needs no scratch
+int launch_cart_hub(const fsw_cart_args* c, hipStream_t stream), launch_cart_hub_bwd(const fsw_cart_args* c, hipStream_t stream);
+int launch_cart_hub_w(const fsw_cart_args* c, hipStream_t stream), launch_cart_hub_w_bwd(const fsw_cart_args* c, hipStream_t stream);
+
+// Rows the classes do not take (float32 storage): the generic kernel, forward or, with c->g, backward.
+inline int launch_cart_long_rows(const fsw_cart_args* c, const CartLongMode& m, hipStream_t stream) {
+  const int p0 = c->bin_start_host[m.generic_bin];
+  const int64_t rows = (int64_t)c->bin_start_host[FSW_NUM_BINS] - p0;
+  if (c->max_degree < m.generic_min_degree || rows <= 0) return 0;
+  return launch_embed_generic(generic_args(*c, true, c->F), 0, c->perm + p0, rows, m.generic_min_degree, stream);
 }
 
 }  // namespace fsw

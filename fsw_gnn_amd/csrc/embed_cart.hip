@@ -279,14 +279,6 @@ int launch_cart_wave(const CartTuned& t, bool weighted, int p0, int rows, int S,
 
 }  // namespace
 
-int bin_upper_degree(int b) {
-  constexpr int sizes[FSW_NUM_MID_BINS] = FSW_MID_SIZES;
-  if (b <= FSW_REG_MAX_DEG) return b;
-  if (b < FSW_BIN_LDS0) return sizes[b - FSW_BIN_MID0];
-  if (b < FSW_BIN_HUB0) return 512 << (b - FSW_BIN_LDS0);
-  return 1 << 30;
-}
-
 int cart_check_common(const fsw_cart_args* c) {
   FSW_REQUIRE(c, "fsw_embed_cart: null args");
   FSW_REQUIRE(c->rowptr && c->Xp && c->freqs && (c->num_rows == 0 || c->col || c->max_degree == 0), "fsw_embed_cart: null pointer");
@@ -301,6 +293,46 @@ int cart_check_common(const fsw_cart_args* c) {
 }  // namespace fsw
 
 using namespace fsw;
+
+// a buffer for `lines` scratch lines: at most kCartLineMaxWaves of them and 2 GiB (fewer wavefronts then share the work), at least one
+static size_t cart_line_buffer_bytes(int64_t line_elems, int64_t lines) {
+  const size_t line_bytes = (size_t)line_elems * kCartLineBytes;
+  const size_t cap = (size_t)2 << 30;                            // as embed_global_scratch_bytes
+  const size_t waves = std::min<size_t>((size_t)std::min<int64_t>(lines, kCartLineMaxWaves), cap / line_bytes);
+  return std::max<size_t>(waves, 1) * line_bytes;
+}
+
+// the backward's scratch for a longest row of max_degree neighbours and long_rows rows from the first class on
+static size_t cart_backward_scratch_bytes(const CartLongMode& m, int64_t max_degree, int64_t long_rows, int32_t S) {
+  if (max_degree <= m.cls[0].dlo) return 0;
+  const int64_t rows = std::max<int64_t>(long_rows, 1);
+  size_t bytes = cart_line_buffer_bytes(cart_line_elems(m, std::min<int64_t>(max_degree, m.last().dhi)), rows * std::max<int32_t>(S, 1));
+  // the rows beyond the classes run on the generic kernel out of the same buffer
+  if (max_degree >= m.generic_min_degree) bytes = std::max(bytes, fsw_embed_cart_generic_scratch_bytes(max_degree, rows));
+  return bytes;
+}
+
+extern "C" size_t fsw_embed_cart_scratch_bytes(const fsw_cart_args* c, int backward) {
+  if (!c || !c->bin_start_host) return 0;
+  const CartLongMode& m = cart_long_mode(cart_unit_fast(c));
+  const int32_t* bs = c->bin_start_host;
+  // forward: only the rows that run on the generic kernel need scratch
+  const int64_t generic_rows = (int64_t)bs[FSW_NUM_BINS] - bs[m.generic_bin];
+  const size_t forward = c->max_degree < m.generic_min_degree
+                             ? 0 : fsw_embed_cart_generic_scratch_bytes(c->max_degree, std::max<int64_t>(generic_rows, 1));
+  if (!backward) return forward;
+  // unit weights without a row in the class bins: the backward runs the same kernels as the forward, out of the forward's buffer
+  if (m.pad == 0 && bs[m.last().bin_hi + 1] == bs[m.cls[0].bin_lo]) return forward;
+  return cart_backward_scratch_bytes(m, c->max_degree, (int64_t)bs[FSW_NUM_BINS] - bs[m.cls[0].bin_lo], c->S);
+}
+
+extern "C" size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S) {
+  return cart_backward_scratch_bytes(kCartLong[0], max_degree, long_rows, S);
+}
+
+extern "C" size_t fsw_embed_cart_weighted_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S) {
+  return cart_backward_scratch_bytes(kCartLong[1], max_degree, long_rows, S);
+}
 
 extern "C" int fsw_embed_cart_generic(const fsw_cart_args* c, fsw_stream_t stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -324,7 +356,7 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   FSW_REQUIRE(c->value_dtype == 0 && !c->g, "fsw_embed_cart_f32: float32 forward only (fsw_embed_cart_generic for the rest)");
   FSW_REQUIRE(c->perm && c->bin_start && c->bin_start_host, "fsw_embed_cart_f32: needs perm, bin_start and its host copy");
   FSW_REQUIRE(c->out && c->ldo >= (int64_t)c->has_mass + (int64_t)c->S * c->F, "fsw_embed_cart_f32: bad output");
-  const bool unit_fast = c->w == nullptr && c->tau <= 1.0;
+  const bool unit_fast = cart_unit_fast(c);
   FSW_REQUIRE(!unit_fast || (c->unit_table && c->ldt >= c->F), "fsw_embed_cart_f32: unit weights with tau <= 1 need unit_table");
   if (c->num_rows == 0) return 0;
   const int32_t* bs = c->bin_start_host;
@@ -367,10 +399,8 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
     }
   });
   if (rc) return rc;
-  // unit weights, 2049 .. 32768 neighbours: one workgroup of 2 .. 16 wavefronts per line (embed_cart_hub.hip)
-  if (unit_fast && (rc = launch_cart_hub(c, stream))) return rc;
-  // general weights, lines of 2049 .. 16384 elements: one workgroup of 2, 4 or 8 wavefronts per line (embed_cart_hub_w.hip)
-  if (!unit_fast && (rc = launch_cart_hub_w(c, stream))) return rc;
-  // what is left (general weights: D + 1 > 16384; unit weights: D > 32768): the generic kernel
-  return launch_cart_long_rows(c, extra, unit_fast, stream);
+  // lines above kCartMaxLine elements (the classes of embed_cart.h: kCartLong): one workgroup of 2 .. 16 wavefronts per line
+  if ((rc = unit_fast ? launch_cart_hub(c, stream) : launch_cart_hub_w(c, stream))) return rc;
+  // what is left: the generic kernel
+  return launch_cart_long_rows(c, cart_long_mode(unit_fast), stream);
 }

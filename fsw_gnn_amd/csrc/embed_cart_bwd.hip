@@ -390,7 +390,7 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
   FSW_REQUIRE(c->perm && c->bin_start && c->bin_start_host, "fsw_embed_cart_backward_keys_f32: needs perm, bin_start and its host copy");
   FSW_REQUIRE(c->ldg >= (int64_t)c->has_mass + (int64_t)c->S * c->F && c->ldk >= c->S,
               "fsw_embed_cart_backward_keys_f32: bad gradient strides");
-  const bool unit_fast = c->w == nullptr && c->tau <= 1.0;
+  const bool unit_fast = cart_unit_fast(c);
   FSW_REQUIRE(!unit_fast || (c->unit_table && c->ldt >= c->F && unit_dtable && lddt >= c->F),
               "fsw_embed_cart_backward_keys_f32: unit weights with tau <= 1 need unit_table and unit_dtable");
   if (c->num_rows == 0) return 0;
@@ -427,10 +427,8 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
     }
   });
   if (rc) return rc;
-  // unit weights, 2049 .. 32768 neighbours: one wavefront per line in a scratch line (embed_cart_hub_bwd.hip)
-  if (unit_fast && (rc = launch_cart_hub_bwd(c, stream))) return rc;
-  // general weights, lines of 2049 .. 16384 elements: one wavefront per line in a scratch line (embed_cart_hub_w_bwd.hip)
-  if (!unit_fast && (rc = launch_cart_hub_w_bwd(c, stream))) return rc;
-  // what is left (general weights: D + 1 > 16384; unit weights: D > 32768): the generic kernel in backward mode
-  return launch_cart_long_rows(c, extra, unit_fast, stream);
+  // lines above kCartMaxLine elements (the classes of embed_cart.h: kCartLong): one wavefront per line in a scratch line
+  if ((rc = unit_fast ? launch_cart_hub_bwd(c, stream) : launch_cart_hub_w_bwd(c, stream))) return rc;
+  // what is left: the generic kernel in backward mode
+  return launch_cart_long_rows(c, cart_long_mode(unit_fast), stream);
 }

@@ -2,7 +2,7 @@
 //
 // The line-in-registers structure of the diagonal hub kernels (embed_hub.hip, building blocks in hub_line.h): one workgroup of
 // NW = 2, 4, 8 or 16 wavefronts takes ONE (recipient row, slice) line of up to NW * 2048 keys, wavefront w holds elements
-// w * 2048 .. w * 2048 + 2047 (32 per lane), every wavefront gathers and sorts its chunk and the merge levels above one chunk
+// w * 2048 .. (w + 1) * 2048 - 1 (32 per lane), every wavefront gathers and sorts its chunk and the merge levels above one chunk
 // exchange registers through LDS.  The sort is paid once per slice; the sorted registers are then read out at all F frequencies
 // (unit_readout: one float64 FMA per key and frequency).  The F sums of a line are reduced over the workgroup in batches of kFB
 // frequencies per barrier: every wavefront drops its kFB wave sums into an LDS table, ONE barrier, then lane f of the batch adds
@@ -19,9 +19,6 @@
 namespace fsw {
 
 namespace {
-
-constexpr int kCartHubM = 32;     // keys per lane
-constexpr int kFB = 16;           // frequencies per synchronisation of the readout
 
 struct CartHub {
   const int32_t* rowptr;
@@ -49,14 +46,9 @@ __global__ void __launch_bounds__(NW* kWave, 4) k_cart_hub(const CartHub a, int 
   const int pbeg = a.bin_start[bin], nrows = a.bin_start[bin + 1] - pbeg;
   const int lane = lane_id(), w = wave_id();
   const int S = a.S, F = a.F;
-  // virtual block -> (row, slice) as in k_embed_hub: the blocks b, b + 8, b + 16, ... (one XCD under round-robin dispatch) take the
-  // slices 0 .. S - 1 of row xcd, then of row xcd + 8, ...; the grid is capped, a multiple of 8, and strides over the virtual blocks
   const int xcd = blockIdx.x & 7;
   for (int64_t vb = blockIdx.x;; vb += gridDim.x) {
-    const int64_t i = vb >> 3;
-    const int64_t rl = i / S;
-    const int s = (int)(i - rl * S);
-    const int64_t r = rl * 8 + xcd;
+    const auto [r, s] = hub_virtual_line(vb, xcd, 1, S);
     if (r >= nrows) return;                 // the whole workgroup leaves
     const int node = a.perm[pbeg + r];
     const int start = a.rowptr[node];
@@ -92,19 +84,15 @@ __global__ void __launch_bounds__(NW* kWave, 4) k_cart_hub(const CartHub a, int 
 }
 
 template <int NW>
-int launch_cart_hub_bin(const CartHub& t, int bin, int64_t rows, hipStream_t stream) {
-  if (rows <= 0) return 0;
-  // virtual blocks = (rows rounded up to 8) x slices; the launched grid is capped at 2^20 workgroups and strides
-  const int64_t nvirtual = ceil_div(rows, 8) * t.S * 8;
-  const int64_t nblocks = std::min<int64_t>(nvirtual, 1ll << 20);
-  k_cart_hub<NW, kCartHubM><<<(unsigned)nblocks, NW * kWave, 0, stream>>>(t, bin);
+int launch_cart_hub_class(const CartHub& t, const CartLongClass& k, int64_t rows, hipStream_t stream) {
+  k_cart_hub<NW, kCartLongM><<<cart_hub_grid(rows, t.S), NW * kWave, 0, stream>>>(t, k.bin_lo);
   FSW_LAUNCH_CHECK();
   return 0;
 }
 
 }  // namespace
 
-// unit weights with tau <= 1: the rows of the four hub bins, one launch per populated bin (bin FSW_BIN_HUB0 + i: NW = 2 << i)
+// unit weights with tau <= 1: one launch per populated class of kCartLong[0] (one hub bin each)
 int launch_cart_hub(const fsw_cart_args* c, hipStream_t stream) {
   const int32_t* bs = c->bin_start_host;
   CartHub t;
@@ -112,11 +100,15 @@ int launch_cart_hub(const fsw_cart_args* c, hipStream_t stream) {
   t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F;
   t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
   t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
-  int rc;
-  if ((rc = launch_cart_hub_bin<2>(t, FSW_BIN_HUB0, (int64_t)bs[FSW_BIN_HUB0 + 1] - bs[FSW_BIN_HUB0], stream))) return rc;
-  if ((rc = launch_cart_hub_bin<4>(t, FSW_BIN_HUB0 + 1, (int64_t)bs[FSW_BIN_HUB0 + 2] - bs[FSW_BIN_HUB0 + 1], stream))) return rc;
-  if ((rc = launch_cart_hub_bin<8>(t, FSW_BIN_HUB0 + 2, (int64_t)bs[FSW_BIN_HUB0 + 3] - bs[FSW_BIN_HUB0 + 2], stream))) return rc;
-  return launch_cart_hub_bin<16>(t, FSW_BIN_HUB0 + 3, (int64_t)bs[FSW_BIN_HUB0 + 4] - bs[FSW_BIN_HUB0 + 3], stream);
+  constexpr decltype(&launch_cart_hub_class<2>) launch[] = {launch_cart_hub_class<2>, launch_cart_hub_class<4>, launch_cart_hub_class<8>,
+                                                            launch_cart_hub_class<16>};   // class i: 2 << i wavefronts
+  const CartLongMode& m = kCartLong[0];
+  for (int i = 0; i < m.num; ++i) {
+    const int64_t rows = (int64_t)bs[m.cls[i].bin_hi + 1] - bs[m.cls[i].bin_lo];
+    if (rows <= 0) continue;
+    if (const int rc = launch[i](t, m.cls[i], rows, stream)) return rc;
+  }
+  return 0;
 }
 
 }  // namespace fsw

@@ -23,10 +23,6 @@ namespace fsw {
 
 namespace {
 
-constexpr int kLongM = 32;                     // words per lane of a chunk
-constexpr int kLongCap = kLongM * kWave;       // 2048
-constexpr int kLongMaxWaves = 2048;            // resident wavefronts a launch uses at most
-
 struct CartBwdLong {
   const int32_t* rowptr;
   const int32_t* col;
@@ -47,11 +43,11 @@ struct CartBwdLong {
 
 __global__ void __launch_bounds__(256) k_cart_bwd_long(const CartBwdLong a, int bin, char* __restrict__ scratch, int64_t line_elems,
                                                        int nwaves) {
-  constexpr int M = kLongM, CAP = kLongCap;
+  constexpr int M = kCartLongM, CAP = kCartMaxLine;
   const int lane = lane_id();
   const int gw = blockIdx.x * 4 + wave_id();
   if (gw >= nwaves) return;                                      // the wavefronts never synchronise with each other
-  unsigned long long* se = reinterpret_cast<unsigned long long*>(scratch + (int64_t)gw * line_elems * 12);   // packed (key, index) words
+  unsigned long long* se = reinterpret_cast<unsigned long long*>(scratch + (int64_t)gw * line_elems * kCartLineBytes);   // packed (key, index) words
   float* sc = reinterpret_cast<float*>(se + line_elems);                                                     // key gradients, entry order
   const int pbeg = a.bin_start[bin], pend = a.bin_start[bin + 1];
   const int S = a.S, F = a.F;
@@ -156,52 +152,18 @@ __global__ void __launch_bounds__(256) k_cart_bwd_long(const CartBwdLong a, int 
   }
 }
 
-// bytes of one wavefront's scratch line for rows of up to `degree` neighbours
-size_t long_line_bytes(int64_t degree) { return (size_t)pow2ceil((uint32_t)degree) * 12; }
-
 }  // namespace
 
-// unit weights with tau <= 1: the rows of the four hub bins, one launch per populated bin, the scratch line sized by the bin's own
-// longest row; as many wavefronts as the buffer holds lines (at most kLongMaxWaves), at least one
+// unit weights with tau <= 1: the classes of kCartLong[0], one launch per populated hub bin (embed_cart.h: for_each_cart_line_bin)
 int launch_cart_hub_bwd(const fsw_cart_args* c, hipStream_t stream) {
-  const int32_t* bs = c->bin_start_host;
-  if ((int64_t)bs[FSW_BIN_GLOBAL] - bs[FSW_BIN_HUB0] <= 0) return 0;
-  FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0,
-              "fsw_embed_cart_backward_keys_f32: rows above FSW_LDS_MAX_DEG need a 16-byte aligned scratch buffer "
-              "(fsw_embed_cart_backward_scratch_bytes)");
   CartBwdLong t;
   t.rowptr = c->rowptr; t.col = c->col; t.perm = c->perm; t.bin_start = c->bin_start;
   t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F;
   t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
   t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
-  for (int i = 0; i < FSW_NUM_HUB_BINS; ++i) {
-    const int bin = FSW_BIN_HUB0 + i;
-    const int64_t rows = (int64_t)bs[bin + 1] - bs[bin];
-    if (rows <= 0) continue;
-    const int64_t bin_max = std::min<int64_t>(std::max<int64_t>(c->max_degree, FSW_LDS_MAX_DEG + 1), (int64_t)(2 * FSW_LDS_MAX_DEG) << i);
-    const size_t line_bytes = long_line_bytes(bin_max);
-    int64_t nwaves = std::min<int64_t>((int64_t)(c->scratch_bytes / line_bytes), kLongMaxWaves);
-    nwaves = std::min<int64_t>(nwaves, rows * c->S);
-    FSW_REQUIRE(nwaves >= 1, "fsw_embed_cart_backward_keys_f32: scratch buffer too small (need fsw_embed_cart_backward_scratch_bytes)");
-    k_cart_bwd_long<<<(unsigned)ceil_div(nwaves, 4), 256, 0, stream>>>(t, bin, reinterpret_cast<char*>(c->scratch),
-                                                                       (int64_t)(line_bytes / 12), (int)nwaves);
-    FSW_LAUNCH_CHECK();
-  }
-  return 0;
+  return for_each_cart_line_bin(c, kCartLong[0], [&](int bin, int64_t line_elems, int nwaves) {
+    k_cart_bwd_long<<<(unsigned)ceil_div(nwaves, 4), 256, 0, stream>>>(t, bin, reinterpret_cast<char*>(c->scratch), line_elems, nwaves);
+  });
 }
 
 }  // namespace fsw
-
-using namespace fsw;
-
-extern "C" size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S) {
-  if (max_degree <= FSW_LDS_MAX_DEG) return 0;
-  const size_t line_bytes = long_line_bytes(std::min<int64_t>(max_degree, FSW_HUB_MAX_DEG));
-  const size_t cap = (size_t)2 << 30;                            // as embed_global_scratch_bytes: fewer wavefronts then share the lines
-  const int64_t lines = std::max<int64_t>(long_rows, 1) * std::max<int32_t>(S, 1);
-  const size_t waves = std::max<size_t>(std::min<size_t>((size_t)std::min<int64_t>(lines, kLongMaxWaves), cap / line_bytes), 1);
-  size_t bytes = waves * line_bytes;
-  // rows above FSW_HUB_MAX_DEG run on the generic kernel out of the same buffer
-  if (max_degree > FSW_HUB_MAX_DEG) bytes = std::max(bytes, fsw_embed_cart_generic_scratch_bytes(max_degree, std::max<int64_t>(long_rows, 1)));
-  return bytes;
-}

@@ -25,9 +25,6 @@ namespace fsw {
 
 namespace {
 
-constexpr int kCartHubWM = 32;    // elements per lane
-constexpr int kFB = 16;           // frequencies per synchronisation of the readout
-
 struct CartHubW {
   const int32_t* rowptr;
   const int32_t* col;
@@ -61,14 +58,9 @@ __global__ void __launch_bounds__(NW* kWave, 2) k_cart_hub_w(const CartHubW a, i
   const int lane = lane_id(), w = wave_id();
   const int S = a.S, F = a.F;
   const double taud = (double)a.tau;
-  // virtual block -> (row, slice) as in k_cart_hub: the blocks of one XCD walk the slices of one row, then the row 8 further on;
-  // the grid is capped, a multiple of 8, and strides over the virtual blocks
   const int xcd = blockIdx.x & 7;
   for (int64_t vb = blockIdx.x;; vb += gridDim.x) {
-    const int64_t i = vb >> 3;
-    const int64_t rl = i / S;
-    const int s = (int)(i - rl * S);
-    const int64_t r = rl * 8 + xcd;
+    const auto [r, s] = hub_virtual_line(vb, xcd, 1, S);
     if (r >= nrows) return;                 // the whole workgroup leaves
     const int node = a.perm[pbeg + r];
     const int start = a.rowptr[node];
@@ -179,27 +171,19 @@ __global__ void __launch_bounds__(NW* kWave, 2) k_cart_hub_w(const CartHubW a, i
   }
 }
 
-// one class: the rows of the bins bin_lo .. bin_hi with dlo < D <= dhi
 template <int NW>
-int launch_cart_hub_w_class(const CartHubW& t, const int32_t* bs, int bin_lo, int bin_hi, int dlo, int dhi, int64_t max_degree,
-                            hipStream_t stream) {
-  constexpr int M = kCartHubWM;
-  static_assert(NW * M * kWave <= FSW_CART_W_MAX_LINE, "the classes end at FSW_CART_W_MAX_LINE elements");
-  const int64_t rows = (int64_t)bs[bin_hi + 1] - bs[bin_lo];
-  if (rows <= 0 || max_degree <= dlo) return 0;
+int launch_cart_hub_w_class(const CartHubW& t, const CartLongClass& k, int64_t rows, hipStream_t stream) {
+  constexpr int M = kCartLongM;
   const size_t lds = sizeof(float) * 2 * NW * M * kWave;
   if (lds + 2048 > 64 * 1024) FSW_SET_MAX_LDS_ONCE((&k_cart_hub_w<NW, M>), lds);   // the kernel's static LDS comes on top of the 64 KB default
-  // virtual blocks = (rows rounded up to 8) x slices; the launched grid is capped at 2^20 workgroups and strides
-  const int64_t nvirtual = ceil_div(rows, 8) * t.S * 8;
-  const int64_t nblocks = std::min<int64_t>(nvirtual, 1ll << 20);
-  k_cart_hub_w<NW, M><<<(unsigned)nblocks, NW * kWave, lds, stream>>>(t, bin_lo, bin_hi, dlo, std::min(dhi, NW * M * kWave - 1));
+  k_cart_hub_w<NW, M><<<cart_hub_grid(rows, t.S), NW * kWave, lds, stream>>>(t, k.bin_lo, k.bin_hi, k.dlo, k.dhi);
   FSW_LAUNCH_CHECK();
   return 0;
 }
 
 }  // namespace
 
-// general weights: the rows of 2048 .. FSW_CART_W_MAX_LINE - 1 neighbours (lines of 2049 .. FSW_CART_W_MAX_LINE elements)
+// general weights: one launch per class of kCartLong[1] that the graph can have rows of
 int launch_cart_hub_w(const fsw_cart_args* c, hipStream_t stream) {
   const int32_t* bs = c->bin_start_host;
   CartHubW t;
@@ -207,11 +191,15 @@ int launch_cart_hub_w(const fsw_cart_args* c, hipStream_t stream) {
   t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
   t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
   t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
-  constexpr int kLastLds = FSW_BIN_LDS0 + FSW_NUM_LDS_BINS - 1;   // D = 2048 lives in the last LDS bin
-  int rc;
-  if ((rc = launch_cart_hub_w_class<2>(t, bs, kLastLds, FSW_BIN_HUB0, 2047, 4095, c->max_degree, stream))) return rc;
-  if ((rc = launch_cart_hub_w_class<4>(t, bs, FSW_BIN_HUB0, FSW_BIN_HUB0 + 1, 4095, 8191, c->max_degree, stream))) return rc;
-  return launch_cart_hub_w_class<8>(t, bs, FSW_BIN_HUB0 + 1, FSW_BIN_HUB0 + 2, 8191, 16383, c->max_degree, stream);
+  constexpr decltype(&launch_cart_hub_w_class<2>) launch[] = {launch_cart_hub_w_class<2>, launch_cart_hub_w_class<4>,
+                                                              launch_cart_hub_w_class<8>};   // class i: 2 << i wavefronts
+  const CartLongMode& m = kCartLong[1];
+  for (int i = 0; i < m.num; ++i) {
+    const int64_t rows = (int64_t)bs[m.cls[i].bin_hi + 1] - bs[m.cls[i].bin_lo];
+    if (rows <= 0 || c->max_degree <= m.cls[i].dlo) continue;
+    if (const int rc = launch[i](t, m.cls[i], rows, stream)) return rc;
+  }
+  return 0;
 }
 
 }  // namespace fsw

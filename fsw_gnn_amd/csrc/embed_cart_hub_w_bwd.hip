@@ -28,10 +28,6 @@ namespace fsw {
 
 namespace {
 
-constexpr int kLongWM = 32;                     // words per lane of a chunk
-constexpr int kLongWCap = kLongWM * kWave;      // 2048
-constexpr int kLongWMaxWaves = 2048;            // resident wavefronts a launch uses at most
-
 struct CartBwdLongW {
   const int32_t* rowptr;
   const int32_t* col;
@@ -54,11 +50,11 @@ struct CartBwdLongW {
 
 __global__ void __launch_bounds__(256) k_cart_bwd_long_w(const CartBwdLongW a, int bin, char* __restrict__ scratch, int64_t line_elems,
                                                          int nwaves) {
-  constexpr int M = kLongWM, CAP = kLongWCap;
+  constexpr int M = kCartLongM, CAP = kCartMaxLine;
   const int lane = lane_id();
   const int gw = blockIdx.x * 4 + wave_id();
   if (gw >= nwaves) return;                                      // the wavefronts never synchronise with each other
-  unsigned long long* se = reinterpret_cast<unsigned long long*>(scratch + (int64_t)gw * line_elems * 12);   // packed (key, index) words
+  unsigned long long* se = reinterpret_cast<unsigned long long*>(scratch + (int64_t)gw * line_elems * kCartLineBytes);   // packed (key, index) words
   float* sc = reinterpret_cast<float*>(se + line_elems);                                                     // key gradients, entry order
   const int pbeg = a.bin_start[bin], pend = a.bin_start[bin + 1];
   const int S = a.S, F = a.F;
@@ -191,59 +187,18 @@ __global__ void __launch_bounds__(256) k_cart_bwd_long_w(const CartBwdLongW a, i
   }
 }
 
-// elements of one wavefront's scratch line for rows of up to `degree` neighbours (the pad element included)
-int64_t long_w_line_elems(int64_t degree) {
-  return (int64_t)pow2ceil((uint32_t)(std::min<int64_t>(degree, FSW_CART_W_MAX_LINE - 1) + 1));
-}
-
 }  // namespace
 
-// general weights: the rows of 2048 .. FSW_CART_W_MAX_LINE - 1 neighbours -- D = 2048 in the last LDS bin, the others in the first
-// three hub bins -- one launch per populated bin, the scratch line sized by the bin's own longest row; as many wavefronts as the
-// buffer holds lines (at most kLongWMaxWaves), at least one
+// general weights: the classes of kCartLong[1], one launch per populated bin they touch (embed_cart.h: for_each_cart_line_bin)
 int launch_cart_hub_w_bwd(const fsw_cart_args* c, hipStream_t stream) {
-  const int32_t* bs = c->bin_start_host;
-  constexpr int kLastLds = FSW_BIN_LDS0 + FSW_NUM_LDS_BINS - 1;
-  if (c->max_degree < FSW_LDS_MAX_DEG || (int64_t)bs[FSW_BIN_HUB0 + 3] - bs[kLastLds] <= 0) return 0;
-  FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0,
-              "fsw_embed_cart_backward_keys_f32: rows of FSW_LDS_MAX_DEG neighbours and more need a 16-byte aligned scratch buffer "
-              "(fsw_embed_cart_weighted_backward_scratch_bytes)");
   CartBwdLongW t;
   t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
   t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
   t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
   t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
-  for (int bin = kLastLds; bin <= FSW_BIN_HUB0 + 2; ++bin) {
-    const int64_t rows = (int64_t)bs[bin + 1] - bs[bin];
-    if (rows <= 0) continue;
-    // longest row of the bin: FSW_LDS_MAX_DEG << (bin - kLastLds) neighbours
-    const int64_t bin_max = std::min<int64_t>(c->max_degree, (int64_t)FSW_LDS_MAX_DEG << (bin - kLastLds));
-    if (bin_max < FSW_LDS_MAX_DEG) continue;
-    const int64_t line_elems = long_w_line_elems(bin_max);
-    const size_t line_bytes = (size_t)line_elems * 12;
-    int64_t nwaves = std::min<int64_t>((int64_t)(c->scratch_bytes / line_bytes), kLongWMaxWaves);
-    nwaves = std::min<int64_t>(nwaves, rows * c->S);
-    FSW_REQUIRE(nwaves >= 1,
-                "fsw_embed_cart_backward_keys_f32: scratch buffer too small (need fsw_embed_cart_weighted_backward_scratch_bytes)");
-    k_cart_bwd_long_w<<<(unsigned)ceil_div(nwaves, 4), 256, 0, stream>>>(t, bin, reinterpret_cast<char*>(c->scratch), line_elems,
-                                                                         (int)nwaves);
-    FSW_LAUNCH_CHECK();
-  }
-  return 0;
+  return for_each_cart_line_bin(c, kCartLong[1], [&](int bin, int64_t line_elems, int nwaves) {
+    k_cart_bwd_long_w<<<(unsigned)ceil_div(nwaves, 4), 256, 0, stream>>>(t, bin, reinterpret_cast<char*>(c->scratch), line_elems, nwaves);
+  });
 }
 
 }  // namespace fsw
-
-using namespace fsw;
-
-extern "C" size_t fsw_embed_cart_weighted_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S) {
-  if (max_degree < FSW_LDS_MAX_DEG) return 0;
-  const size_t line_bytes = (size_t)long_w_line_elems(max_degree) * 12;
-  const size_t cap = (size_t)2 << 30;                            // fewer wavefronts then share the lines
-  const int64_t lines = std::max<int64_t>(long_rows, 1) * std::max<int32_t>(S, 1);
-  const size_t waves = std::max<size_t>(std::min<size_t>((size_t)std::min<int64_t>(lines, kLongWMaxWaves), cap / line_bytes), 1);
-  size_t bytes = waves * line_bytes;
-  // rows of FSW_CART_W_MAX_LINE neighbours and more run on the generic kernel out of the same buffer
-  if (max_degree >= FSW_CART_W_MAX_LINE) bytes = std::max(bytes, fsw_embed_cart_generic_scratch_bytes(max_degree, std::max<int64_t>(long_rows, 1)));
-  return bytes;
-}

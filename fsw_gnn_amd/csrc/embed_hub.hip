@@ -138,10 +138,7 @@ __global__ void __launch_bounds__(NW* kWave, M > 32 ? 2 : FSW_HUB_MINWAVES) k_em
   for (int64_t n = 0;; ++n) {
     const int64_t vb = blockIdx.x + (n >> 2) * (int64_t)gridDim.x;
     const int sl = (int)(n & 3);
-    const int64_t i = (vb >> 3) * 4;
-    const int64_t rl = i / S;
-    const int k0 = (int)(i - rl * S);
-    const int64_t r = rl * 8 + xcd;
+    const auto [r, k0] = hub_virtual_line(vb, xcd, 4, S);
     if (r >= nrows) return;
     const int node = perm[pbeg + r];
     const int start = rowptr[node];
@@ -254,10 +251,7 @@ __global__ void __launch_bounds__(256, FSW_HUB_MINWAVES) k_embed_hub_quad(
   const int lane = lane_id(), w = wave_id();
   const int xcd = blockIdx.x & 7;
   for (int64_t vb = blockIdx.x;; vb += gridDim.x) {
-    const int64_t i = (vb >> 3) * 4;              // the workgroup's first line; S % 4 == 0: its four lines are one row's
-    const int64_t rl = i / S;
-    const int k0 = (int)(i - rl * S);
-    const int64_t r = rl * 8 + xcd;
+    const auto [r, k0] = hub_virtual_line(vb, xcd, 4, S);   // the workgroup's first line; S % 4 == 0: its four lines are one row's
     if (r >= nrows) return;                       // the whole workgroup
     const int node = perm[pbeg + r];
     const int start = rowptr[node];

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include "embed_launch.h"
 #include "fourier_coef.h"
+#include "hub_line.h"
 #include "sortnet.h"
 #include "wave_sort.h"
 
@@ -222,10 +223,7 @@ __global__ void __launch_bounds__(256, (M >= 32 ? 2 : (M >= 16 ? 3 : 4))) k_embe
   const int lane = lane_id(), w = wave_id();
   const int xcd = blockIdx.x & 7;
   for (int64_t vb = blockIdx.x;; vb += gridDim.x) {
-    const int64_t i = (vb >> 3) * 4;              // the workgroup's first slice; S % 4 == 0: four slices of one row
-    const int64_t rl = i / S;
-    const int k0 = (int)(i - rl * S);
-    const int64_t r = rl * 8 + xcd;
+    const auto [r, k0] = hub_virtual_line(vb, xcd, 4, S);   // the workgroup's first slice; S % 4 == 0: four slices of one row
     if (r >= nrows) return;                       // the whole workgroup
     const int node = perm[pbeg + r];
     const int start = rowptr[node];

@@ -134,4 +134,15 @@ __device__ __forceinline__ void gather_chunk(WaveLine<M, false>& ln, const int32
     ln.k[j] = c[j] >= 0 ? ((FSW_HUB_ABL & 1) ? (float)((c[j] * 2654435761u) >> 8) : Xp[(int64_t)c[j] * ldp + k]) : __builtin_inff();
 }
 
+// Virtual block vb -> (row r of the launch's bins, first slice): the workgroups b, b + 8, b + 16, ... (one XCD under round-robin
+// dispatch) walk the slices of row xcd = b & 7, lines_per_block at a time, then those of row xcd + 8, ...  The launched grid is capped, a
+// multiple of 8 and strides (vb += gridDim.x), so a workgroup stays on its residue and leaves at its first row past the bins.
+struct HubLineId { int64_t r; int s; };
+__device__ __forceinline__ HubLineId hub_virtual_line(int64_t vb, int xcd, int lines_per_block, int S) {
+  const int64_t i = (vb >> 3) * lines_per_block;
+  const int64_t rl = i / S;
+  const int s = (int)(i - rl * S);
+  return {rl * 8 + xcd, s};
+}
+
 }  // namespace fsw

@@ -22,10 +22,10 @@ every slice is sorted once and read out at all F frequencies (csrc/embed_cart.hi
 (<batch>, [nR,] S*F + mass_dim) collapsed, column s*F + f (after the mass column).  float32 calls run on the tuned kernels, under
 autograd through _CartEmbedFn (backward kernels of csrc/embed_cart_bwd.hip, the key gradients summed sender by sender without
 float atomics; gradients for X, projVecs, freqs, bias and the total-mass scale); float64 modules and calls whose W requires grad
-run on the generic Cartesian kernel (_GenericEmbedFn).  Unit-weight rows of 2049 .. 32768 neighbours have hub kernels of their own
-(csrc/embed_cart_hub.hip: the line in the registers of 2 .. 16 wavefronts, no scratch; csrc/embed_cart_hub_bwd.hip: one wavefront per
-line in a scratch line that _CartEmbedFn.backward allocates); general-weight rows of 2048 neighbours and more and any row above
-32768 run on the generic kernel inside the tuned entry points.  It needs a HIP device at construction (this
+run on the generic Cartesian kernel (_GenericEmbedFn).  Lines above 2048 elements have kernels of their own (csrc/embed_cart_hub*.hip:
+forward, the line in the registers of 2 .. 16 wavefronts; backward, one wavefront per line in a scratch line), longer ones still run
+on the generic kernel inside the tuned entry points: the library's table (csrc/embed_cart.h: kCartLong) says which rows go where, the
+host layer only asks it for the scratch size (_cart_scratch_bytes).  It needs a HIP device at construction (this
 package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
 differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
 bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
@@ -490,9 +490,9 @@ class _CartEmbedFn(torch.autograd.Function):
     projVecs, freqs, bias and the total-mass scale (the weights are constants: a W that requires grad takes _GenericEmbedFn).
 
     Forward: one projection of all S slices (prepare_cartesian) + fsw_embed_cart_f32; the projection, the stats and the unit table
-    stay on ctx.  Backward: fsw_embed_cart_backward_keys_f32 (csrc/embed_cart_bwd.hip; it allocates the scratch lines of the
-    unit-weight hub rows itself, _cart_backward_scratch) stores the key gradient of every entry,
-    [nnz, S], and accumulates the frequency gradients; the store-and-sum pair (graph.sender_major + fsw_segment_sum_rows_f32) sums
+    stay on ctx.  Backward: fsw_embed_cart_backward_keys_f32 (csrc/embed_cart_bwd.hip; its scratch is the forward's buffer where that is
+    large enough, else a buffer of its own: _cart_scratch) stores the key gradient of every entry, [nnz, S], and accumulates the
+    frequency gradients; the store-and-sum pair (graph.sender_major + fsw_segment_sum_rows_f32) sums
     the entries sender by sender without float atomics, then the two GEMMs of _EmbedGraphFn.  bias: None for 'homog' /
     'homog_alt' (the caller applies _homog_epilogue on the 'plain' output)."""
 
@@ -531,7 +531,7 @@ class _CartEmbedFn(torch.autograd.Function):
                 _lib.check(L.fsw_unit_dcoeff_table(_lib.ptr(fr), F, _lib.REG_MAX_DEG, _lib.ptr(dtable), F, stream), "fsw_unit_dcoeff_table")
             gf = torch.zeros(F, dtype=torch.float32, device=dev)
             gkey = torch.empty((nnz, S), dtype=torch.float32, device=dev)      # every entry is stored
-            scratch = module._cart_backward_scratch(graph, st, prepared["scratch"])
+            scratch = module._cart_scratch(graph, st, backward=True, reuse=prepared["scratch"])
             a = module._cart_tuned_args(graph, st, prepared["Xp"], ldp, fr, S, table, scratch, out_scale, has_mass)
             a.g, a.ldg, a.gkey, a.ldk, a.gfreq = g.data_ptr(), g.stride(0), gkey.data_ptr(), S, gf.data_ptr()
             _lib.check(L.fsw_embed_cart_backward_keys_f32(ctypes.byref(a), _lib.ptr(dtable), F, stream), "fsw_embed_cart_backward_keys_f32")
@@ -959,36 +959,21 @@ class FSW_embedding(nn.Module):
                                           torch.cuda.current_stream(fr.device).cuda_stream), "fsw_unit_coeff_table")
         return table
 
-    def _cart_scratch(self, graph, st):
-        """Forward scratch: only for the rows that still run on the generic kernel (None without such rows) -- unit weights with
-        tau <= 1: the rows above 32768 neighbours; otherwise the rows of 16384 neighbours and more (the third hub bin and above)."""
-        unit = self._unit_fast(graph)
-        if st[_lib.STAT_MAX_DEGREE] < (_lib.HUB_MAX_DEG + 1 if unit else _lib.CART_W_MAX_LINE):
-            return None
-        bsh = graph.bin_start_host[0]
-        first = _lib.NUM_BINS - 1 if unit else _lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS + 2
-        long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[first])
-        return torch.empty(int(_lib.lib().fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
-                           dtype=torch.uint8, device=graph.rowptr.device)
+    def _cart_scratch_bytes(self, graph, st, backward):
+        """Bytes of scratch the tuned Cartesian forward (backward: its backward) needs on this graph, 0 for none: the library's answer
+        from the host copy of the degree bins, the longest row, the weight mode and the number of slices.  No device is touched."""
+        a = _lib.CartArgs()
+        a.S, a.tau, a.max_degree = self.nSlices, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
+        a.w = graph.w.data_ptr() if graph.w is not None else None
+        a.bin_start_host = graph.bin_start_host[0].ctypes.data
+        return int(_lib.lib().fsw_embed_cart_scratch_bytes(ctypes.byref(a), int(backward)))
 
-    def _cart_backward_scratch(self, graph, st, forward_scratch):
-        """Backward scratch: the forward's, unless the graph has unit-weight hub rows (2049 .. 32768 neighbours) or general-weight
-        rows of 2048 .. 16383 neighbours -- their backward kernels sort every line in a scratch line; the buffer then also serves the
-        generic kernel on the longer rows."""
-        bsh = graph.bin_start_host[0]
-        hub0 = _lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS
-        if not self._unit_fast(graph):
-            if st[_lib.STAT_MAX_DEGREE] < _lib.LDS_MAX_DEG:
-                return forward_scratch
-            long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[hub0 - 1])     # a row of exactly 2048 neighbours is in the last LDS bin
-            return torch.empty(int(_lib.lib().fsw_embed_cart_weighted_backward_scratch_bytes(st[_lib.STAT_MAX_DEGREE], long_rows,
-                                                                                          self.nSlices)),
-                               dtype=torch.uint8, device=graph.rowptr.device)
-        if int(bsh[_lib.NUM_BINS - 1]) == int(bsh[hub0]):
-            return forward_scratch
-        long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[hub0])
-        return torch.empty(int(_lib.lib().fsw_embed_cart_backward_scratch_bytes(st[_lib.STAT_MAX_DEGREE], long_rows, self.nSlices)),
-                           dtype=torch.uint8, device=graph.rowptr.device)
+    def _cart_scratch(self, graph, st, backward=False, reuse=None):
+        """The scratch buffer of _cart_scratch_bytes, None for 0 bytes; reuse (the forward's buffer) when it is large enough."""
+        nbytes = self._cart_scratch_bytes(graph, st, backward)
+        if reuse is not None and reuse.numel() >= nbytes:
+            return reuse
+        return torch.empty(nbytes, dtype=torch.uint8, device=graph.rowptr.device) if nbytes else None
 
     def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass):
         """struct fsw_cart_args of the tuned entry points (fsw_embed_cart_f32, fsw_embed_cart_backward_keys_f32) without the

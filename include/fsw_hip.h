@@ -360,15 +360,8 @@ int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double
  * fsw_embed_cart_backward_keys_f32 (below) is the tuned float32 backward of fsw_embed_cart_f32 for keys and frequencies.
  * fsw_embed_cart_f32      tuned float32 forward on a graph of fsw_graph_build: needs perm, bin_start and bin_start_host and
  *                         unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1.
- *                         Scratch, forward: only the rows that run on the generic kernel of fsw_embed_cart_generic need it --
- *                           w == NULL and tau <= 1: rows above FSW_HUB_MAX_DEG (rows of FSW_LDS_MAX_DEG + 1 .. FSW_HUB_MAX_DEG
- *                             neighbours keep their lines in registers, csrc/embed_cart_hub.hip); scratch may be NULL when
- *                             max_degree <= FSW_HUB_MAX_DEG;
- *                           otherwise (w != NULL or tau > 1): rows of FSW_CART_W_MAX_LINE neighbours and above (the pad element
- *                             makes a line of D + 1; lines of up to FSW_CART_W_MAX_LINE elements keep keys and weights in
- *                             registers, csrc/embed_cart_hub_w.hip); scratch may be NULL when max_degree < FSW_CART_W_MAX_LINE;
- *                         fsw_embed_cart_generic_scratch_bytes(max_degree, number of those rows) bytes: 36 bytes per element of a
- *                         line of the next power of two >= max_degree + 1 and workgroup.
+ *                         Scratch: fsw_embed_cart_scratch_bytes(args, 0) bytes (0: scratch may be NULL).  Only the rows
+ *                         beyond the tuned classes (csrc/embed_cart.h: kCartLong) need it: they run on the generic kernel.
  *                         Rows of 1 .. FSW_REG_MAX_DEG unit-weight neighbours are stored 16 bytes at a time when F % 4 == 0,
  *                         ldo % 4 == 0, ldt % 4 == 0 and out + has_mass, bias + has_mass and unit_table are 16-byte aligned (a
  *                         caller with a mass column gets there by starting its rows 3 floats into an aligned buffer).
@@ -425,24 +418,16 @@ int fsw_embed_cart_f32(const fsw_cart_args* args, fsw_stream_t stream);
  * Adds    args->gfreq[f]         += out_scale * sum_{r,s} g[r, has_mass + s F + f] * d out[r,s,f] / d xi_f  (nullable; caller zeroes)
  * args->gw must be NULL (gradients w.r.t. the weights stay on fsw_embed_cart_generic).
  * unit_dtable: fsw_unit_dcoeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1 (with args->unit_table as in the forward).
- * Scratch, backward: w == NULL and tau <= 1: needed as soon as max_degree > FSW_LDS_MAX_DEG.  A row of FSW_LDS_MAX_DEG + 1 ..
- *   FSW_HUB_MAX_DEG neighbours is sorted by one wavefront per (row, slice) in a scratch line of 12 bytes per element of the next
- *   power of two >= the longest row of its degree bin (csrc/embed_cart_hub_bwd.hip); the launch uses as many wavefronts as the
- *   buffer holds lines (at most 2048) and needs one.  fsw_embed_cart_backward_scratch_bytes(max_degree, rows above
- *   FSW_LDS_MAX_DEG, S) returns the recommended size (room for min(2048, rows * S) wavefronts, capped at 2 GiB; 0 when
- *   max_degree <= FSW_LDS_MAX_DEG; with rows above FSW_HUB_MAX_DEG at least what the generic kernel needs for them).  A buffer of
- *   fsw_embed_cart_generic_scratch_bytes(max_degree, rows >= 1) bytes also suffices (three lines or more).
- *   Otherwise (w != NULL or tau > 1): needed as soon as max_degree >= FSW_LDS_MAX_DEG.  A row of FSW_LDS_MAX_DEG ..
- *   FSW_CART_W_MAX_LINE - 1 neighbours is sorted by one wavefront per (row, slice) in a scratch line of 12 bytes per element of the
- *   next power of two >= the longest line (D + 1) of its degree bin (csrc/embed_cart_hub_w_bwd.hip); as many wavefronts as the
- *   buffer holds lines (at most 2048), at least one.  fsw_embed_cart_weighted_backward_scratch_bytes(max_degree, rows of
- *   FSW_LDS_MAX_DEG neighbours and more, S) returns the recommended size: min(2048, rows * S) lines of
- *   12 * pow2ceil(min(max_degree, FSW_CART_W_MAX_LINE - 1) + 1) bytes, capped at 2 GiB; 0 when max_degree < FSW_LDS_MAX_DEG; with
- *   rows of FSW_CART_W_MAX_LINE neighbours and more (they run on the generic kernel in backward mode out of the same buffer) at
- *   least fsw_embed_cart_generic_scratch_bytes(max_degree, rows).  A buffer of fsw_embed_cart_generic_scratch_bytes(max_degree,
- *   rows >= 1) bytes also suffices (three lines or more) and gives bit-identical gkey.
+ * Scratch: fsw_embed_cart_scratch_bytes(args, 1) bytes (0: scratch may be NULL).
+ *   A buffer of fsw_embed_cart_generic_scratch_bytes(max_degree, rows >= 1) bytes also suffices and gives bit-identical gkey.
  * The buffer must be 16-byte aligned. */
 int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* args, const float* unit_dtable, int64_t lddt, fsw_stream_t stream);
+/* Scratch of fsw_embed_cart_f32 (backward == 0) or fsw_embed_cart_backward_keys_f32 (backward != 0) for the graph and weight mode of
+ * args, of which it reads bin_start_host, max_degree, w (NULL or not), tau and S: host values only, no device is needed. */
+size_t fsw_embed_cart_scratch_bytes(const fsw_cart_args* args, int backward);
+/* The parts of that answer for a caller without the bins: the backward's scratch for w == NULL and tau <= 1 given the rows above
+ * FSW_LDS_MAX_DEG neighbours, and for general weights given the rows of FSW_LDS_MAX_DEG neighbours and more (lines of 12 bytes per
+ * element of the padded longest line, min(2048, long_rows * S) of them, at most 2 GiB; 0 when no row is that long). */
 size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S);
 size_t fsw_embed_cart_weighted_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S);
 /* FSW_conv with a Cartesian embedding, fast path (csrc/conv_fused.hip: k_conv_fused_cart): fsw_conv_fused_f32 for an embedding row

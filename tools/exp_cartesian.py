@@ -35,7 +35,8 @@ training step (forward + backward) each:
   rmat     FSW_embedding(nSlices=16, nFreqs=16) on the RMAT-20 graph of tools/exp_skew.py (1M nodes, 10M unit edges, prebuilt CSR)
 The library is the one FSW_HIP_LIBRARY names (fsw_gnn_amd/_lib.py).  A build from before the hub kernels (no export
 fsw_embed_cart_backward_scratch_bytes: a parent commit built in a copy of the tree and copied to _variants/) is driven by the same
-host code with the scratch its generic kernel needs for every row above 2048 neighbours, so both builds can alternate on one box:
+host code with the scratch its generic kernel needs for every row above 2048 neighbours, and a build from before
+fsw_embed_cart_scratch_bytes with the sizes the host layer chose then, so that builds can alternate on one box:
     python tools/exp_cartesian.py --hub [--workload readout,rmat] --steps 3 --warmup 1
     FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --hub --steps 3 --warmup 1
     rocprofv3 --kernel-trace --stats -d DIR -o hub -- python tools/exp_cartesian.py --hub --workload readout --steps 1
@@ -185,28 +186,32 @@ def hub_leg():
     has_hub_w = hasattr(handle, "fsw_embed_cart_weighted_backward_scratch_bytes")
     general = args.weights != "unit" or args.tau > 1.0
 
-    def generic_scratch(self, graph, st):
-        if st[_lib.STAT_MAX_DEGREE] < _lib.LDS_MAX_DEG:
-            return None
-        bsh = graph.bin_start_host[0]
-        long_rows = int(bsh[_lib.NUM_BINS]) - int(bsh[_lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS - 1])
-        return torch.empty(int(_lib.lib().fsw_embed_cart_generic_scratch_bytes(st[_lib.STAT_MAX_DEGREE], max(long_rows, 1))),
-                           dtype=torch.uint8, device=graph.rowptr.device)
+    def scratch_bytes_before(self, graph, st, backward):
+        """The host layer's rules from before fsw_embed_cart_scratch_bytes, on the size functions the build has: a build without the
+        classes of a weight mode runs those rows on the generic kernel, which needs its scratch in both directions."""
+        L, md, bsh, S = _lib.lib(), st[_lib.STAT_MAX_DEGREE], graph.bin_start_host[0], self.nSlices
+        hub0 = _lib.BIN_MID0 + len(_lib.MID_SIZES) + _lib.NUM_LDS_BINS
 
+        def generic(first_bin):
+            return int(L.fsw_embed_cart_generic_scratch_bytes(md, max(int(bsh[_lib.NUM_BINS]) - int(bsh[first_bin]), 1)))
+
+        unit = self._unit_fast(graph)
+        if not (has_hub if unit else has_hub_w):
+            return 0 if md < _lib.LDS_MAX_DEG else generic(hub0 - 1)
+        forward = 0 if md < (_lib.HUB_MAX_DEG + 1 if unit else _lib.CART_W_MAX_LINE) else generic(_lib.NUM_BINS - 1 if unit else hub0 + 2)
+        if not backward or (int(bsh[_lib.NUM_BINS - 1]) == int(bsh[hub0]) if unit else md < _lib.LDS_MAX_DEG):
+            return forward
+        size, first = ((L.fsw_embed_cart_backward_scratch_bytes, hub0) if unit else
+                       (L.fsw_embed_cart_weighted_backward_scratch_bytes, hub0 - 1))
+        return int(size(md, int(bsh[_lib.NUM_BINS]) - int(bsh[first]), S))
+
+    if not hasattr(handle, "fsw_embed_cart_scratch_bytes"):
+        del _lib._SIGNATURES["fsw_embed_cart_scratch_bytes"]
+        FSW_embedding._cart_scratch_bytes = scratch_bytes_before
     if not has_hub_w:
-        # a build from before the general-weight classes: no such export, and every general-weight row of 2048 neighbours and more runs
-        # on the generic kernel, which needs its scratch in both directions
         del _lib._SIGNATURES["fsw_embed_cart_weighted_backward_scratch_bytes"]
-        tuned_scratch, tuned_backward_scratch = FSW_embedding._cart_scratch, FSW_embedding._cart_backward_scratch
-        FSW_embedding._cart_scratch = lambda self, graph, st: (
-            tuned_scratch(self, graph, st) if self._unit_fast(graph) else generic_scratch(self, graph, st))
-        FSW_embedding._cart_backward_scratch = lambda self, graph, st, forward_scratch: (
-            tuned_backward_scratch(self, graph, st, forward_scratch) if self._unit_fast(graph) else forward_scratch)
     if not has_hub:
-        # a build from before the hub kernels: the same for the unit-weight rows above 2048 neighbours
         del _lib._SIGNATURES["fsw_embed_cart_backward_scratch_bytes"]
-        FSW_embedding._cart_scratch = generic_scratch
-        FSW_embedding._cart_backward_scratch = lambda self, graph, st, forward_scratch: forward_scratch
     print("library %s: %s" % (_lib.LIB_PATH, ("general-weight hub kernels" if has_hub_w else "generic kernel on the general-weight rows of "
                                               "2048 neighbours and more") if general else
                               ("hub kernels" if has_hub else "generic kernel on the rows above 2048 neighbours")), flush=True)
