@@ -136,7 +136,7 @@ __global__ void __launch_bounds__(256) k_embed_reg_unit_bwd(const int32_t* __res
 // xi-derivative in float64 (the two terms of dF/dxi cancel from O(c/xi) to O(1)).
 __device__ __forceinline__ void F_dF(double xi, double c, double& F, double& dF) {
   const double x = 2.0 * kPi * xi * c;
-  if (x < 1e-4) {
+  if (fabs(x) < 1e-4) {
     const double q = 1.0 - x * x * (1.0 / 6.0);
     F = (1.0 + xi) * 2.0 * c * q;
     dF = 2.0 * c * q - (1.0 + xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * xi * (1.0 / 3.0);

@@ -133,7 +133,7 @@ __device__ __forceinline__ void cart_reg_weighted(const CartTuned& a, int p, int
       const float xif = as_const(a.freqs)[f];
       const double xi = (double)xif;
       float val;
-      if (xif < 1e-30f) {                             // xi == 0: Delta_t = 2 w_t
+      if (fabsf(xif) < 1e-30f) {                             // xi == 0: Delta_t = 2 w_t
         float acc0 = 0.f;
 #pragma unroll
         for (int t = 0; t <= D; ++t) acc0 = fmaf(net.w[t], net.k[t], acc0);
@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(64) k_cart_wave(const CartTuned a, int p0) {
     const int Q = kWave / NF;
     const int f = f0 + lane % NF, q = lane / NF;
     const double xi = (double)a.freqs[f];
-    const bool lin = xi < 1e-30;
+    const bool lin = fabs(xi) < 1e-30;
     float acc = 0.f;
     if (q < Q) {
       for (int t = q; t < L; t += Q) {

@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(NW* kWave, 2) k_cart_hub_w(const CartHubW a, i
       for (int q = 0; q < nf; ++q) {
         const float xif = a.freqs[f0 + q];
         float acc = 0.f;
-        if (xif < 1e-30f) {                                     // xi == 0: Delta_t = 2 w_t / max(m, tau)
+        if (fabsf(xif) < 1e-30f) {                                     // xi == 0: Delta_t = 2 w_t / max(m, tau)
 #pragma unroll
           for (int j = 0; j < M; ++j) acc = fmaf(ln.w[j], ln.k[j], acc);
         } else {
@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(NW* kWave, 2) k_cart_hub_w(const CartHubW a, i
         for (int u = 0; u < NW; ++u) val += red[buf][lane][u];
         const float xif = a.freqs[f0 + lane];
         const double xi = (double)xif;
-        val *= xif < 1e-30f ? 2.f * (float)inv : (float)((1.0 + xi) / (kPi * xi));
+        val *= fabsf(xif) < 1e-30f ? 2.f * (float)inv : (float)((1.0 + xi) / (kPi * xi));
         const int64_t c = c0 + f0 + lane;
         orow[c] = a.out_scale * (val + (a.bias ? a.bias[c] : 0.f));
       }

@@ -720,7 +720,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k
     // readout: element (w, lane, j) has rank w * CAP + lane * M + j
     const float xif = freqs[k];
     const double xi = (double)xif;
-    const bool lin = xif < 1e-30f;
+    const bool lin = fabsf(xif) < 1e-30f;
     double lsum = 0.0;
 #pragma unroll
     for (int j = 0; j < M; ++j) lsum += (double)ln.w[j];
@@ -877,7 +877,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_embed_mergepath_w(
     const double taud = (double)tau;
     const float xif = freqs[k];
     const double xi = (double)xif;
-    const bool lin = xif < 1e-30f;
+    const bool lin = fabsf(xif) < 1e-30f;
     WaveLine<M, true> ln;
 #pragma unroll 1
     for (int b = 0; b < nb; ++b) {

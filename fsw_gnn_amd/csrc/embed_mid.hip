@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_unit(const int32_t* __restric
   const int pbeg = bin_start[bin], pend = bin_start[bin + 1];
   const float xif = freqs[kc];
   const double xi = (double)xif;
-  const bool lin = xif < 1e-30f;   // xi == 0: Delta_t = 2 w_t
+  const bool lin = fabsf(xif) < 1e-30f;   // xi == 0: Delta_t = 2 w_t
   const float b = bias ? out_scale * bias[has_mass + kc] : 0.f;
   const float* xk = Xp + kc;
   // A row's descriptors arrive ahead of it: its node id (perm) is requested before the previous row's gather, its CSR range (rowptr)
@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(256, 1) k_embed_mid_unit_pf(const int32_t* __r
   const int pbeg = bin_start[bin], pend = bin_start[bin + 1];
   const float xif = freqs[kc];
   const double xi = (double)xif;
-  const bool lin = xif < 1e-30f;
+  const bool lin = fabsf(xif) < 1e-30f;
   const float b = bias ? out_scale * bias[has_mass + kc] : 0.f;
   const float* xk = Xp + kc;
   const int stride = gridDim.x;
@@ -222,7 +222,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
   const int pbeg = bin_start[bin], pend = bin_start[bin + 1];
   const float xif = freqs[kc];
   const double xi = (double)xif;
-  const bool lin = xif < 1e-30f;
+  const bool lin = fabsf(xif) < 1e-30f;
   const float scale = lin ? 2.f : (float)((1.0 + xi) / (kPi * xi));
   const float b = bias ? bias[has_mass + kc] : 0.f;
   const double taud = (double)tau;

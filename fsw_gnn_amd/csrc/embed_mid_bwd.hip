@@ -18,7 +18,7 @@ namespace fsw {
 struct FCoefM {
   double xi, a1, a2, a3;   // a1 = (1 + xi)/(pi xi), a2 = 1/(pi xi^2), a3 = 2 (1 + xi)/xi: no division left per element
   __device__ __forceinline__ explicit FCoefM(double x) : xi(x) {
-    const double r = x > 0.0 ? 1.0 / x : 0.0;
+    const double r = x != 0.0 ? 1.0 / x : 0.0;
     a1 = (1.0 + x) * r * (1.0 / kPi);
     a2 = r * r * (1.0 / kPi);
     a3 = 2.0 * (1.0 + x) * r;
@@ -26,7 +26,7 @@ struct FCoefM {
 };
 __device__ __forceinline__ void F_dF_sc_m(const FCoefM& f, double c, double s, double co, double& F, double& dF) {
   const double x = 2.0 * kPi * f.xi * c;
-  if (x < 1e-4) {   // series: the two terms of dF cancel for tiny phases; xi == 0 gives F = dF = 2 c
+  if (fabs(x) < 1e-4) {   // series: the two terms of dF cancel for tiny phases; xi == 0 gives F = dF = 2 c
     const double q = 1.0 - x * x * (1.0 / 6.0);
     F = (1.0 + f.xi) * 2.0 * c * q;
     dF = 2.0 * c * q - (1.0 + f.xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * f.xi * (1.0 / 3.0);

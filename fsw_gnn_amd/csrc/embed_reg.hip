@@ -192,7 +192,7 @@ __device__ __forceinline__ void weighted_run(int p, int pe, const int32_t* __res
                                              const float* __restrict__ Ve, int64_t ldve, int d_edge) {
   const float xif = freqs[kc];
   const double xi = (double)xif;
-  const bool lin = xif < 1e-30f;  // xi == 0: sinc(0) = 1 and cos(0) = 1, Delta_t = 2 w_t
+  const bool lin = fabsf(xif) < 1e-30f;  // xi == 0: sinc(0) = 1 and cos(0) = 1, Delta_t = 2 w_t
   const float scale = lin ? 2.f : (float)((1.0 + xi) / (kPi * xi));
   const float b = bias ? bias[has_mass + kc] : 0.f;
   const float b0 = bias ? bias[0] : 0.f;

@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
         ln.sort();
         const float xif = freqs[k];
         const double xi = (double)xif;
-        const bool lin = xif < 1e-30f;                   // xi == 0: Delta_t = 2 w_t
+        const bool lin = fabsf(xif) < 1e-30f;                   // xi == 0: Delta_t = 2 w_t
         float acc = 0.f;
         if constexpr (!WEIGHTED) {
           if (lin) {
@@ -277,7 +277,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
     const double inv = 1.0 / (WEIGHTED ? fmax(m, (double)tau) : m);
     const float xif = freqs[k];
     const double xi = (double)xif;
-    const bool lin = xif < 1e-30f;
+    const bool lin = fabsf(xif) < 1e-30f;
     // A. chunks: gather, sort in registers, park in the scratch line
     for (int c0 = 0; c0 < Dp; c0 += CAP) {
       WaveLine<M, WEIGHTED> ln;

@@ -99,7 +99,7 @@ __device__ __forceinline__ float unit_readout(const Line& ln, int r0, int D, flo
   const double xi = (double)xif;
   const double inv = 1.0 / (double)D;
   float acc = 0.f;
-  if (xif < 1e-30f) {                       // xi == 0: Delta_t = 2 w_t
+  if (fabsf(xif) < 1e-30f) {                       // xi == 0: Delta_t = 2 w_t
 #pragma unroll
     for (int j = 0; j < M; ++j) acc += (r0 + j < D) ? ln.k[j] : 0.f;
     return acc * 2.f * (float)inv;

@@ -423,8 +423,18 @@ class _GenericEmbedFn(torch.autograd.Function):
     def key_grads(ctx, g, gkey, gf, gw):
         """The entry point in backward mode: stores gkey [nnz, S], accumulates gf [nFreqs] and gw [nnz] (each nullable)."""
         freqs = ctx.saved_tensors[2]
+        fields = {}
+        if gw is not None:
+            # The reference pads no row unless the mass of SOME row is below the threshold (`if (W_pad > 0).any()`, fsw_embedding.py:790):
+            # without a deficient row there is no pad element and no clamp on the path of the weights, so a row with m == tau exactly
+            # gets d out / d a_j = [R(rank_j) - sum_t H_t c_t] / m, without the kernel's [m <= tau] R(rank_pad) term.  Every m >= tau then,
+            # and with tau / 2 in place of tau the kernel computes the same coefficients and takes that branch.
+            csr, wv, tau = ctx.csr, ctx.aux[3], float(ctx.module.total_mass_pad_thresh)
+            m = torch.zeros(csr.num_rows, dtype=torch.float64, device=wv.device).index_add_(0, csr.rec, wv.double())
+            if not bool((m < tau).any()):
+                fields["tau"] = 0.5 * tau
         _GenericEmbedFn.launch(ctx.module, ctx.csr, ctx.aux, freqs.detach().contiguous(), ctx.out_scale, ctx.mass_scale_value,
-                               " (backward)", g=g.data_ptr(), ldg=g.stride(0),
+                               " (backward)", **fields, g=g.data_ptr(), ldg=g.stride(0),
                                gkey=gkey.data_ptr() if gkey is not None else None, ldk=gkey.shape[1] if gkey is not None else 0,
                                gfreq=gf.data_ptr() if gf is not None else None, gw=gw.data_ptr() if gw is not None else None)
 

@@ -179,7 +179,7 @@ typedef struct {
   /* projected features and slice parameters */
   const float* Xp;
   int64_t ldp;
-  const float* freqs; /* [S] */
+  const float* freqs; /* [S], any finite value of either sign: 0 and -0.0 take the linear branch, -1 yields out_scale * bias only */
   int32_t S;
   float tau;                 /* total_mass_pad_thresh */
   const float* unit_table;   /* from fsw_unit_coeff_table, required when w == NULL and tau <= 1 */
@@ -388,7 +388,7 @@ typedef struct {
   int64_t max_degree;    /* host value: an upper bound of the longest row */
   const void* Xp;
   int64_t ldp;
-  const void* freqs;     /* [F] */
+  const void* freqs;     /* [F], any finite value of either sign: 0 and -0.0 take the linear branch, -1 yields out_scale * bias only */
   double tau;
   const float* unit_table;
   int64_t ldt;

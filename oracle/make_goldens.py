@@ -356,6 +356,44 @@ def case_ties(emb):
     save("ties", **arrays)
 
 
+SIGNED_FREQS = (-13.0, -2.5, -1.0, -0.37, -1e-3, -0.0, 1e-3, 0.37, 2.5, 13.0)
+
+
+def case_signed_freqs(emb):
+    """Frequencies of both signs (tests/test_oracle_vs_golden.py::test_signed_frequencies): the reference accepts any finite
+    frequency (fsw_embedding.py:496-516, 568-582; with learnable_freqs the run-time check is for NaN/Inf only, :632-634).  Its
+    float64 autograd on a recipient x sender graph with rows of 1, 2, 7, 33, 40 and 50 neighbours (133 entries: the reference's
+    pure-torch segcumsum needs at least twice the longest row), unit weights, general weights with the row of 7 at total mass 0.4,
+    and the general weights again at tau = 3; the weights require grad in every mode."""
+    degs = np.array([1, 2, 7, 33, 40, 50], dtype=np.int64)
+    n, d, S, nrows = 60, 5, len(SIGNED_FREQS), degs.size
+    rec = np.repeat(np.arange(nrows), degs)
+    snd = np.concatenate([np.sort(np.argsort(synth.uniform01(121, r, 0, n))[:k]) for r, k in enumerate(degs)])
+    X0 = synth.features(n, d, seed=122)
+    V = synth.unit_slices(S, d, seed=123)
+    fr = np.array(SIGNED_FREQS, dtype=np.float32).astype(np.float64)         # frequencies and weights are float32 values, so that the
+    R = synth.normal(124, 1, (nrows, S), dtype=np.float64)                   # C oracle and the float32 modules read the same numbers
+    w = np.array([0.25, 0.5, 1.0])[synth.randint(125, 1, 3, rec.size)]
+    w[rec == 2] *= 0.4 / w[rec == 2].sum()
+    w = w.astype(np.float32).astype(np.float64)
+    arrays = dict(degrees=degs, senders=snd, X=X0, V=V, freqs=fr, R=R, w_general=w)
+    dt = torch.float64
+    idx = torch.from_numpy(np.stack([rec, snd]))
+    for tag, wv, tau in (("unit", np.ones(rec.size), 1.0), ("general", w, 1.0), ("general_tau3", w, 3.0)):
+        Em = emb.FSW_embedding(d_in=d, d_out=S, total_mass_pad_thresh=tau, learnable_slices=True, learnable_freqs=True, device="cpu",
+                               dtype=dt, load_custom_cuda_lib=False, enable_bias=False)
+        set_params(Em, V, fr)
+        assert np.array_equal(Em.freqs.detach().numpy(), fr) and np.signbit(Em.freqs.detach().numpy()[5])
+        vals = torch.from_numpy(wv.copy()).requires_grad_(True)
+        A = torch.sparse_coo_tensor(idx, vals, (nrows, n), is_coalesced=True)
+        X = T(X0, dt).requires_grad_(True)
+        out = Em(X, A, graph_mode=True)
+        (out * torch.from_numpy(R)).sum().backward()
+        arrays.update({"out_" + tag: out.detach().numpy(), "gX_" + tag: X.grad.numpy(), "gV_" + tag: Em.projVecs.grad.numpy(),
+                       "gfreqs_" + tag: Em.freqs.grad.numpy(), "gW_" + tag: vals.grad.numpy()})
+    save("signed_freqs", **arrays)
+
+
 def case_testconv64(emb, conv):
     """The configuration of the reference's own test_conv.py (:9-57) on deterministic inputs: float64, 100 vertices, 50 vertex /
     11 edge features, 35 outputs, three MLP layers, homogeneous degree encoding with the 'log' function and a learnable scale,
@@ -489,12 +527,14 @@ def main():
         case_grads_w(emb, conv)
     elif what == "ties":
         case_ties(emb)
+    elif what == "signed_freqs":
+        case_signed_freqs(emb)
     elif what == "testconv64":
         case_testconv64(emb, conv)
     elif what == "er1m":
         timings.update(case_er1m(emb, conv))
     else:
-        raise SystemExit("usage: python -m oracle.make_goldens [small|grads|grads_homog|coherence|edgefeat|grads_w|ties|testconv64|er1m]")
+        raise SystemExit("usage: python -m oracle.make_goldens [small|grads|grads_homog|coherence|edgefeat|grads_w|ties|signed_freqs|testconv64|er1m]")
     json.dump(timings, open(timings_path, "w"), indent=1, sort_keys=True)
 
 

@@ -64,8 +64,8 @@ def graph_case(beyond):
 
 
 @functools.lru_cache(maxsize=None)
-def inputs(S, F):
-    """Xp [SENDERS, round_up(S, 32)] float32, frequencies, bias, output gradient (for the graph with the row of BEYOND)."""
+def inputs(S, F, freqs=FREQS):
+    """Xp [SENDERS, round_up(S, 32)] float32, frequencies freqs[:F], bias, output gradient (for the graph with the row of BEYOND)."""
     rng = np.random.default_rng(72 + S)
     ldp = (S + 31) // 32 * 32
     Xp = rng.standard_normal((SENDERS, ldp)).astype(np.float32)
@@ -78,7 +78,7 @@ def inputs(S, F):
         elif kind == "e":                                           # ... but the control column: distinct, exact in float32
             Xp[:, c] = (rng.permutation(SENDERS).astype(np.float32) - 16500.0) / 4096.0
     assert np.unique(Xp[:, kinds.index("e")]).size == SENDERS and np.array_equal(Xp[pairs[0], 0], Xp[pairs[1], 0])
-    fr = np.array(FREQS[:F], dtype=np.float32)
+    fr = np.array(freqs[:F], dtype=np.float32)
     width = HAS_MASS + S * F
     bias = (0.1 * rng.standard_normal(width)).astype(np.float32)
     g = rng.standard_normal((len(DEGREES) + 1, width)).astype(np.float32)
@@ -88,10 +88,10 @@ def inputs(S, F):
 
 
 @functools.lru_cache(maxsize=None)
-def forward_reference(S, F):
+def forward_reference(S, F, freqs=FREQS):
     """The float64 oracle through the diagonal identity, on the graph with the row of BEYOND (its first rows are the other graph's):
     [rows, HAS_MASS + S F] with bias and out_scale."""
-    c, x = graph_case(True), inputs(S, F)
+    c, x = graph_case(True), inputs(S, F, freqs)
     X = x["Xp"][:, :S].astype(np.float64)
     V = np.repeat(np.eye(S), F, axis=0)
     emb, mass = O.fsw_embed_csr(X, c["rowptr"], c["col"], np.ones(c["nnz"]), V, np.tile(x["fr"].astype(np.float64), S), return_mass=True)
@@ -127,11 +127,11 @@ def unit_tables(fr, F, stream):
     return table, dtable
 
 
-def run_forward(c, S, F, scratch):
+def run_forward(c, S, F, scratch, freqs=FREQS):
     """(status, out) of fsw_embed_cart_f32; out pre-filled with NaN."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
-    x = inputs(S, F)
+    x = inputs(S, F, freqs)
     stream = torch.cuda.current_stream(DEV).cuda_stream
     Xp, fr, bias = t(x["Xp"]), t(x["fr"]), t(x["bias"])
     table, _ = unit_tables(fr, F, stream)
@@ -184,9 +184,14 @@ def test_backward(S, F):
     """fsw_embed_cart_backward_keys_f32 with the scratch of fsw_embed_cart_backward_scratch_bytes and with the smallest scratch that
     was valid before (fsw_embed_cart_generic_scratch_bytes(max_degree, 1)): bit-identical gkey; against the generic kernel with
     float64 storage per row <= F32_BOUND, per entry <= PER_ENTRY of the line maximum, gfreq <= F32_BOUND."""
+    check_backward(S, F)
+
+
+def check_backward(S, F, freqs=FREQS):
+    """The body of test_backward at the frequencies freqs[:F]."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
-    c, x = graph_case(False), inputs(S, F)
+    c, x = graph_case(False), inputs(S, F, freqs)
     nnz, nrows, rowptr = c["nnz"], len(DEGREES), c["rowptr"]
     stream = torch.cuda.current_stream(DEV).cuda_stream
     g_host = x["g"][:nrows]

@@ -77,8 +77,8 @@ def graph_case(mode, beyond):
 
 
 @functools.lru_cache(maxsize=None)
-def inputs(S, F):
-    """Xp [SENDERS, round_up(S, 32)] float32, frequencies, bias, output gradient (for the graph with the row of BEYOND)."""
+def inputs(S, F, freqs=FREQS):
+    """Xp [SENDERS, round_up(S, 32)] float32, frequencies freqs[:F], bias, output gradient (for the graph with the row of BEYOND)."""
     rng = np.random.default_rng(82 + S)
     ldp = (S + 31) // 32 * 32
     Xp = rng.standard_normal((SENDERS, ldp)).astype(np.float32)
@@ -93,7 +93,7 @@ def inputs(S, F):
         elif kind == "e":                                           # ... but the control column: distinct, exact in float32
             Xp[:, c] = (rng.permutation(SENDERS).astype(np.float32) - 8500.0) / 4096.0
     assert np.unique(Xp[:, kinds.index("e")]).size == SENDERS and np.array_equal(Xp[pairs[0], 0], Xp[pairs[1], 0])
-    fr = np.array(FREQS[:F], dtype=np.float32)
+    fr = np.array(freqs[:F], dtype=np.float32)
     width = HAS_MASS + S * F
     bias = (0.1 * rng.standard_normal(width)).astype(np.float32)
     g = rng.standard_normal((len(DEGREES) + 1, width)).astype(np.float32)
@@ -103,10 +103,10 @@ def inputs(S, F):
 
 
 @functools.lru_cache(maxsize=None)
-def forward_reference(mode, S, F):
+def forward_reference(mode, S, F, freqs=FREQS):
     """The float64 oracle with the graph's weights and tau through the diagonal identity, on the graph with the row of BEYOND (its
     first rows are the other graph's): [rows, HAS_MASS + S F] with bias and out_scale."""
-    c, x = graph_case(mode, True), inputs(S, F)
+    c, x = graph_case(mode, True), inputs(S, F, freqs)
     X = x["Xp"][:, :S].astype(np.float64)
     V = np.repeat(np.eye(S), F, axis=0)
     emb, mass = O.fsw_embed_csr(X, c["rowptr"], c["col"], c["w64"], V, np.tile(x["fr"].astype(np.float64), S),
@@ -127,11 +127,11 @@ def weighted_args(c, x, S, F, Xp, fr, scratch, dtype=0):
     return a, keep
 
 
-def run_forward(c, S, F, scratch):
+def run_forward(c, S, F, scratch, freqs=FREQS):
     """(status, out) of fsw_embed_cart_f32; out pre-filled with NaN."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
-    x = inputs(S, F)
+    x = inputs(S, F, freqs)
     stream = torch.cuda.current_stream(DEV).cuda_stream
     Xp, fr, bias = t(x["Xp"]), t(x["fr"]), t(x["bias"])
     out = torch.full((len(c["degrees"]), HAS_MASS + S * F), float("nan"), device=DEV)
@@ -175,9 +175,14 @@ def test_backward(mode, S, F):
     that was valid before (fsw_embed_cart_generic_scratch_bytes(max_degree, 1)): bit-identical gkey, finite everywhere (gkey is
     pre-filled with NaN: neither the pad element nor the fill elements leave one); against the generic kernel with float64 storage per
     row <= F32_BOUND, per entry <= PER_ENTRY of the line maximum, gfreq <= F32_BOUND."""
+    check_backward(mode, S, F)
+
+
+def check_backward(mode, S, F, freqs=FREQS):
+    """The body of test_backward at the frequencies freqs[:F]."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
-    c, x = graph_case(mode, False), inputs(S, F)
+    c, x = graph_case(mode, False), inputs(S, F, freqs)
     nnz, nrows, rowptr = c["nnz"], len(DEGREES), c["rowptr"]
     stream = torch.cuda.current_stream(DEV).cuda_stream
     g_host = x["g"][:nrows]

@@ -82,14 +82,14 @@ def edge_list(weights):
     return rec[order], snd[order], None if w is None else w[order]
 
 
-def key_columns(rowptr):
-    """float32 keys [NNZ, len(COLUMNS)] per CSR entry, column c of kind COLUMNS[c]."""
+def key_columns(rowptr, kinds=COLUMNS):
+    """float32 keys [NNZ, len(kinds)] per CSR entry, column c of kind kinds[c]."""
     rng = np.random.default_rng(42)
     deg = np.diff(rowptr)
     pos = np.arange(NNZ) - np.repeat(rowptr[:-1], deg)              # position of the entry in its row
     last = np.repeat(deg, deg) - 1 - pos
-    K = np.empty((NNZ, len(COLUMNS)), dtype=np.float32)
-    for c, kind in enumerate(COLUMNS):
+    K = np.empty((NNZ, len(kinds)), dtype=np.float32)
+    for c, kind in enumerate(kinds):
         if kind == "a":
             K[:, c] = 0.75
         elif kind == "b":
@@ -108,7 +108,8 @@ def key_columns(rowptr):
                     dup = np.setdiff1d(np.arange(b - a), first)
                     v[a + dup] = rng.standard_normal(dup.size).astype(np.float32)
             K[:, c] = v
-    assert np.signbit(K[:, 1]).any() and not np.signbit(K[:, 1]).all()
+    if kinds[1] == "b":
+        assert np.signbit(K[:, 1]).any() and not np.signbit(K[:, 1]).all()
     return K
 
 
@@ -137,9 +138,9 @@ def per_row(fn, rowptr):
 
 def coefficient_scale(G, freqs):
     """[rows, len(freqs)]: |G| times the size of the two values F(xi; c) = (1 + xi) sin(2 pi xi c) / (pi xi) whose difference a
-    coefficient is, min(2, 1 / (pi xi)) (1 + xi)."""
+    coefficient is, min(2, 1 / (pi |xi|)) |1 + xi| (frequencies of either sign)."""
     xi = np.asarray(freqs, dtype=np.float64)
-    return np.abs(G) * ((1 + xi) * np.minimum(2.0, 1.0 / (np.pi * np.maximum(xi, 1e-300))))[None, :]
+    return np.abs(G) * (np.abs(1 + xi) * np.minimum(2.0, 1.0 / (np.pi * np.maximum(np.abs(xi), 1e-300))))[None, :]
 
 
 def check_key_gradients(got, ref, rowptr, columns, what, scale, row_bound=F32_BOUND, entry_bound=PER_ENTRY, floor=1e-6):
@@ -169,7 +170,7 @@ def check_key_gradients(got, ref, rowptr, columns, what, scale, row_bound=F32_BO
 
 # ---- the graph on the device and the oracle's answers, computed once per weight mode ----------------------------------------------
 @functools.lru_cache(maxsize=None)
-def tied_case(weights):
+def tied_case(weights, kinds=COLUMNS):
     from fsw_gnn_amd import _lib, build_csr
     dev = torch.device("cuda:0")
     rec, snd, w = edge_list(weights)
@@ -191,18 +192,21 @@ def tied_case(weights):
         for deg in LOW_MASS_ROWS:
             r = DEGREES.index(deg)
             assert abs(wv[rowptr[r]:rowptr[r + 1]].sum() - 0.4) < 1e-5
-    K = key_columns(rowptr)
+    K = key_columns(rowptr, kinds)
     Xp = np.zeros((NNZ, 64), dtype=np.float32)
     Xp[col, :K.shape[1]] = K                                       # sender col[e] carries the keys of entry e
     g = np.random.default_rng(43).standard_normal((len(DEGREES), HAS_MASS + 20)).astype(np.float32)
+    more = np.random.default_rng(44).standard_normal((len(DEGREES), 12)).astype(np.float32)     # columns 21 .. 32: Cartesian 4 x 8
+    g = np.concatenate([g, more], axis=1)
     return {"graph": graph, "st": st, "rowptr": rowptr, "col": col, "w": wv, "K": K, "Xp": Xp, "g": g}
 
 
 @functools.lru_cache(maxsize=None)
-def diagonal_reference(weights, tau, S):
-    """Oracle (float64, entry order among equal keys) on the first S key columns: out [rows, 1 + S], gkey [nnz, S], gfreq [S]."""
-    c = tied_case(weights)
-    K, fr, rowptr = c["K"][:, :S].astype(np.float64), np.array(FREQS[:S]), c["rowptr"]
+def diagonal_reference(weights, tau, S, freqs=FREQS, kinds=COLUMNS):
+    """Oracle (float64, entry order among equal keys) on the first S key columns (of kind kinds[:S], at freqs[:S]): out [rows, 1 + S],
+    gkey [nnz, S], gfreq [S]."""
+    c = tied_case(weights, kinds)
+    K, fr, rowptr = c["K"][:, :S].astype(np.float64), np.array(freqs[:S]), c["rowptr"]
     ident = np.arange(NNZ)                                         # the oracle's "features" are the keys of every entry
     emb, mass = O.fsw_embed_csr(K, rowptr, ident, c["w"], np.eye(S), fr, total_mass_pad_thresh=tau, return_mass=True)
     G = OUT_SCALE * c["g"][:, HAS_MASS:HAS_MASS + S].astype(np.float64)
@@ -213,19 +217,20 @@ def diagonal_reference(weights, tau, S):
 
 
 @functools.lru_cache(maxsize=None)
-def cartesian_reference(weights, tau, cols, F):
-    """The oracle through the diagonal identity of tests/test_cartesian_cpu.py: key column s repeated F times, freqs tiled;
-    gkey[e, s] is the sum over f."""
-    c = tied_case(weights)
+def cartesian_reference(weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS):
+    """The oracle through the diagonal identity of tests/test_cartesian_cpu.py: key column s repeated F times, freqs[:F] tiled;
+    gkey[e, s] is the sum over f, gkey_sf [nnz, S, F] its terms."""
+    c = tied_case(weights, kinds)
     S, rowptr = len(cols), c["rowptr"]
     K = np.repeat(c["K"][:, list(cols)].astype(np.float64), F, axis=1)        # column s F + f = key column s
-    fr = np.tile(np.array(FREQS[:F]), S)
+    fr = np.tile(np.array(freqs[:F]), S)
     ident = np.arange(NNZ)
     emb, mass = O.fsw_embed_csr(K, rowptr, ident, c["w"], np.eye(S * F), fr, total_mass_pad_thresh=tau, return_mass=True)
     G = OUT_SCALE * c["g"][:, HAS_MASS:HAS_MASS + S * F].astype(np.float64)
     _, _, gxi, gkey = O.fsw_embed_csr_backward(K, rowptr, ident, c["w"], np.eye(S * F), fr, G, total_mass_pad_thresh=tau, return_gkey=True)
     return {"out": OUT_SCALE * np.concatenate([mass[:, None], emb], axis=1), "gkey": gkey.reshape(NNZ, S, F).sum(axis=2),
-            "gfreq": gxi.reshape(S, F).sum(axis=0), "scale": coefficient_scale(G, fr).reshape(-1, S, F).sum(axis=2)}
+            "gfreq": gxi.reshape(S, F).sum(axis=0), "scale": coefficient_scale(G, fr).reshape(-1, S, F).sum(axis=2),
+            "gkey_sf": gkey.reshape(NNZ, S, F)}
 
 
 def check_forward(got, ref, what):
@@ -253,24 +258,16 @@ def embed_args(c, S, tau, fr, table, scratch):
     return a
 
 
-@pytest.mark.parametrize("S", [8, 6])
-@pytest.mark.parametrize("weights,tau", MODES)
-def test_tuned_kernels_on_tied_keys(dev, weights, tau, S):
-    """fsw_embed_f32, fsw_embed_backward_f32 (atomics) and fsw_embed_backward_keys_f32 (stored key gradients: unit weights with the
-    coefficient tables = the store-and-sum form, the other modes without) on the graph of DEGREES and the key columns COLUMNS[:S].
-    S = 8: rows of 129 .. 2048 neighbours take k_embed_quad_bwd in the store form; S = 6: k_embed_wsort_bwd.  unit / tau = 3 runs the
-    general kernels with w == NULL; 'random' weights hold exact zeros and three rows of total mass 0.4, whose pad element ties with
-    every zero key (all keys of column b).
-    Forward per row <= TOL; gkey of both forms against the oracle and against each other: finite (gkey is pre-filled with NaN), per
-    row <= F32_BOUND, per entry <= PER_ENTRY of the line maximum; gfreq <= F32_BOUND."""
+def run_tuned_kernels(dev, weights, tau, S, freqs=FREQS, kinds=COLUMNS):
+    """fsw_embed_f32, fsw_embed_backward_f32 and fsw_embed_backward_keys_f32 on the graph of DEGREES, key columns kinds[:S], frequencies
+    freqs[:S]: (out [rows, 1 + S], gkey read back from the atomic form [nnz, S], stored gkey [nnz, S], {name: gfreq [S]}), float64."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
-    c = dict(tied_case(weights))
-    ref = diagonal_reference(weights, tau, S)
-    rowptr, col, graph = c["rowptr"], c["col"], c["graph"]
+    c = dict(tied_case(weights, kinds))
+    col = c["col"]
     stream = torch.cuda.current_stream(dev).cuda_stream
     c["Xp_dev"] = t(c["Xp"], dev)
-    fr = t(np.array(FREQS[:S]), dev)
+    fr = t(np.array(freqs[:S]), dev)
     g = t(c["g"][:, :HAS_MASS + S], dev)
     unit_fast = weights == "unit" and tau <= 1.0
     table = dtable = None
@@ -280,14 +277,12 @@ def test_tuned_kernels_on_tied_keys(dev, weights, tau, S):
         _lib.check(L.fsw_unit_coeff_table(_lib.ptr(fr), S, _lib.REG_MAX_DEG, _lib.ptr(table), 64, stream), "fsw_unit_coeff_table")
         _lib.check(L.fsw_unit_dcoeff_table(_lib.ptr(fr), S, _lib.REG_MAX_DEG, _lib.ptr(dtable), 64, stream), "fsw_unit_dcoeff_table")
     scratch = torch.empty(int(L.fsw_embed_scratch_bytes(max(DEGREES))), dtype=torch.uint8, device=dev)
-    what = "%s tau %g S %d" % (weights, tau, S)
 
     out = torch.full((len(DEGREES), HAS_MASS + S), float("nan"), device=dev)
     a = embed_args(c, S, tau, fr, table, scratch)
     a.out, a.ldo = out.data_ptr(), out.stride(0)
     _lib.check(L.fsw_embed_f32(ctypes.byref(a), stream), "fsw_embed_f32")
     torch.cuda.synchronize()
-    check_forward(out.cpu().numpy().astype(np.float64), ref["out"], what)
 
     a = embed_args(c, S, tau, fr, table, scratch)
     gXp = torch.zeros((NNZ, 64), device=dev)
@@ -302,35 +297,46 @@ def test_tuned_kernels_on_tied_keys(dev, weights, tau, S):
     atomic = gXp.cpu().numpy().astype(np.float64)
     assert np.abs(atomic[:, S:]).max() == 0.0
     atomic = atomic[col, :S]                                       # every sender has one entry: its gXp row is that entry's key gradient
-    keys = gkey.cpu().numpy().astype(np.float64)
+    return (out.cpu().numpy().astype(np.float64), atomic, gkey.cpu().numpy().astype(np.float64),
+            {"atomics": gf_atomic.cpu().numpy(), "stored": gf_keys.cpu().numpy()})
+
+
+@pytest.mark.parametrize("S", [8, 6])
+@pytest.mark.parametrize("weights,tau", MODES)
+def test_tuned_kernels_on_tied_keys(dev, weights, tau, S):
+    """fsw_embed_f32, fsw_embed_backward_f32 (atomics) and fsw_embed_backward_keys_f32 (stored key gradients: unit weights with the
+    coefficient tables = the store-and-sum form, the other modes without) on the graph of DEGREES and the key columns COLUMNS[:S].
+    S = 8: rows of 129 .. 2048 neighbours take k_embed_quad_bwd in the store form; S = 6: k_embed_wsort_bwd.  unit / tau = 3 runs the
+    general kernels with w == NULL; 'random' weights hold exact zeros and three rows of total mass 0.4, whose pad element ties with
+    every zero key (all keys of column b).
+    Forward per row <= TOL; gkey of both forms against the oracle and against each other: finite (gkey is pre-filled with NaN), per
+    row <= F32_BOUND, per entry <= PER_ENTRY of the line maximum; gfreq <= F32_BOUND."""
+    ref = diagonal_reference(weights, tau, S)
+    rowptr = tied_case(weights)["rowptr"]
+    what = "%s tau %g S %d" % (weights, tau, S)
+    out, atomic, keys, gfreq = run_tuned_kernels(dev, weights, tau, S)
+    check_forward(out, ref["out"], what)
     check_key_gradients(atomic, ref["gkey"], rowptr, COLUMNS[:S], what + " atomics", ref["scale"])
     check_key_gradients(keys, ref["gkey"], rowptr, COLUMNS[:S], what + " stored", ref["scale"])
     check_key_gradients(keys, atomic, rowptr, COLUMNS[:S], what + " stored vs atomics", ref["scale"])
-    for name, gf in (("atomics", gf_atomic), ("stored", gf_keys)):
-        e = relerr(gf.cpu().numpy(), ref["gfreq"])
+    for name, gf in gfreq.items():
+        e = relerr(gf, ref["gfreq"])
         print("%s %s: gfreq %.2e" % (what, name, e))
         assert e <= F32_BOUND, (what, name, e)
 
 
-@pytest.mark.parametrize("storage", ["float64", "float32"])
-@pytest.mark.parametrize("weights,tau", MODES)
-def test_generic_kernel_on_tied_keys(dev, weights, tau, storage):
-    """fsw_embed_generic (the yardstick of the Cartesian and weight-gradient tests) on the same plain CSR and the 8 key columns,
-    forward and backward: float64 storage per row <= G64_ROW (forward and gkey) and per entry 1e-10 of the line maximum; float32 storage at
-    the bounds of the tuned kernels.
-    The float64 per-entry check floors the line maximum at 2e-4 of the line's scale: the oracle itself evaluates sin(pi xi w) with
-    an argument rounded to float64, an absolute error of 2 pi xi 2^-53 <= 1e-14 of the scale at xi = 13, i.e. 1e-10 of a line of
-    1e-4 of the scale (measured on the vanishing lines, where the kernel's sinpi returns an exact 0: 5.9e-15 of the scale)."""
+def run_generic_kernel(dev, weights, tau, storage, freqs=FREQS, kinds=COLUMNS):
+    """fsw_embed_generic, forward and backward, on the plain CSR of the graph of DEGREES, the 8 key columns `kinds` and frequencies
+    `freqs`: (out [rows, 9], gkey [nnz, 8], gfreq [8]) in the storage type."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
     S = 8
-    c = tied_case(weights)
-    ref = diagonal_reference(weights, tau, S)
-    graph, rowptr = c["graph"], c["rowptr"]
+    c = tied_case(weights, kinds)
+    graph = c["graph"]
     dt = torch.float64 if storage == "float64" else torch.float32
     stream = torch.cuda.current_stream(dev).cuda_stream
     Xp = t(c["Xp"], dev, dt)
-    fr = t(np.array(FREQS[:S]), dev, dt)
+    fr = t(np.array(freqs[:S]), dev, dt)
     g = t(c["g"][:, :HAS_MASS + S], dev, dt)
     w = graph.w[:NNZ].to(dt).contiguous() if graph.w is not None else None
     scratch = torch.empty(int(L.fsw_embed_generic_scratch_bytes(max(DEGREES), len(DEGREES))), dtype=torch.uint8, device=dev)
@@ -354,19 +360,34 @@ def test_generic_kernel_on_tied_keys(dev, weights, tau, storage):
     _lib.check(L.fsw_embed_generic(ctypes.byref(args(g=g.data_ptr(), ldg=g.stride(0), gkey=gkey.data_ptr(), ldk=S, gfreq=gf.data_ptr())),
                                    stream), "fsw_embed_generic (backward)")
     torch.cuda.synchronize()
+    return out.cpu().numpy().astype(np.float64), gkey.cpu().numpy().astype(np.float64), gf.cpu().numpy()
+
+
+@pytest.mark.parametrize("storage", ["float64", "float32"])
+@pytest.mark.parametrize("weights,tau", MODES)
+def test_generic_kernel_on_tied_keys(dev, weights, tau, storage):
+    """fsw_embed_generic (the yardstick of the Cartesian and weight-gradient tests) on the same plain CSR and the 8 key columns,
+    forward and backward: float64 storage per row <= G64_ROW (forward and gkey) and per entry 1e-10 of the line maximum; float32 storage at
+    the bounds of the tuned kernels.
+    The float64 per-entry check floors the line maximum at 2e-4 of the line's scale: the oracle itself evaluates sin(pi xi w) with
+    an argument rounded to float64, an absolute error of 2 pi xi 2^-53 <= 1e-14 of the scale at xi = 13, i.e. 1e-10 of a line of
+    1e-4 of the scale (measured on the vanishing lines, where the kernel's sinpi returns an exact 0: 5.9e-15 of the scale)."""
+    S = 8
+    ref = diagonal_reference(weights, tau, S)
+    rowptr = tied_case(weights)["rowptr"]
+    got, gkey, gf = run_generic_kernel(dev, weights, tau, storage)
     what = "generic %s %s tau %g" % (storage, weights, tau)
-    got = out.cpu().numpy().astype(np.float64)
     if storage == "float64":
         errs = np.array([relerr(got[r], ref["out"][r]) for r in range(len(DEGREES))])
         print("%s: forward per row max %.2e" % (what, errs.max()))
         assert np.isfinite(got).all() and errs.max() <= G64_ROW, (what, errs)
-        check_key_gradients(gkey.cpu().numpy(), ref["gkey"], rowptr, COLUMNS[:S], what, ref["scale"], row_bound=G64_ROW, entry_bound=G64_ROW,
+        check_key_gradients(gkey, ref["gkey"], rowptr, COLUMNS[:S], what, ref["scale"], row_bound=G64_ROW, entry_bound=G64_ROW,
                             floor=2e-4)
-        assert relerr(gf.cpu().numpy(), ref["gfreq"]) <= G64_ROW
+        assert relerr(gf, ref["gfreq"]) <= G64_ROW
     else:
         check_forward(got, ref["out"], what)
-        check_key_gradients(gkey.cpu().numpy().astype(np.float64), ref["gkey"], rowptr, COLUMNS[:S], what, ref["scale"])
-        e = relerr(gf.cpu().numpy(), ref["gfreq"])
+        check_key_gradients(gkey, ref["gkey"], rowptr, COLUMNS[:S], what, ref["scale"])
+        e = relerr(gf, ref["gfreq"])
         print("%s: gfreq %.2e" % (what, e))
         assert e <= F32_BOUND, (what, e)
 
@@ -374,25 +395,20 @@ def test_generic_kernel_on_tied_keys(dev, weights, tau, storage):
 CART_COLUMNS = [(0, 1, 2, 5), (3, 4, 6, 5)]      # indices into COLUMNS: (a, b, c, e) and (d_up, d_down, b, e)
 
 
-@pytest.mark.parametrize("cols", CART_COLUMNS)
-@pytest.mark.parametrize("weights,tau", MODES)
-def test_cartesian_kernels_on_tied_keys(dev, weights, tau, cols):
-    """fsw_embed_cart_f32 and fsw_embed_cart_backward_keys_f32, S = 4 slices x F = 5 frequencies, on the same graph and key columns
-    (two sets of four, each with the control column); the rows above 2048 neighbours run the generic kernel inside these entries.
-    Same per-row, per-entry and gfreq assertions as the diagonal kernels."""
+def run_cartesian_kernels(dev, weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS):
+    """fsw_embed_cart_f32 and fsw_embed_cart_backward_keys_f32, S = len(cols) slices (key columns cols of `kinds`) x F frequencies
+    freqs[:F], on the graph of DEGREES: (out [rows, 1 + S F], gkey [nnz, S], gfreq [F])."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
-    S, F = 4, 5
-    c = tied_case(weights)
-    ref = cartesian_reference(weights, tau, cols, F)
-    graph, st, rowptr = c["graph"], c["st"], c["rowptr"]
+    S = len(cols)
+    c = tied_case(weights, kinds)
+    graph, st = c["graph"], c["st"]
     stream = torch.cuda.current_stream(dev).cuda_stream
     Xp_host = np.zeros((NNZ, 32), dtype=np.float32)
     Xp_host[:, :S] = c["Xp"][:, list(cols)]
     Xp = t(Xp_host, dev)
-    fr = t(np.array(FREQS[:F]), dev)
+    fr = t(np.array(freqs[:F]), dev)
     g = t(c["g"][:, :HAS_MASS + S * F], dev)
-    names = [COLUMNS[i] for i in cols]
     unit_fast = weights == "unit" and tau <= 1.0
     table = dtable = None
     if unit_fast:
@@ -415,7 +431,6 @@ def test_cartesian_kernels_on_tied_keys(dev, weights, tau, cols):
         a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
         return a
 
-    what = "cartesian %s tau %g columns %s" % (weights, tau, ",".join(names))
     out = torch.full((len(DEGREES), HAS_MASS + S * F), float("nan"), device=dev)
     a = args()
     a.out, a.ldo = out.data_ptr(), out.stride(0)
@@ -426,9 +441,24 @@ def test_cartesian_kernels_on_tied_keys(dev, weights, tau, cols):
     a.g, a.ldg, a.gkey, a.ldk, a.gfreq = g.data_ptr(), g.stride(0), gkey.data_ptr(), S, gf.data_ptr()
     _lib.check(L.fsw_embed_cart_backward_keys_f32(ctypes.byref(a), _lib.ptr(dtable), F, stream), "fsw_embed_cart_backward_keys_f32")
     torch.cuda.synchronize()
-    check_forward(out.cpu().numpy().astype(np.float64), ref["out"], what)
-    check_key_gradients(gkey.cpu().numpy().astype(np.float64), ref["gkey"], rowptr, names, what, ref["scale"])
-    e = relerr(gf.cpu().numpy(), ref["gfreq"])
+    return out.cpu().numpy().astype(np.float64), gkey.cpu().numpy().astype(np.float64), gf.cpu().numpy()
+
+
+@pytest.mark.parametrize("cols", CART_COLUMNS)
+@pytest.mark.parametrize("weights,tau", MODES)
+def test_cartesian_kernels_on_tied_keys(dev, weights, tau, cols):
+    """fsw_embed_cart_f32 and fsw_embed_cart_backward_keys_f32, S = 4 slices x F = 5 frequencies, on the same graph and key columns
+    (two sets of four, each with the control column); the rows above 2048 neighbours run the generic kernel inside these entries.
+    Same per-row, per-entry and gfreq assertions as the diagonal kernels."""
+    F = 5
+    ref = cartesian_reference(weights, tau, cols, F)
+    rowptr = tied_case(weights)["rowptr"]
+    names = [COLUMNS[i] for i in cols]
+    what = "cartesian %s tau %g columns %s" % (weights, tau, ",".join(names))
+    out, gkey, gf = run_cartesian_kernels(dev, weights, tau, cols, F)
+    check_forward(out, ref["out"], what)
+    check_key_gradients(gkey, ref["gkey"], rowptr, names, what, ref["scale"])
+    e = relerr(gf, ref["gfreq"])
     print("%s: gfreq %.2e" % (what, e))
     assert e <= F32_BOUND, (what, e)
 

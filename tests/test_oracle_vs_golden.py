@@ -232,3 +232,34 @@ def test_tied_keys_contract(tag):
             direct[a:b, s] = (R[r, s] * (1 + fr[s]) * delta)[:-1]
     assert np.abs(sums - g["tie_sums_" + tag])[valid].max() <= 1e-12 * scale
     assert np.abs(direct - gkey).max() <= 1e-12 * scale
+
+
+def test_signed_frequencies():
+    """Frequencies of both signs (tests/golden/signed_freqs.npz, oracle/make_goldens.py::case_signed_freqs): the reference's float64
+    autograd at xi = -13 .. 13 with -1, -0.0 and +-1e-3 among them, rows of 1 .. 50 neighbours, unit weights, general weights with a
+    row of total mass 0.4, and the general weights at tau = 3.  Python oracle forward and backward, C oracle forward (the fixture's
+    inputs are float32 values, which the C oracle reads).  Every coefficient carries the factor (1 + xi): the column at xi = -1 is
+    exactly zero in the reference and in both oracles.  The oracle has no dL/dW: gW is compared on the GPU
+    (tests/test_hip_signed_freqs.py)."""
+    from oracle import c_oracle as C
+    g = golden("signed_freqs")
+    degs, snd, X, V, fr, R = g["degrees"], g["senders"], g["X"], g["V"], g["freqs"], g["R"]
+    rowptr = np.concatenate([[0], np.cumsum(degs)])
+    assert (fr < 0).sum() == 5 and np.signbit(fr[5]) and fr[5] == 0 and fr[2] == -1.0 and 2 * degs.max() <= snd.size
+    mass = np.add.reduceat(g["w_general"], rowptr[:-1])
+    assert abs(mass[2] - 0.4) < 1e-7 and (mass[3:] > 3).all()
+    for tag, w, tau in (("unit", np.ones(snd.size), 1.0), ("general", g["w_general"], 1.0), ("general_tau3", g["w_general"], 3.0)):
+        ref = g["out_" + tag]
+        assert np.abs(ref[:, 2]).max() == 0.0 and np.abs(ref[:, [0, 1, 3, 4]]).min() > 0
+        out = O.fsw_embedding_forward(X, rowptr, snd, w, V, fr, total_mass_pad_thresh=tau)
+        assert relerr(out, ref) < TOL64, tag
+        cout = C.embed(X, rowptr, snd, w, V, fr, tau=tau)
+        assert relerr(cout, ref) < TOL64, tag
+        assert np.abs(out[:, 2]).max() == 0.0 and np.abs(cout[:, 2]).max() == 0.0
+        for c in range(fr.size):                                       # per column: no frequency hides in a row norm
+            if c != 2:
+                assert relerr(out[:, c], ref[:, c]) < TOL64 and relerr(cout[:, c], ref[:, c]) < TOL64, (tag, c)
+        gX, gV, gxi = O.fsw_embed_csr_backward(X, rowptr, snd, w, V, fr, R, total_mass_pad_thresh=tau)
+        assert relerr(gX, g["gX_" + tag]) < 1e-10 and relerr(gV, g["gV_" + tag]) < 1e-10, tag
+        assert relerr(gxi, g["gfreqs_" + tag]) < 1e-10 and np.abs(gxi - g["gfreqs_" + tag]).max() < 1e-10 * np.abs(gxi).max(), tag
+        assert g["gfreqs_" + tag][2] != 0 and np.abs(gV[2]).max() == 0.0 and np.abs(g["gV_" + tag][2]).max() == 0.0
