@@ -1,4 +1,4 @@
-// What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip) and the tuned backward (embed_cart_bwd.hip,
+// What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_giant_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
 // embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip) of Cartesian mode share: the degree classes, the
 // constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
 #pragma once
@@ -58,8 +58,9 @@ int for_each_wave_group(const int32_t* bs, int extra, Fn fn) {
 }
 
 // ---- the classes of the rows whose line is longer than kCartMaxLine elements: THE table (DESIGN.md prints it too) ---------------
-// Everything that decides which rows a class takes reads it: the four launchers of embed_cart_hub*.hip, launch_cart_long_rows and
-// the scratch sizes (fsw_embed_cart_scratch_bytes, which the host layer calls).
+// Everything that decides which rows a class takes reads it: the four launchers of embed_cart_hub*.hip, the two of embed_giant_cart*.hip,
+// launch_cart_long_rows and the scratch sizes (fsw_embed_cart_scratch_bytes and fsw_embed_cart_forward_scratch_bytes, which the host
+// layer calls).
 struct CartLongClass {
   int bin_lo, bin_hi;   // the degree bins its rows lie in
   int dlo, dhi;         // its rows: dlo < D <= dhi
@@ -70,7 +71,9 @@ struct CartLongMode {
   int pad;              // elements of a line next to the D neighbours: the pad element of general weights
   int num;              // classes
   CartLongClass cls[FSW_NUM_HUB_BINS];
-  int generic_bin, generic_min_degree;   // rows of generic_min_degree neighbours and more (they begin in generic_bin): the generic kernel
+  int generic_bin, generic_min_degree;   // backward: rows of generic_min_degree neighbours and more (they begin in generic_bin): the generic kernel
+  int giant_bin, giant_min_degree;       // forward: rows of giant_min_degree neighbours and more (they begin in giant_bin): sorted blocks in a
+                                         // scratch line (embed_giant_cart.hip: k_cart_giant, embed_giant_cart_w.hip: k_cart_mergepath_w)
   constexpr const CartLongClass& last() const { return cls[num - 1]; }
 };
 constexpr int kCartLastLdsBin = FSW_BIN_HUB0 - 1;             // rows of 1025 .. FSW_LDS_MAX_DEG neighbours
@@ -81,13 +84,13 @@ constexpr CartLongMode kCartLong[2] = {
       {FSW_BIN_HUB0 + 1, FSW_BIN_HUB0 + 1, 4096, 8192, 4, true},
       {FSW_BIN_HUB0 + 2, FSW_BIN_HUB0 + 2, 8192, 16384, 8, true},
       {FSW_BIN_HUB0 + 3, FSW_BIN_HUB0 + 3, 16384, 32768, 16, true}},
-     FSW_BIN_GLOBAL, 32769},
+     FSW_BIN_GLOBAL, 32769, FSW_BIN_GLOBAL, 32769},
     // general weights (w != NULL or tau > 1): lines of D + 1 elements, so every class ends one neighbour below a bin's end
     {1, 3,
      {{kCartLastLdsBin, FSW_BIN_HUB0, 2047, 4095, 2, true},
       {FSW_BIN_HUB0, FSW_BIN_HUB0 + 1, 4095, 8191, 4, true},
       {FSW_BIN_HUB0 + 1, FSW_BIN_HUB0 + 2, 8191, 16383, 8, true}},
-     FSW_BIN_HUB0 + 2, 16384},
+     FSW_BIN_HUB0 + 2, 16384, FSW_BIN_HUB0 + 2, 16384},
 };
 constexpr const CartLongMode& cart_long_mode(bool unit_fast) { return kCartLong[unit_fast ? 0 : 1]; }
 inline bool cart_unit_fast(const fsw_cart_args* c) { return c->w == nullptr && c->tau <= 1.0; }
@@ -96,6 +99,8 @@ constexpr bool cart_long_table_ok(const CartLongMode& m, int max_line) {
   if (m.cls[0].dlo + m.pad != kCartMaxLine || m.last().dhi + m.pad != max_line) return false;   // from the wavefront path to max_line
   if (m.generic_min_degree != m.last().dhi + 1) return false;
   if (bin_upper_degree(m.generic_bin - 1) >= m.generic_min_degree || m.generic_min_degree > bin_upper_degree(m.generic_bin)) return false;
+  if (m.giant_min_degree != m.last().dhi + 1) return false;                                     // the forward leaves no row without a class
+  if (bin_upper_degree(m.giant_bin - 1) >= m.giant_min_degree || m.giant_min_degree > bin_upper_degree(m.giant_bin)) return false;
   for (int i = 0; i < m.num; ++i) {
     const CartLongClass& k = m.cls[i];
     if (k.nw != 2 << i || (i > 0 && k.dlo != m.cls[i - 1].dhi)) return false;                   // the launchers index by i
@@ -145,7 +150,52 @@ int for_each_cart_line_bin(const fsw_cart_args* c, const CartLongMode& m, Fn fn)
 int launch_cart_hub(const fsw_cart_args* c, hipStream_t stream), launch_cart_hub_bwd(const fsw_cart_args* c, hipStream_t stream);
 int launch_cart_hub_w(const fsw_cart_args* c, hipStream_t stream), launch_cart_hub_w_bwd(const fsw_cart_args* c, hipStream_t stream);
 
-// Rows the classes do not take (float32 storage): the generic kernel, forward or, with c->g, backward.
+// ---- forward of the giant class (rows of giant_min_degree neighbours and more): one workgroup per (row, slice) line, the line in sorted
+// blocks in the workgroup's scratch line ------------------------------------------------------------------------------------------------
+constexpr int kCartGiantNW = 16;                              // unit weights: wavefronts of a workgroup, kCartLongM keys per lane each
+constexpr int kCartGiantBlk = kCartGiantNW * kCartMaxLine;    // unit weights: keys of a block (sorted in the workgroup's registers)
+constexpr int kCartGiantWBlk = kCartLong[1].cls[1].dhi + kCartLong[1].pad;   // general weights: (key, weight) elements of a block: the longest
+                                                              // line of the four-wavefront class (= merge_path.h: kMpBlk)
+constexpr int kCartGiantMaxWg[2] = {256, 512};                // resident workgroups: one (130 KiB of LDS) / two (64 KiB) per CU of 256
+static_assert(kCartGiantBlk == kCartLong[0].last().dhi && kCartLong[0].last().nw == kCartGiantNW && kCartLong[1].cls[1].nw == 4,
+              "blocks: the longest line of the 16-wavefront unit class / of the four-wavefront general-weight class");
+
+// bytes of one scratch line for rows of up to max_degree neighbours: the block-rounded line at 4 B per key (unit weights), four
+// block-rounded float lines (general weights: keys and weights, ping and pong)
+inline size_t cart_giant_line_bytes(const CartLongMode& m, int64_t max_degree) {
+  const int64_t blk = m.pad ? kCartGiantWBlk : kCartGiantBlk;
+  return (size_t)(ceil_div(max_degree + m.pad, blk) * blk) * sizeof(float) * (m.pad ? 4 : 1);
+}
+// workgroups of a launch over nlines lines out of a buffer that holds `held` scratch lines: a multiple of 8 from 8 on (one residue per XCD)
+inline int64_t cart_giant_workgroups(const CartLongMode& m, int64_t held, int64_t nlines) {
+  int64_t n = std::min<int64_t>({held, nlines, (int64_t)kCartGiantMaxWg[m.pad]});
+  if (n >= 8) n &= ~(int64_t)7;
+  return n;
+}
+// rows the giant class may hold: all from its first bin on.  The host knows the bins, not the degrees: general weights share that bin
+// with the class below, whose rows are counted here and skipped by the kernel (workgroup-uniform `continue`)
+inline int64_t cart_giant_rows(const fsw_cart_args* c, const CartLongMode& m) {
+  return c->max_degree < m.giant_min_degree ? 0 : (int64_t)c->bin_start_host[FSW_NUM_BINS] - c->bin_start_host[m.giant_bin];
+}
+// embed_giant_cart.hip (kCartLong[0]) and embed_giant_cart_w.hip (kCartLong[1]); scratch: fsw_embed_cart_forward_scratch_bytes
+int launch_cart_giant(const fsw_cart_args* c, hipStream_t stream);
+int launch_cart_giant_w(const fsw_cart_args* c, hipStream_t stream);
+
+// what the launchers of the giant class check before they launch: sets *nwg (0: nothing to launch) and *line_bytes
+inline int cart_giant_plan(const fsw_cart_args* c, const CartLongMode& m, int64_t* nwg, size_t* line_bytes) {
+  *nwg = 0;
+  const int64_t rows = (int64_t)c->bin_start_host[FSW_NUM_BINS] - c->bin_start_host[m.giant_bin];
+  if (rows <= 0 || (c->max_degree > 0 && c->max_degree < m.giant_min_degree)) return 0;
+  FSW_REQUIRE(c->max_degree >= m.giant_min_degree, "fsw_embed_cart_f32: max_degree (host value) is required for the rows of the longest class");
+  FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0,
+              "fsw_embed_cart_f32: rows of the longest class need a 16-byte aligned scratch buffer (fsw_embed_cart_forward_scratch_bytes)");
+  *line_bytes = cart_giant_line_bytes(m, c->max_degree);
+  *nwg = cart_giant_workgroups(m, (int64_t)(c->scratch_bytes / *line_bytes), rows * c->S);
+  FSW_REQUIRE(*nwg >= 1, "fsw_embed_cart_f32: scratch buffer too small for one line (need fsw_embed_cart_forward_scratch_bytes)");
+  return 0;
+}
+
+// Backward (c->g) of the rows the classes do not take (float32 storage): the generic kernel.
 inline int launch_cart_long_rows(const fsw_cart_args* c, const CartLongMode& m, hipStream_t stream) {
   const int p0 = c->bin_start_host[m.generic_bin];
   const int64_t rows = (int64_t)c->bin_start_host[FSW_NUM_BINS] - p0;

@@ -17,8 +17,9 @@
 //                    (embed_cart_hub.hip: k_cart_hub, the hub machinery of the diagonal kernels), no scratch.
 //   2049 <= L <= 16384, general weights: one workgroup of 2, 4 or 8 wavefronts per (row, slice), keys and weights in their registers
 //                    (embed_cart_hub_w.hip: k_cart_hub_w), no scratch.
-//   longer lines     (general weights above 16384 elements, any row above 32768) the generic kernel in its Cartesian readout
-//                    (k_embed_generic, embed_generic.hip; correct, not tuned: DESIGN.md).
+//   longer lines     (general weights above 16384 elements, any row above 32768; any length) one workgroup per (row, slice), the line
+//                    in sorted blocks in a scratch line: embed_giant_cart.hip (k_cart_giant: bitonic block sweeps) and
+//                    embed_giant_cart_w.hip (k_cart_mergepath_w: merge path).  Their backward: the generic kernel.
 // Readout, by summation by parts of the reference's Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t)):
 //   out = (1 + xi) / (pi xi) sum_t sin(2 pi xi c_t) (p_(t) - p_(t+1)),  p_(L) = 0;   xi = 0:  out = sum_t 2 c_t (p_(t) - p_(t+1)).
 //
@@ -326,6 +327,18 @@ extern "C" size_t fsw_embed_cart_scratch_bytes(const fsw_cart_args* c, int backw
   return cart_backward_scratch_bytes(m, c->max_degree, (int64_t)bs[FSW_NUM_BINS] - bs[m.cls[0].bin_lo], c->S);
 }
 
+// forward of the tuned entry point: one scratch line per workgroup the launcher of the giant class would use, at most 2 GiB, at least one
+extern "C" size_t fsw_embed_cart_forward_scratch_bytes(const fsw_cart_args* c) {
+  if (!c || !c->bin_start_host) return 0;
+  const CartLongMode& m = cart_long_mode(cart_unit_fast(c));
+  const int64_t rows = cart_giant_rows(c, m);
+  if (rows <= 0) return 0;
+  const size_t line_bytes = cart_giant_line_bytes(m, c->max_degree);
+  const size_t cap = (size_t)2 << 30;                            // as cart_line_buffer_bytes
+  const size_t lines = std::min<size_t>((size_t)cart_giant_workgroups(m, INT64_MAX, rows * std::max<int32_t>(c->S, 1)), cap / line_bytes);
+  return std::max<size_t>(lines, 1) * line_bytes;
+}
+
 extern "C" size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S) {
   return cart_backward_scratch_bytes(kCartLong[0], max_degree, long_rows, S);
 }
@@ -401,6 +414,6 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   if (rc) return rc;
   // lines above kCartMaxLine elements (the classes of embed_cart.h: kCartLong): one workgroup of 2 .. 16 wavefronts per line
   if ((rc = unit_fast ? launch_cart_hub(c, stream) : launch_cart_hub_w(c, stream))) return rc;
-  // what is left: the generic kernel
-  return launch_cart_long_rows(c, cart_long_mode(unit_fast), stream);
+  // the giant class (any length): sorted blocks in the scratch lines of c->scratch, one workgroup per line
+  return unit_fast ? launch_cart_giant(c, stream) : launch_cart_giant_w(c, stream);
 }

@@ -2,7 +2,8 @@
 // NW wavefronts of a workgroup: the striped gather of a wavefront's chunk, the register exchange between wavefronts through LDS, the
 // bitonic merge levels above one chunk and the unit-weight readout of a lane's keys.  Shared by the diagonal kernels of
 // embed_hub.hip (k_embed_hub, k_embed_hub_q4, k_embed_giant; general weights: k_embed_hub_w, k_embed_mergepath_w) and the Cartesian
-// ones of embed_cart_hub.hip (k_cart_hub) and embed_cart_hub_w.hip (k_cart_hub_w).  gfx950.
+// ones of embed_cart_hub.hip (k_cart_hub), embed_cart_hub_w.hip (k_cart_hub_w), embed_giant_cart.hip (k_cart_giant) and
+// embed_giant_cart_w.hip (k_cart_mergepath_w).  gfx950.
 #pragma once
 #include "fsw_common.h"
 #include "wave_sort.h"
@@ -40,7 +41,7 @@ __device__ __forceinline__ void wave_exchange(WaveLine<M, false>& ln, float* __r
 }
 
 // the same exchange for a (key, weight) line through xk | xw [NW][CAP] each: the weight follows its key (embed_hub.hip: k_embed_hub_w,
-// k_embed_mergepath_w; embed_cart_hub_w.hip: k_cart_hub_w)
+// k_embed_mergepath_w; embed_cart_hub_w.hip: k_cart_hub_w; embed_giant_cart_w.hip: k_cart_mergepath_w)
 template <int M>
 __device__ __forceinline__ void wave_exchange_w(WaveLine<M, true>& ln, float* __restrict__ xk, float* __restrict__ xw, int w, int lane,
                                                 int partner, bool mirrored, bool lower) {

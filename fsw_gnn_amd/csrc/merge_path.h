@@ -1,4 +1,5 @@
 // Merge levels above one sorted block for the longest neighbourhoods: merge path.  gfx950.
+// Callers: embed_hub.hip (k_embed_mergepath_w) and, in Cartesian mode, embed_giant_cart_w.hip (k_cart_mergepath_w).
 //
 // A line longer than one workgroup's registers is sorted in blocks of kMpBlk elements (phase A of the callers: four wavefronts x
 // 32 keys per lane, bitonic inside the workgroup) that are parked in a scratch line.  The levels above a block used to be bitonic

@@ -23,9 +23,10 @@ every slice is sorted once and read out at all F frequencies (csrc/embed_cart.hi
 autograd through _CartEmbedFn (backward kernels of csrc/embed_cart_bwd.hip, the key gradients summed sender by sender without
 float atomics; gradients for X, projVecs, freqs, bias and the total-mass scale); float64 modules and calls whose W requires grad
 run on the generic Cartesian kernel (_GenericEmbedFn).  Lines above 2048 elements have kernels of their own (csrc/embed_cart_hub*.hip:
-forward, the line in the registers of 2 .. 16 wavefronts; backward, one wavefront per line in a scratch line), longer ones still run
-on the generic kernel inside the tuned entry points: the library's table (csrc/embed_cart.h: kCartLong) says which rows go where, the
-host layer only asks it for the scratch size (_cart_scratch_bytes).  It needs a HIP device at construction (this
+forward, the line in the registers of 2 .. 16 wavefronts; backward, one wavefront per line in a scratch line).  Longer ones, of any
+length, are sorted in blocks in a scratch line per workgroup in the forward (csrc/embed_giant_cart.hip, csrc/embed_giant_cart_w.hip);
+their backward still runs on the generic kernel inside the tuned entry point.  The library's table (csrc/embed_cart.h: kCartLong) says
+which rows go where, the host layer only asks it for the scratch sizes (_cart_forward_scratch_bytes, _cart_scratch_bytes).  It needs a HIP device at construction (this
 package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
 differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
 bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
@@ -978,9 +979,19 @@ class FSW_embedding(nn.Module):
         a.bin_start_host = graph.bin_start_host[0].ctypes.data
         return int(_lib.lib().fsw_embed_cart_scratch_bytes(ctypes.byref(a), int(backward)))
 
+    def _cart_forward_scratch_bytes(self, graph, st):
+        """Bytes of scratch the tuned Cartesian forward uses on this graph, 0 for none: one scratch line per workgroup of the longest rows'
+        kernels (fsw_embed_cart_forward_scratch_bytes), from the same host values as _cart_scratch_bytes."""
+        a = _lib.CartArgs()
+        a.S, a.tau, a.max_degree = self.nSlices, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
+        a.w = graph.w.data_ptr() if graph.w is not None else None
+        a.bin_start_host = graph.bin_start_host[0].ctypes.data
+        return int(_lib.lib().fsw_embed_cart_forward_scratch_bytes(ctypes.byref(a)))
+
     def _cart_scratch(self, graph, st, backward=False, reuse=None):
-        """The scratch buffer of _cart_scratch_bytes, None for 0 bytes; reuse (the forward's buffer) when it is large enough."""
-        nbytes = self._cart_scratch_bytes(graph, st, backward)
+        """The scratch buffer of the forward (_cart_forward_scratch_bytes) or of the backward (_cart_scratch_bytes), None for 0 bytes;
+        reuse (the forward's buffer) when it is large enough."""
+        nbytes = self._cart_scratch_bytes(graph, st, True) if backward else self._cart_forward_scratch_bytes(graph, st)
         if reuse is not None and reuse.numel() >= nbytes:
             return reuse
         return torch.empty(nbytes, dtype=torch.uint8, device=graph.rowptr.device) if nbytes else None

@@ -360,8 +360,14 @@ int fsw_project_f64(const double* X, int64_t n, int d, int64_t ldx, const double
  * fsw_embed_cart_backward_keys_f32 (below) is the tuned float32 backward of fsw_embed_cart_f32 for keys and frequencies.
  * fsw_embed_cart_f32      tuned float32 forward on a graph of fsw_graph_build: needs perm, bin_start and bin_start_host and
  *                         unit_table = fsw_unit_coeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1.
- *                         Scratch: fsw_embed_cart_scratch_bytes(args, 0) bytes (0: scratch may be NULL).  Only the rows
- *                         beyond the tuned classes (csrc/embed_cart.h: kCartLong) need it: they run on the generic kernel.
+ *                         Scratch: fsw_embed_cart_forward_scratch_bytes(args) bytes (0: scratch may be NULL).  Only the rows of
+ *                         the longest class (csrc/embed_cart.h: kCartLong -- w == NULL and tau <= 1: above FSW_HUB_MAX_DEG neighbours;
+ *                         general weights: FSW_CART_W_MAX_LINE neighbours and more) need it: their lines are sorted in blocks in a
+ *                         scratch line per workgroup.  The minimum is ONE line (the query for one such row and S = 1), 16-byte
+ *                         aligned; a buffer of fsw_embed_cart_scratch_bytes(args, 0) bytes, the size before that query existed,
+ *                         still works.  The output does not depend on the size of the buffer.
+ *                         max_degree (host value) is required: with max_degree == 0 and a row in the first degree bin of
+ *                         the longest class the call is refused.
  *                         Rows of 1 .. FSW_REG_MAX_DEG unit-weight neighbours are stored 16 bytes at a time when F % 4 == 0,
  *                         ldo % 4 == 0, ldt % 4 == 0 and out + has_mass, bias + has_mass and unit_table are 16-byte aligned (a
  *                         caller with a mass column gets there by starting its rows 3 floats into an aligned buffer).
@@ -425,7 +431,17 @@ int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* args, const float* uni
 /* Scratch of fsw_embed_cart_f32 (backward == 0) or fsw_embed_cart_backward_keys_f32 (backward != 0) for the graph and weight mode of
  * args, of which it reads bin_start_host, max_degree, w (NULL or not), tau and S: host values only, no device is needed. */
 size_t fsw_embed_cart_scratch_bytes(const fsw_cart_args* args, int backward);
-/* The parts of that answer for a caller without the bins: the backward's scratch for w == NULL and tau <= 1 given the rows above
+/* Scratch of fsw_embed_cart_f32 for the graph and weight mode of args, of which it reads bin_start_host, max_degree, w (NULL or not),
+ * tau and S: host values only.  0 when no row belongs to the longest class of its mode.  Otherwise lines x line_bytes: line_bytes is
+ * what ONE workgroup needs for the longest row -- 4 bytes per key of the line rounded up to whole blocks (w == NULL and tau <= 1),
+ * four float lines of max_degree + 1 elements rounded up to whole blocks (general weights: keys and weights, twice) --, and
+ * lines = min(rows from the class's first degree bin on x S, the workgroups the launch would use), the whole at most 2 GiB and never below one line.
+ *   (general weights: that bin also holds shorter rows of the class below, which are counted but skipped by the kernel.)
+ *   Any 16-byte aligned buffer that holds at least one line works: fewer workgroups then share the rows, with bit-identical output.
+ *   A buffer of fsw_embed_cart_generic_scratch_bytes(max_degree, 1) bytes still suffices: its 36 * pow2ceil(max_degree + 1) bytes
+ *   exceed one line in both modes. */
+size_t fsw_embed_cart_forward_scratch_bytes(const fsw_cart_args* args);
+/* The parts of the answer of fsw_embed_cart_scratch_bytes for a caller without the bins: the backward's scratch for w == NULL and tau <= 1 given the rows above
  * FSW_LDS_MAX_DEG neighbours, and for general weights given the rows of FSW_LDS_MAX_DEG neighbours and more (lines of 12 bytes per
  * element of the padded longest line, min(2048, long_rows * S) of them, at most 2 GiB; 0 when no row is that long). */
 size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S);

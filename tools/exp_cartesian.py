@@ -47,8 +47,17 @@ on csrc/embed_cart_hub_w.hip / csrc/embed_cart_hub_w_bwd.hip, the batch of 24000
 d_in 3, S = 64, F = 16, W = 'uniform', through the public forward.  A build from before these classes (no export
 fsw_embed_cart_weighted_backward_scratch_bytes) is driven with the generic kernel's scratch for every row of 2048 neighbours and more:
     python tools/exp_cartesian.py --hub --weights uniform [--workload readout,pc4096] --steps 3 --warmup 1
-    FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --hub --weights uniform --steps 3 --warmup 1"""
+    FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --hub --weights uniform --steps 3 --warmup 1
+--giant: the longest rows -- unit weights above 32768 neighbours, general weights from 16384 (csrc/embed_giant_cart.hip,
+csrc/embed_giant_cart_w.hip) --, forward (no_grad) and one training step, S = F = --slices / --freqs: batches of 8 graphs x 24 000
+weighted and 8 x 40 000 unit vertices, the mixed batch 2500 .. 30000 with weights, one cloud of 150 000 and one of 1 000 000 points,
+unit and weighted.  A build without fsw_embed_cart_forward_scratch_bytes (the generic kernel on these rows) is driven with the scratch
+that kernel needs.
+    python tools/exp_cartesian.py --giant [--workload w24000,u40000,mixed,c150000,c1000000] --steps 3 --warmup 1
+    FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --giant --steps 3 --warmup 1
+    rocprofv3 --kernel-trace --stats -d DIR -o giant -- python tools/exp_cartesian.py --giant --workload c150000 --steps 1"""
 import argparse
+import ctypes
 import os
 import sys
 
@@ -74,6 +83,7 @@ ap.add_argument("--conv", action="store_true", help="time the FSW_conv layer (di
 ap.add_argument("--forms", default="unfused,fused", help="--conv: forms to time, alternating over the runs (--train: diag, cart)")
 ap.add_argument("--runs", type=int, default=5, help="--conv: runs of every form")
 ap.add_argument("--hub", action="store_true", help="time the unit-weight hub rows (2049 .. 32768 neighbours), forward and training step")
+ap.add_argument("--giant", action="store_true", help="time the longest rows (unit: above 32768 neighbours, weights: from 16384), forward and training step")
 ap.add_argument("--weights", choices=("unit", "uniform", "random"), default="unit",
                 help="--hub: unit weights (the unit hub kernels), or a weight per vertex: 1 / size of its graph, or random in (0.05, 1)")
 ap.add_argument("--tau", type=float, default=1.0, help="--hub: total_mass_pad_thresh of the embedding (> 1: general-weight kernels with w = NULL)")
@@ -325,6 +335,65 @@ def weighted_workloads(workload, batches, time_pair):
         time_pair("point clouds %d x %d, d_in 3, S=%d F=%d, W='uniform'" % (B, npts, Spc, Fpc), lambda: pc(X, 'uniform'), step_pc)
 
 
+def library_exports(symbol):
+    """Whether the build that FSW_HIP_LIBRARY names exports symbol."""
+    return hasattr(ctypes.CDLL(_lib.LIB_PATH), symbol)
+
+
+def drive_without(symbol, method, rule):
+    """An older build without an export of the binding: drop its signature (lib() binds every one it lists) and let FSW_embedding.method
+    follow the host rule from before the export."""
+    del _lib._SIGNATURES[symbol]
+    setattr(FSW_embedding, method, rule)
+
+
+def giant_leg():
+    has_giant = library_exports("fsw_embed_cart_forward_scratch_bytes")
+    if not has_giant:      # the generic kernel runs these rows: the forward's scratch is what the older query says
+        drive_without("fsw_embed_cart_forward_scratch_bytes", "_cart_forward_scratch_bytes",
+                      lambda self, graph, st: self._cart_scratch_bytes(graph, st, False))
+    print("library %s: %s" % (_lib.LIB_PATH, "kernels of the longest rows" if has_giant else "generic kernel on the longest rows"), flush=True)
+    S, F, d = args.slices, args.freqs, 32
+    steps, warmup = args.steps, args.warmup
+    workload = "w24000,u40000,mixed,c150000,c1000000" if args.workload == ap.get_default("workload") else args.workload
+    cases = [("w24000", "8 graphs x 24000, weights", [24000] * 8, True), ("u40000", "8 graphs x 40000, unit", [40000] * 8, False),
+             ("mixed", "mixed 2500 .. 30000, weights", [2500, 5000, 9000, 12000, 16000, 20000, 25000, 30000], True),
+             ("c150000", "one cloud of 150000, unit", [150000], False), ("c150000", "one cloud of 150000, weights", [150000], True),
+             ("c1000000", "one cloud of 1000000, unit", [1000000], False), ("c1000000", "one cloud of 1000000, weights", [1000000], True)]
+    torch.manual_seed(7)
+    mod = FSW_embedding(d_in=d, nSlices=S, nFreqs=F, collapse_freqs=True, enable_bias=False, learnable_slices=True,
+                        learnable_freqs=True, freqs_init='spread', device=dev)
+    for key, name, sizes, weighted in cases:
+        if key not in workload.split(","):
+            continue
+        gi = torch.cat([torch.full((m,), g, dtype=torch.int64) for g, m in enumerate(sizes)]).to(dev)
+        nv = gi.numel()
+        w = (0.05 + 0.95 * torch.rand(nv, generator=torch.Generator().manual_seed(8))).to(dev) if weighted else None
+        graph = build_csr(gi.contiguous(), torch.arange(nv, device=dev), w, len(sizes), nv)
+        graph.read_stats()
+        x = torch.randn((nv, d), device=dev)
+        xg = x.clone().requires_grad_(True)
+        out = torch.empty((len(sizes), S * F), device=dev)
+        G = torch.randn((len(sizes), S * F), device=dev)
+
+        def step():
+            mod.zero_grad(set_to_none=True)
+            xg.grad = None
+            mod.embed_cartesian_autograd(xg, graph).backward(G)
+
+        with torch.no_grad():
+            for _ in range(warmup):
+                mod.embed_cartesian_into(x, graph, out)
+            fwd = bench.timed_ms(lambda: mod.embed_cartesian_into(x, graph, out), steps, dev)
+        for _ in range(warmup):
+            step()
+        print("%-36s S=%d F=%d  forward %10.3f ms   training step %10.3f ms" % (name, S, F, fwd, bench.timed_ms(step, steps, dev)), flush=True)
+        del graph, x, xg, out, G, gi, w
+
+
+if args.giant:
+    giant_leg()
+    sys.exit(0)
 if args.hub:
     hub_leg()
     sys.exit(0)
