@@ -106,6 +106,7 @@ _SIGNATURES = {
     "fsw_embed_cart_backward_keys_f32": (ctypes.c_int, [ctypes.POINTER(CartArgs), c_vp, c_i64, c_vp]),
     "fsw_embed_cart_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs), ctypes.c_int]),
     "fsw_embed_cart_forward_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs)]),
+    "fsw_embed_cart_backward_keys_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs)]),
     "fsw_embed_cart_backward_scratch_bytes": (c_sz, [c_i64, c_i64, c_i32]),
     "fsw_embed_cart_weighted_backward_scratch_bytes": (c_sz, [c_i64, c_i64, c_i32]),
     "fsw_conv_fused_cart_lds_bytes": (c_sz, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),

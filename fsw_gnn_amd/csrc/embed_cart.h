@@ -1,5 +1,5 @@
 // What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_giant_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
-// embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip) of Cartesian mode share: the degree classes, the
+// embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip, embed_giant_cart_bwd.hip) of Cartesian mode share: the degree classes, the
 // constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
 #pragma once
 #include <algorithm>
@@ -58,9 +58,9 @@ int for_each_wave_group(const int32_t* bs, int extra, Fn fn) {
 }
 
 // ---- the classes of the rows whose line is longer than kCartMaxLine elements: THE table (DESIGN.md prints it too) ---------------
-// Everything that decides which rows a class takes reads it: the four launchers of embed_cart_hub*.hip, the two of embed_giant_cart*.hip,
-// launch_cart_long_rows and the scratch sizes (fsw_embed_cart_scratch_bytes and fsw_embed_cart_forward_scratch_bytes, which the host
-// layer calls).
+// Everything that decides which rows a class takes reads it: the four launchers of embed_cart_hub*.hip, the three of embed_giant_cart*.hip
+// and the scratch sizes (fsw_embed_cart_scratch_bytes, fsw_embed_cart_forward_scratch_bytes and
+// fsw_embed_cart_backward_keys_scratch_bytes, which the host layer calls).
 struct CartLongClass {
   int bin_lo, bin_hi;   // the degree bins its rows lie in
   int dlo, dhi;         // its rows: dlo < D <= dhi
@@ -71,9 +71,11 @@ struct CartLongMode {
   int pad;              // elements of a line next to the D neighbours: the pad element of general weights
   int num;              // classes
   CartLongClass cls[FSW_NUM_HUB_BINS];
-  int generic_bin, generic_min_degree;   // backward: rows of generic_min_degree neighbours and more (they begin in generic_bin): the generic kernel
-  int giant_bin, giant_min_degree;       // forward: rows of giant_min_degree neighbours and more (they begin in giant_bin): sorted blocks in a
-                                         // scratch line (embed_giant_cart.hip: k_cart_giant, embed_giant_cart_w.hip: k_cart_mergepath_w)
+  int generic_bin, generic_min_degree;   // the rows past the classes as the older scratch queries count them (fsw_embed_cart_scratch_bytes and the
+                                         // two legacy size functions keep the values they had when these rows ran on the generic kernel)
+  int giant_bin, giant_min_degree;       // rows of giant_min_degree neighbours and more (they begin in giant_bin): one workgroup per line in a
+                                         // scratch line -- forward: sorted blocks (embed_giant_cart.hip: k_cart_giant, embed_giant_cart_w.hip:
+                                         // k_cart_mergepath_w); backward: sorted runs + merge path (embed_giant_cart_bwd.hip: k_cart_giant_bwd)
   constexpr const CartLongClass& last() const { return cls[num - 1]; }
 };
 constexpr int kCartLastLdsBin = FSW_BIN_HUB0 - 1;             // rows of 1025 .. FSW_LDS_MAX_DEG neighbours
@@ -99,7 +101,8 @@ constexpr bool cart_long_table_ok(const CartLongMode& m, int max_line) {
   if (m.cls[0].dlo + m.pad != kCartMaxLine || m.last().dhi + m.pad != max_line) return false;   // from the wavefront path to max_line
   if (m.generic_min_degree != m.last().dhi + 1) return false;
   if (bin_upper_degree(m.generic_bin - 1) >= m.generic_min_degree || m.generic_min_degree > bin_upper_degree(m.generic_bin)) return false;
-  if (m.giant_min_degree != m.last().dhi + 1) return false;                                     // the forward leaves no row without a class
+  if (m.giant_min_degree != m.last().dhi + 1) return false;                                     // neither direction leaves a row without a class
+  if (m.giant_bin != m.generic_bin) return false;                                               // the older queries count the giant class's rows
   if (bin_upper_degree(m.giant_bin - 1) >= m.giant_min_degree || m.giant_min_degree > bin_upper_degree(m.giant_bin)) return false;
   for (int i = 0; i < m.num; ++i) {
     const CartLongClass& k = m.cls[i];
@@ -195,12 +198,22 @@ inline int cart_giant_plan(const fsw_cart_args* c, const CartLongMode& m, int64_
   return 0;
 }
 
-// Backward (c->g) of the rows the classes do not take (float32 storage): the generic kernel.
-inline int launch_cart_long_rows(const fsw_cart_args* c, const CartLongMode& m, hipStream_t stream) {
-  const int p0 = c->bin_start_host[m.generic_bin];
-  const int64_t rows = (int64_t)c->bin_start_host[FSW_NUM_BINS] - p0;
-  if (c->max_degree < m.generic_min_degree || rows <= 0) return 0;
-  return launch_embed_generic(generic_args(*c, true, c->F), 0, c->perm + p0, rows, m.generic_min_degree, stream);
+// ---- backward of the giant class: one workgroup of four wavefronts per (row, slice) line; the line as packed (key, entry index) words
+// in sorted runs of kCartMaxLine (one wavefront's chunk), merged by merge path (merge_path64.h) between two scratch lines -------------
+constexpr int kCartGiantBwdElemBytes = 16;                    // per word of the line: ping and pong; the key gradients pass through the one
+                                                              // that the last level leaves free
+constexpr int kCartGiantBwdMaxWg[2] = {512, 512};             // resident workgroups: two (20.5 KiB of LDS, <= 256 registers) per CU of 256
+// bytes of one scratch line for rows of up to max_degree neighbours: the line rounded up to whole runs
+inline size_t cart_giant_bwd_line_bytes(const CartLongMode& m, int64_t max_degree) {
+  return (size_t)(ceil_div(max_degree + m.pad, kCartMaxLine) * kCartMaxLine) * kCartGiantBwdElemBytes;
 }
+// workgroups of a launch over nlines lines out of a buffer that holds `held` scratch lines: a multiple of 8 from 8 on (one residue per XCD)
+inline int64_t cart_giant_bwd_workgroups(const CartLongMode& m, int64_t held, int64_t nlines) {
+  int64_t n = std::min<int64_t>({held, nlines, (int64_t)kCartGiantBwdMaxWg[m.pad]});
+  if (n >= 8) n &= ~(int64_t)7;
+  return n;
+}
+// embed_giant_cart_bwd.hip: the giant class of the call's mode out of c->scratch (fsw_embed_cart_backward_keys_scratch_bytes)
+int launch_cart_giant_bwd(const fsw_cart_args* c, hipStream_t stream);
 
 }  // namespace fsw

@@ -19,7 +19,7 @@
 //                    (embed_cart_hub_w.hip: k_cart_hub_w), no scratch.
 //   longer lines     (general weights above 16384 elements, any row above 32768; any length) one workgroup per (row, slice), the line
 //                    in sorted blocks in a scratch line: embed_giant_cart.hip (k_cart_giant: bitonic block sweeps) and
-//                    embed_giant_cart_w.hip (k_cart_mergepath_w: merge path).  Their backward: the generic kernel.
+//                    embed_giant_cart_w.hip (k_cart_mergepath_w: merge path).  Their backward: embed_giant_cart_bwd.hip.
 // Readout, by summation by parts of the reference's Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t)):
 //   out = (1 + xi) / (pi xi) sum_t sin(2 pi xi c_t) (p_(t) - p_(t+1)),  p_(L) = 0;   xi = 0:  out = sum_t 2 c_t (p_(t) - p_(t+1)).
 //
@@ -337,6 +337,29 @@ extern "C" size_t fsw_embed_cart_forward_scratch_bytes(const fsw_cart_args* c) {
   const size_t cap = (size_t)2 << 30;                            // as cart_line_buffer_bytes
   const size_t lines = std::min<size_t>((size_t)cart_giant_workgroups(m, INT64_MAX, rows * std::max<int32_t>(c->S, 1)), cap / line_bytes);
   return std::max<size_t>(lines, 1) * line_bytes;
+}
+
+// backward of the tuned entry point: the larger of what the launches of the classes with a scratch line per wavefront need and of one
+// scratch line per workgroup the launcher of the giant class would use (at most 2 GiB, at least one line)
+extern "C" size_t fsw_embed_cart_backward_keys_scratch_bytes(const fsw_cart_args* c) {
+  if (!c || !c->bin_start_host) return 0;
+  const CartLongMode& m = cart_long_mode(cart_unit_fast(c));
+  const int32_t* bs = c->bin_start_host;
+  const int32_t S = std::max<int32_t>(c->S, 1);
+  size_t bytes = 0;
+  // unit weights without a row in the class bins launch none of these classes
+  if (c->max_degree > m.cls[0].dlo && !(m.pad == 0 && bs[m.last().bin_hi + 1] == bs[m.cls[0].bin_lo])) {
+    const int64_t rows = std::max<int64_t>((int64_t)bs[FSW_NUM_BINS] - bs[m.cls[0].bin_lo], 1);
+    bytes = cart_line_buffer_bytes(cart_line_elems(m, std::min<int64_t>(c->max_degree, m.last().dhi)), rows * S);
+  }
+  const int64_t rows = cart_giant_rows(c, m);
+  if (rows > 0) {
+    const size_t line_bytes = cart_giant_bwd_line_bytes(m, c->max_degree);
+    const size_t cap = (size_t)2 << 30;                          // as cart_line_buffer_bytes
+    const size_t lines = std::min<size_t>((size_t)cart_giant_bwd_workgroups(m, INT64_MAX, rows * S), cap / line_bytes);
+    bytes = std::max(bytes, std::max<size_t>(lines, 1) * line_bytes);
+  }
+  return bytes;
 }
 
 extern "C" size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S) {

@@ -18,8 +18,10 @@
 //                    (embed_cart_hub_bwd.hip: k_cart_bwd_long), 12 bytes of scratch per element of the padded line and wavefront.
 //   2049 <= L <= 16384, general weights: one wavefront per (row, slice) in a scratch line of packed words, the weights re-read by
 //                    entry index (embed_cart_hub_w_bwd.hip: k_cart_bwd_long_w), 12 bytes of scratch per element of the padded line.
-//   longer lines     (general weights above 16384 elements, any row above 32768) the generic kernel in backward mode
-//                    (k_embed_generic, embed_generic.hip), as in the forward.
+//   longer lines     (general weights above 16384 elements, any row above 32768; any length) one workgroup of four wavefronts per
+//                    (row, slice): the packed words in sorted runs in a scratch line, merge path above a run
+//                    (embed_giant_cart_bwd.hip: k_cart_giant_bwd), 16 bytes of scratch per element of the line and workgroup.
+// No float32 row runs on the generic kernel (k_embed_generic, embed_generic.hip).
 // gfreq: the register class sums a workgroup's partials in LDS, the wavefront class across the wavefront; one float atomic per
 // (workgroup resp. wavefront, frequency).
 #include <algorithm>
@@ -429,6 +431,6 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
   if (rc) return rc;
   // lines above kCartMaxLine elements (the classes of embed_cart.h: kCartLong): one wavefront per line in a scratch line
   if ((rc = unit_fast ? launch_cart_hub_bwd(c, stream) : launch_cart_hub_w_bwd(c, stream))) return rc;
-  // what is left: the generic kernel in backward mode
-  return launch_cart_long_rows(c, cart_long_mode(unit_fast), stream);
+  // the giant class (any length): sorted runs + merge path in the scratch lines of c->scratch, one workgroup per line
+  return launch_cart_giant_bwd(c, stream);
 }

@@ -8,7 +8,7 @@
 // frequencies per barrier: every wavefront drops its kFB wave sums into an LDS table, ONE barrier, then lane f of the batch adds
 // the NW partials and the batch's outputs leave as one contiguous run.  The table is double-buffered, so no second barrier frees
 // it.  Nothing of the line goes to global memory and the kernel needs no scratch.
-// The rows above FSW_HUB_MAX_DEG stay on the generic kernel (embed_cart.h); general weights: embed_cart_hub_w.hip.
+// The rows above FSW_HUB_MAX_DEG: the giant class (embed_cart.h; embed_giant_cart.hip); general weights: embed_cart_hub_w.hip.
 #include <algorithm>
 #include "embed_cart.h"
 #include "embed_launch.h"

@@ -12,8 +12,8 @@
 // kFB frequencies per barrier in a double-buffered LDS table, lanes 0 .. kFB - 1 of wavefront 0 store a contiguous run of outputs.
 // Nothing of the line goes to global memory and the kernel needs no scratch.
 // The classes follow the line length, not the degree bins (cut at D = 2048, 4096, ...): each class is launched over the two bins it
-// touches with a workgroup-uniform dlo < D <= dhi filter, as launch_hub_w does.  Rows of FSW_CART_W_MAX_LINE neighbours and more stay
-// on the generic kernel (embed_cart.h: launch_cart_long_rows).
+// touches with a workgroup-uniform dlo < D <= dhi filter, as launch_hub_w does.  Rows of FSW_CART_W_MAX_LINE neighbours and more: the
+// giant class (embed_cart.h; embed_giant_cart_w.hip, backward embed_giant_cart_bwd.hip).
 #include <algorithm>
 #include "embed_cart.h"
 #include "embed_launch.h"

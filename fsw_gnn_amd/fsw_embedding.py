@@ -24,9 +24,10 @@ autograd through _CartEmbedFn (backward kernels of csrc/embed_cart_bwd.hip, the 
 float atomics; gradients for X, projVecs, freqs, bias and the total-mass scale); float64 modules and calls whose W requires grad
 run on the generic Cartesian kernel (_GenericEmbedFn).  Lines above 2048 elements have kernels of their own (csrc/embed_cart_hub*.hip:
 forward, the line in the registers of 2 .. 16 wavefronts; backward, one wavefront per line in a scratch line).  Longer ones, of any
-length, are sorted in blocks in a scratch line per workgroup in the forward (csrc/embed_giant_cart.hip, csrc/embed_giant_cart_w.hip);
-their backward still runs on the generic kernel inside the tuned entry point.  The library's table (csrc/embed_cart.h: kCartLong) says
-which rows go where, the host layer only asks it for the scratch sizes (_cart_forward_scratch_bytes, _cart_scratch_bytes).  It needs a HIP device at construction (this
+length, are sorted in blocks in a scratch line per workgroup in both directions (forward: csrc/embed_giant_cart.hip,
+csrc/embed_giant_cart_w.hip; backward: csrc/embed_giant_cart_bwd.hip), so a float32 call with constant W runs the generic kernel
+nowhere.  The library's table (csrc/embed_cart.h: kCartLong) says which rows go where, the host layer only asks it for the scratch
+sizes (_cart_forward_scratch_bytes, _cart_backward_scratch_bytes).  It needs a HIP device at construction (this
 package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
 differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
 bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
@@ -501,8 +502,9 @@ class _CartEmbedFn(torch.autograd.Function):
     projVecs, freqs, bias and the total-mass scale (the weights are constants: a W that requires grad takes _GenericEmbedFn).
 
     Forward: one projection of all S slices (prepare_cartesian) + fsw_embed_cart_f32; the projection, the stats and the unit table
-    stay on ctx.  Backward: fsw_embed_cart_backward_keys_f32 (csrc/embed_cart_bwd.hip; its scratch is the forward's buffer where that is
-    large enough, else a buffer of its own: _cart_scratch) stores the key gradient of every entry, [nnz, S], and accumulates the
+    stay on ctx.  Backward: fsw_embed_cart_backward_keys_f32 (csrc/embed_cart_bwd.hip, tuned kernels for rows of every length; its
+    scratch, _cart_backward_scratch_bytes, is the forward's buffer where that is large enough, else a buffer of its own:
+    _cart_scratch) stores the key gradient of every entry, [nnz, S], and accumulates the
     frequency gradients; the store-and-sum pair (graph.sender_major + fsw_segment_sum_rows_f32) sums
     the entries sender by sender without float atomics, then the two GEMMs of _EmbedGraphFn.  bias: None for 'homog' /
     'homog_alt' (the caller applies _homog_epilogue on the 'plain' output)."""
@@ -988,10 +990,19 @@ class FSW_embedding(nn.Module):
         a.bin_start_host = graph.bin_start_host[0].ctypes.data
         return int(_lib.lib().fsw_embed_cart_forward_scratch_bytes(ctypes.byref(a)))
 
+    def _cart_backward_scratch_bytes(self, graph, st):
+        """Bytes of scratch the tuned Cartesian backward uses on this graph, 0 for none: one scratch line per wavefront or workgroup of
+        its long-row kernels (fsw_embed_cart_backward_keys_scratch_bytes), from the same host values as _cart_scratch_bytes."""
+        a = _lib.CartArgs()
+        a.S, a.tau, a.max_degree = self.nSlices, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
+        a.w = graph.w.data_ptr() if graph.w is not None else None
+        a.bin_start_host = graph.bin_start_host[0].ctypes.data
+        return int(_lib.lib().fsw_embed_cart_backward_keys_scratch_bytes(ctypes.byref(a)))
+
     def _cart_scratch(self, graph, st, backward=False, reuse=None):
-        """The scratch buffer of the forward (_cart_forward_scratch_bytes) or of the backward (_cart_scratch_bytes), None for 0 bytes;
-        reuse (the forward's buffer) when it is large enough."""
-        nbytes = self._cart_scratch_bytes(graph, st, True) if backward else self._cart_forward_scratch_bytes(graph, st)
+        """The scratch buffer of the forward (_cart_forward_scratch_bytes) or of the backward (_cart_backward_scratch_bytes), None for
+        0 bytes; reuse (the forward's buffer) when it is large enough."""
+        nbytes = self._cart_backward_scratch_bytes(graph, st) if backward else self._cart_forward_scratch_bytes(graph, st)
         if reuse is not None and reuse.numel() >= nbytes:
             return reuse
         return torch.empty(nbytes, dtype=torch.uint8, device=graph.rowptr.device) if nbytes else None

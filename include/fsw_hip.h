@@ -424,9 +424,11 @@ int fsw_embed_cart_f32(const fsw_cart_args* args, fsw_stream_t stream);
  * Adds    args->gfreq[f]         += out_scale * sum_{r,s} g[r, has_mass + s F + f] * d out[r,s,f] / d xi_f  (nullable; caller zeroes)
  * args->gw must be NULL (gradients w.r.t. the weights stay on fsw_embed_cart_generic).
  * unit_dtable: fsw_unit_dcoeff_table(freqs, F, FSW_REG_MAX_DEG) when w == NULL and tau <= 1 (with args->unit_table as in the forward).
- * Scratch: fsw_embed_cart_scratch_bytes(args, 1) bytes (0: scratch may be NULL).
- *   A buffer of fsw_embed_cart_generic_scratch_bytes(max_degree, rows >= 1) bytes also suffices and gives bit-identical gkey.
- * The buffer must be 16-byte aligned. */
+ * Scratch: fsw_embed_cart_backward_keys_scratch_bytes(args) bytes (0: scratch may be NULL).
+ *   A buffer of fsw_embed_cart_scratch_bytes(args, 1) bytes, the size before that query existed, or of
+ *   fsw_embed_cart_generic_scratch_bytes(max_degree, rows >= 1) bytes also suffices and gives bit-identical gkey.
+ * The buffer must be 16-byte aligned.  No float32 row runs on the generic kernel: the rows of the longest class (csrc/embed_cart.h:
+ * kCartLong; csrc/embed_giant_cart_bwd.hip) are sorted in runs in a scratch line per workgroup, as in the forward. */
 int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* args, const float* unit_dtable, int64_t lddt, fsw_stream_t stream);
 /* Scratch of fsw_embed_cart_f32 (backward == 0) or fsw_embed_cart_backward_keys_f32 (backward != 0) for the graph and weight mode of
  * args, of which it reads bin_start_host, max_degree, w (NULL or not), tau and S: host values only, no device is needed. */
@@ -441,6 +443,24 @@ size_t fsw_embed_cart_scratch_bytes(const fsw_cart_args* args, int backward);
  *   A buffer of fsw_embed_cart_generic_scratch_bytes(max_degree, 1) bytes still suffices: its 36 * pow2ceil(max_degree + 1) bytes
  *   exceed one line in both modes. */
 size_t fsw_embed_cart_forward_scratch_bytes(const fsw_cart_args* args);
+/* Scratch of fsw_embed_cart_backward_keys_f32 for the graph and weight mode of args, of which it reads bin_start_host, max_degree, w
+ * (NULL or not), tau and S: host values only.  The maximum of two parts, 0 when neither applies:
+ *   1. the rows of FSW_LDS_MAX_DEG + 1 .. FSW_HUB_MAX_DEG neighbours (general weights: lines of FSW_LDS_MAX_DEG + 1 ..
+ *      FSW_CART_W_MAX_LINE elements), one scratch line per wavefront: fsw_embed_cart_backward_scratch_bytes /
+ *      fsw_embed_cart_weighted_backward_scratch_bytes for min(max_degree, the longest such row) and the rows from the first
+ *      degree bin of these classes on -- the rule of fsw_embed_cart_scratch_bytes(args, 1) without the generic kernel's term;
+ *      nothing when w == NULL, tau <= 1 and the degree bins of these classes are empty;
+ *   2. the rows of the longest class (w == NULL and tau <= 1: above FSW_HUB_MAX_DEG neighbours; general weights: FSW_CART_W_MAX_LINE
+ *      neighbours and more), one scratch line per workgroup: lines x line_bytes, line_bytes = 16 bytes per element of the longest line
+ *      (max_degree elements; general weights: max_degree + 1) rounded up to whole runs of FSW_LDS_MAX_DEG elements -- two lines of
+ *      packed (key, entry index) words, of which the one that the last merge level leaves free carries the key gradients in entry
+ *      order --, lines = min(rows from the class's first degree bin on x S, the workgroups the launch would use: at most 512, a
+ *      multiple of 8 from 8 on), the whole at most 2 GiB and never below one line.
+ *      (general weights: that bin also holds shorter rows of the class below, which are counted but skipped by the kernel.)
+ *   Any 16-byte aligned buffer that holds what part 1 needs and at least one line of part 2 works: fewer workgroups then share the
+ *   rows, with bit-identical gkey.  A buffer of fsw_embed_cart_generic_scratch_bytes(max_degree, 1) bytes still suffices: its
+ *   36 * pow2ceil(max_degree + 1) bytes exceed the 16 * (max_degree + 1 + FSW_LDS_MAX_DEG) bytes of a line for every row of the class. */
+size_t fsw_embed_cart_backward_keys_scratch_bytes(const fsw_cart_args* args);
 /* The parts of the answer of fsw_embed_cart_scratch_bytes for a caller without the bins: the backward's scratch for w == NULL and tau <= 1 given the rows above
  * FSW_LDS_MAX_DEG neighbours, and for general weights given the rows of FSW_LDS_MAX_DEG neighbours and more (lines of 12 bytes per
  * element of the padded longest line, min(2048, long_rows * S) of them, at most 2 GiB; 0 when no row is that long). */

@@ -51,7 +51,8 @@ fsw_embed_cart_weighted_backward_scratch_bytes) is driven with the generic kerne
 --giant: the longest rows -- unit weights above 32768 neighbours, general weights from 16384 (csrc/embed_giant_cart.hip,
 csrc/embed_giant_cart_w.hip) --, forward (no_grad) and one training step, S = F = --slices / --freqs: batches of 8 graphs x 24 000
 weighted and 8 x 40 000 unit vertices, the mixed batch 2500 .. 30000 with weights, one cloud of 150 000 and one of 1 000 000 points,
-unit and weighted.  A build without fsw_embed_cart_forward_scratch_bytes (the generic kernel on these rows) is driven with the scratch
+unit and weighted.  A build without fsw_embed_cart_backward_keys_scratch_bytes (the generic kernel in the backward of these rows) or
+without fsw_embed_cart_forward_scratch_bytes (the generic kernel in both directions) is driven with the scratch
 that kernel needs.
     python tools/exp_cartesian.py --giant [--workload w24000,u40000,mixed,c150000,c1000000] --steps 3 --warmup 1
     FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --giant --steps 3 --warmup 1
@@ -352,7 +353,12 @@ def giant_leg():
     if not has_giant:      # the generic kernel runs these rows: the forward's scratch is what the older query says
         drive_without("fsw_embed_cart_forward_scratch_bytes", "_cart_forward_scratch_bytes",
                       lambda self, graph, st: self._cart_scratch_bytes(graph, st, False))
-    print("library %s: %s" % (_lib.LIB_PATH, "kernels of the longest rows" if has_giant else "generic kernel on the longest rows"), flush=True)
+    has_giant_bwd = library_exports("fsw_embed_cart_backward_keys_scratch_bytes")
+    if not has_giant_bwd:  # the backward of these rows is the generic kernel: its scratch is what the older query says
+        drive_without("fsw_embed_cart_backward_keys_scratch_bytes", "_cart_backward_scratch_bytes",
+                      lambda self, graph, st: self._cart_scratch_bytes(graph, st, True))
+    print("library %s: forward: %s; backward: %s" % (_lib.LIB_PATH, "kernels of the longest rows" if has_giant else "generic kernel on the longest rows",
+                                                      "kernel of the longest rows" if has_giant_bwd else "generic kernel on the longest rows"), flush=True)
     S, F, d = args.slices, args.freqs, 32
     steps, warmup = args.steps, args.warmup
     workload = "w24000,u40000,mixed,c150000,c1000000" if args.workload == ap.get_default("workload") else args.workload
