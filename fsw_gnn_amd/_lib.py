@@ -18,6 +18,7 @@ MID_SIZES = (40, 48, 64, 80, 96, 128, 160, 192, 256)   # FSW_MID_SIZES: padded r
 NUM_LDS_BINS = 3                                          # FSW_NUM_LDS_BINS: degrees <= 512, 1024, 2048
 NUM_HUB_BINS = 4                                          # FSW_NUM_HUB_BINS: degrees <= 4096, 8192, 16384, 32768
 HUB_MAX_DEG = 32768
+CART_SPLIT_LINES = 1          # FSW_CART_SPLIT_LINES: fsw_cart_args.flags, the split form of the longest unit-weight rows (fsw_embed_cart_f32)
 CART_W_MAX_LINE = 16384       # FSW_CART_W_MAX_LINE: Cartesian mode, general weights, longest line (D + 1) of the tuned classes
 BIN_MID0 = REG_MAX_DEG + 1      # first bin above the register path (include/fsw_hip.h: FSW_BIN_MID0)
 NUM_BINS = REG_MAX_DEG + 1 + len(MID_SIZES) + NUM_LDS_BINS + NUM_HUB_BINS + 1
@@ -63,7 +64,7 @@ class CartArgs(ctypes.Structure):
         ("rowptr", c_vp), ("col", c_vp), ("w", c_vp), ("perm", c_vp), ("bin_start", c_vp), ("bin_start_host", c_vp),
         ("num_rows", c_i64), ("max_degree", c_i64), ("Xp", c_vp), ("ldp", c_i64), ("freqs", c_vp), ("tau", ctypes.c_double),
         ("unit_table", c_vp), ("ldt", c_i64), ("out", c_vp), ("ldo", c_i64), ("bias", c_vp), ("out_scale", ctypes.c_double),
-        ("mass_fn", c_i32), ("reserved", c_i32), ("mass_scale", ctypes.c_double), ("g", c_vp), ("ldg", c_i64),
+        ("mass_fn", c_i32), ("flags", c_i32), ("mass_scale", ctypes.c_double), ("g", c_vp), ("ldg", c_i64),
         ("gkey", c_vp), ("ldk", c_i64), ("gfreq", c_vp), ("gw", c_vp), ("scratch", c_vp), ("scratch_bytes", c_sz),
     ]
 
@@ -106,6 +107,9 @@ _SIGNATURES = {
     "fsw_embed_cart_backward_keys_f32": (ctypes.c_int, [ctypes.POINTER(CartArgs), c_vp, c_i64, c_vp]),
     "fsw_embed_cart_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs), ctypes.c_int]),
     "fsw_embed_cart_forward_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs)]),
+    "fsw_embed_cart_split_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs)]),
+    "fsw_embed_cart_split_lines": (c_i64, [ctypes.POINTER(CartArgs)]),
+    "fsw_embed_cart_split_max_lines": (c_i64, []),
     "fsw_embed_cart_backward_keys_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs)]),
     "fsw_embed_cart_backward_scratch_bytes": (c_sz, [c_i64, c_i64, c_i32]),
     "fsw_embed_cart_weighted_backward_scratch_bytes": (c_sz, [c_i64, c_i64, c_i32]),

@@ -1,4 +1,4 @@
-// What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_giant_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
+// What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_split_cart.hip, embed_giant_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
 // embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip, embed_giant_cart_bwd.hip) of Cartesian mode share: the degree classes, the
 // constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
 #pragma once
@@ -197,6 +197,38 @@ inline int cart_giant_plan(const fsw_cart_args* c, const CartLongMode& m, int64_
   FSW_REQUIRE(*nwg >= 1, "fsw_embed_cart_f32: scratch buffer too small for one line (need fsw_embed_cart_forward_scratch_bytes)");
   return 0;
 }
+
+// ---- split form of the giant class's forward, unit weights (embed_split_cart.hip; args->flags & FSW_CART_SPLIT_LINES): every phase of
+// k_cart_giant is a launch of its own over (line, block), so one long line keeps many workgroups busy.  Every line owns a scratch
+// region of line_bytes; the per-block partial sums [lines][nbmax][F] follow the regions -------------------------------------------------
+constexpr int64_t kCartSplitMaxLines = 128;                   // fsw_embed_cart_split_max_lines: the largest measured line count, and the split form won there
+struct CartSplitPlan {
+  int64_t lines;                                              // rows from the giant class's first bin on x S; 0: no split form for this call
+  size_t line_bytes;                                          // cart_giant_line_bytes: nbmax blocks of kCartGiantBlk keys
+  int nbmax;                                                  // blocks of the longest line
+  size_t partial_offset;                                      // bytes: where the partial sums begin (16-byte aligned)
+  size_t bytes;                                               // fsw_embed_cart_split_scratch_bytes
+};
+// host values only (bin_start_host, max_degree, w, tau, S, F).  No split form: general weights, no row of the class, or above 2 GiB
+inline CartSplitPlan cart_split_plan(const fsw_cart_args* c) {
+  CartSplitPlan p = {};
+  if (!c || !c->bin_start_host || !cart_unit_fast(c) || c->S < 1 || c->F < 1) return p;
+  const CartLongMode& m = kCartLong[0];
+  const int64_t rows = cart_giant_rows(c, m);
+  if (rows <= 0) return p;
+  const size_t cap = (size_t)2 << 30;                          // as fsw_embed_cart_forward_scratch_bytes
+  const size_t line_bytes = cart_giant_line_bytes(m, c->max_degree);
+  const int64_t lines = rows * c->S;
+  if (line_bytes > cap || (size_t)lines > cap / line_bytes) return p;
+  const int64_t nbmax = (int64_t)(line_bytes / (kCartGiantBlk * sizeof(float)));
+  const size_t offset = ((size_t)lines * line_bytes + 15) & ~(size_t)15;
+  const size_t partial = (size_t)lines * (size_t)nbmax * (size_t)c->F * sizeof(float);   // lines * nbmax <= 2^14, F < 2^31
+  if (offset + partial > cap) return p;
+  p.lines = lines; p.line_bytes = line_bytes; p.nbmax = (int)nbmax; p.partial_offset = offset; p.bytes = offset + partial;
+  return p;
+}
+// embed_split_cart.hip: the giant class of kCartLong[0] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)
+int launch_cart_split(const fsw_cart_args* c, const CartSplitPlan& p, hipStream_t stream);
 
 // ---- backward of the giant class: one workgroup of four wavefronts per (row, slice) line; the line as packed (key, entry index) words
 // in sorted runs of kCartMaxLine (one wavefront's chunk), merged by merge path (merge_path64.h) between two scratch lines -------------

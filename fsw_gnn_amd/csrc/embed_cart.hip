@@ -20,6 +20,7 @@
 //   longer lines     (general weights above 16384 elements, any row above 32768; any length) one workgroup per (row, slice), the line
 //                    in sorted blocks in a scratch line: embed_giant_cart.hip (k_cart_giant: bitonic block sweeps) and
 //                    embed_giant_cart_w.hip (k_cart_mergepath_w: merge path).  Their backward: embed_giant_cart_bwd.hip.
+//                    Unit weights with args->flags & FSW_CART_SPLIT_LINES: embed_split_cart.hip, one line split over many workgroups.
 // Readout, by summation by parts of the reference's Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t)):
 //   out = (1 + xi) / (pi xi) sum_t sin(2 pi xi c_t) (p_(t) - p_(t+1)),  p_(L) = 0;   xi = 0:  out = sum_t 2 c_t (p_(t) - p_(t+1)).
 //
@@ -339,6 +340,11 @@ extern "C" size_t fsw_embed_cart_forward_scratch_bytes(const fsw_cart_args* c) {
   return std::max<size_t>(lines, 1) * line_bytes;
 }
 
+// the split form of the longest unit-weight rows (embed_split_cart.hip, embed_cart.h: cart_split_plan): host values only
+extern "C" size_t fsw_embed_cart_split_scratch_bytes(const fsw_cart_args* c) { return cart_split_plan(c).bytes; }
+extern "C" int64_t fsw_embed_cart_split_lines(const fsw_cart_args* c) { return cart_split_plan(c).lines; }
+extern "C" int64_t fsw_embed_cart_split_max_lines(void) { return kCartSplitMaxLines; }
+
 // backward of the tuned entry point: the larger of what the launches of the classes with a scratch line per wavefront need and of one
 // scratch line per workgroup the launcher of the giant class would use (at most 2 GiB, at least one line)
 extern "C" size_t fsw_embed_cart_backward_keys_scratch_bytes(const fsw_cart_args* c) {
@@ -396,6 +402,12 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   FSW_REQUIRE(!unit_fast || (c->unit_table && c->ldt >= c->F), "fsw_embed_cart_f32: unit weights with tau <= 1 need unit_table");
   if (c->num_rows == 0) return 0;
   const int32_t* bs = c->bin_start_host;
+  // FSW_CART_SPLIT_LINES: the giant class in the split form where one exists (lines > 0), refused before any launch when the buffer is short
+  const CartSplitPlan split = (c->flags & FSW_CART_SPLIT_LINES) ? cart_split_plan(c) : CartSplitPlan{};
+  if (split.lines > 0) {
+    FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0 && c->scratch_bytes >= split.bytes,
+                "fsw_embed_cart_f32: FSW_CART_SPLIT_LINES needs a 16-byte aligned scratch buffer of fsw_embed_cart_split_scratch_bytes(args) bytes");
+  }
 
   CartTuned t;
   t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
@@ -437,6 +449,8 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   if (rc) return rc;
   // lines above kCartMaxLine elements (the classes of embed_cart.h: kCartLong): one workgroup of 2 .. 16 wavefronts per line
   if ((rc = unit_fast ? launch_cart_hub(c, stream) : launch_cart_hub_w(c, stream))) return rc;
-  // the giant class (any length): sorted blocks in the scratch lines of c->scratch, one workgroup per line
+  // the giant class (any length): sorted blocks in the scratch lines of c->scratch, one workgroup per line -- or, unit weights with
+  // FSW_CART_SPLIT_LINES, every line split over the workgroups of a launch per phase
+  if (split.lines > 0) return launch_cart_split(c, split, stream);
   return unit_fast ? launch_cart_giant(c, stream) : launch_cart_giant_w(c, stream);
 }

@@ -27,7 +27,9 @@ forward, the line in the registers of 2 .. 16 wavefronts; backward, one wavefron
 length, are sorted in blocks in a scratch line per workgroup in both directions (forward: csrc/embed_giant_cart.hip,
 csrc/embed_giant_cart_w.hip; backward: csrc/embed_giant_cart_bwd.hip), so a float32 call with constant W runs the generic kernel
 nowhere.  The library's table (csrc/embed_cart.h: kCartLong) says which rows go where, the host layer only asks it for the scratch
-sizes (_cart_forward_scratch_bytes, _cart_backward_scratch_bytes).  It needs a HIP device at construction (this
+sizes (_cart_forward_scratch_bytes, _cart_backward_scratch_bytes).  One policy is the host's (_cart_split): a forward whose unit-weight
+rows above 32768 neighbours make few (row, slice) lines -- one point cloud, one graph under FSW_readout -- asks for their split form
+(csrc/embed_split_cart.hip: every phase a launch over (line, block), so one line fills the chip).  It needs a HIP device at construction (this
 package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
 differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
 bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
@@ -999,18 +1001,34 @@ class FSW_embedding(nn.Module):
         a.bin_start_host = graph.bin_start_host[0].ctypes.data
         return int(_lib.lib().fsw_embed_cart_backward_keys_scratch_bytes(ctypes.byref(a)))
 
-    def _cart_scratch(self, graph, st, backward=False, reuse=None):
-        """The scratch buffer of the forward (_cart_forward_scratch_bytes) or of the backward (_cart_backward_scratch_bytes), None for
-        0 bytes; reuse (the forward's buffer) when it is large enough."""
-        nbytes = self._cart_backward_scratch_bytes(graph, st) if backward else self._cart_forward_scratch_bytes(graph, st)
+    def _cart_split(self, graph, st):
+        """The policy of the split form of the longest unit-weight rows (csrc/embed_split_cart.hip), decided ONCE per forward on the
+        module's nSlices, so that every serialize_num_slices chunk takes the same form: bytes of scratch the split form needs, or 0 for the
+        one-workgroup-per-line kernel -- no such row, general weights, or more than fsw_embed_cart_split_max_lines() lines, which fill
+        the chip by themselves.  Host values only."""
+        a = _lib.CartArgs()
+        a.S, a.F, a.tau, a.max_degree = self.nSlices, self.nFreqs, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
+        a.w = graph.w.data_ptr() if graph.w is not None else None
+        a.bin_start_host = graph.bin_start_host[0].ctypes.data
+        L = _lib.lib()
+        lines = int(L.fsw_embed_cart_split_lines(ctypes.byref(a)))
+        if not (0 < lines <= int(L.fsw_embed_cart_split_max_lines())):
+            return 0
+        return int(L.fsw_embed_cart_split_scratch_bytes(ctypes.byref(a)))
+
+    def _cart_scratch(self, graph, st, backward=False, reuse=None, split_bytes=0):
+        """The scratch buffer of the forward (_cart_forward_scratch_bytes; split_bytes of _cart_split if larger) or of the backward
+        (_cart_backward_scratch_bytes), None for 0 bytes; reuse (the forward's buffer) when it is large enough."""
+        nbytes = self._cart_backward_scratch_bytes(graph, st) if backward else max(self._cart_forward_scratch_bytes(graph, st), split_bytes)
         if reuse is not None and reuse.numel() >= nbytes:
             return reuse
         return torch.empty(nbytes, dtype=torch.uint8, device=graph.rowptr.device) if nbytes else None
 
-    def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass):
+    def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass, split=False):
         """struct fsw_cart_args of the tuned entry points (fsw_embed_cart_f32, fsw_embed_cart_backward_keys_f32) without the
-        output / gradient fields."""
+        output / gradient fields.  split: FSW_CART_SPLIT_LINES, for the forward call only (_cart_split)."""
         a = _cart_args(self, Xp, ldp, fr, S, out_scale, has_mass, self._mass_scale_read(st))
+        a.flags = _lib.CART_SPLIT_LINES if split else 0
         a.rowptr, a.col = graph.rowptr.data_ptr(), graph.col.data_ptr()
         a.w = graph.w.data_ptr() if graph.w is not None else None
         a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), graph.bin_start_host[0].ctypes.data
@@ -1023,8 +1041,8 @@ class FSW_embedding(nn.Module):
     def prepare_cartesian(self, X, graph: CSRGraph):
         """What the tuned Cartesian forward needs and its backward needs again: ONE projection of all S slices at
         ldp = round_up(S, 32) -- the call the generic path makes (_project), so both sort bit-identical keys --, the one
-        device->host stats read of the forward (input validation as in prepare()), the unit coefficient table and the scratch of
-        the longest rows."""
+        device->host stats read of the forward (input validation as in prepare()), the unit coefficient table, the form the longest
+        unit-weight rows take ("split": _cart_split) and the scratch of the longest rows."""
         L = _lib.lib()
         S = self.nSlices
         assert X.is_contiguous() and X.dtype == torch.float32 and graph.num_chunks == 1
@@ -1035,8 +1053,9 @@ class FSW_embedding(nn.Module):
                                      None, 0, _lib.ptr(graph.stats_dev), torch.cuda.current_stream(X.device).cuda_stream),
                    "fsw_project_f32")
         st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
+        split_bytes = self._cart_split(graph, st)
         return {"Xp": Xp, "ldp": ldp, "stats": st, "table": self._cart_unit_table(graph, self.freqs.detach().contiguous()),
-                "scratch": self._cart_scratch(graph, st)}
+                "scratch": self._cart_scratch(graph, st, split_bytes=split_bytes), "split": split_bytes > 0}
 
     def embed_cartesian_into(self, X, graph: CSRGraph, out, bias=None, serialize_num_slices=None, out_scale=1.0, prepared=None):
         """Tuned float32 Cartesian forward (fsw_embed_cart_f32) of a CSR graph into out [num_rows, d_out] (unit inner stride): the
@@ -1057,12 +1076,14 @@ class FSW_embedding(nn.Module):
             prepared = self.prepare_cartesian(X, graph)
         if prepared is not None:
             Xp, ldp, st, table, scratch = (prepared[k] for k in ("Xp", "ldp", "stats", "table", "scratch"))
+            split = prepared.get("split", False)
         else:       # chunks of slices: Xp once per forward, refilled by every chunk
             ldp = _round_up(step, 32)
             Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=dev)
             V = self.projVecs.detach()
             table = self._cart_unit_table(graph, fr)
             st = scratch = None
+            split = False
         for k0 in range(0, S, step):
             k1 = min(S, k0 + step)
             if prepared is None:
@@ -1072,10 +1093,12 @@ class FSW_embedding(nn.Module):
                            "fsw_project_f32")
                 if st is None:
                     st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
-                    scratch = self._cart_scratch(graph, st)
+                    split_bytes = self._cart_split(graph, st)    # on all nSlices: every chunk takes the same form
+                    split = split_bytes > 0
+                    scratch = self._cart_scratch(graph, st, split_bytes=split_bytes)
             first = k0 == 0
             col0 = 0 if first else has_mass + k0 * F
-            a = self._cart_tuned_args(graph, st, Xp, ldp, fr, k1 - k0, table, scratch, out_scale, has_mass if first else 0)
+            a = self._cart_tuned_args(graph, st, Xp, ldp, fr, k1 - k0, table, scratch, out_scale, has_mass if first else 0, split=split)
             a.out, a.ldo = out.data_ptr() + 4 * col0, out.stride(0)
             a.bias = (bias.data_ptr() + 4 * col0) if bias is not None else None
             _lib.check(L.fsw_embed_cart_f32(ctypes.byref(a), stream), "fsw_embed_cart_f32")

@@ -403,7 +403,7 @@ typedef struct {
   const void* bias;      /* NULL or [has_mass + S F] */
   double out_scale;
   int32_t mass_fn;
-  int32_t reserved;
+  int32_t flags;         /* 0, or FSW_CART_SPLIT_LINES (fsw_embed_cart_f32 only; every other entry point ignores it) */
   double mass_scale;
   const void* g;
   int64_t ldg;
@@ -443,6 +443,27 @@ size_t fsw_embed_cart_scratch_bytes(const fsw_cart_args* args, int backward);
  *   A buffer of fsw_embed_cart_generic_scratch_bytes(max_degree, 1) bytes still suffices: its 36 * pow2ceil(max_degree + 1) bytes
  *   exceed one line in both modes. */
 size_t fsw_embed_cart_forward_scratch_bytes(const fsw_cart_args* args);
+/* Split form of the longest unit-weight rows (csrc/embed_split_cart.hip): args->flags & FSW_CART_SPLIT_LINES asks fsw_embed_cart_f32 to
+ * run the rows above FSW_HUB_MAX_DEG neighbours (w == NULL and tau <= 1) with every phase -- sorting blocks of 32768 keys, the
+ * exchanges between blocks, the tail of every merge level, the readout -- as a launch of its own over (line, block), so that ONE long line
+ * keeps the whole chip busy instead of one workgroup.  Consecutive launches in the caller's stream are the only synchronisation.
+ * All other rows run as without the flag; a line's output depends on the line only (not on S, the other rows or the scratch's content).
+ *   fsw_embed_cart_split_scratch_bytes  host values only (bin_start_host, max_degree, w, tau, S, F).  With the flag set, args->scratch
+ *       must be 16-byte aligned and hold at least this many bytes, else the call is refused before any launch:
+ *         lines = (rows from the first degree bin of that class on) x S,   nbmax = ceil(max_degree / 32768),
+ *         bytes = lines * nbmax * 32768 * 4   (every line owns a region of block-rounded max_degree keys, 4 bytes each)
+ *               + lines * nbmax * F * 4       (one partial sum per line, block and frequency; the part starts 16-byte aligned).
+ *       0 when there is nothing to split -- w != NULL, tau > 1, no row in that bin, max_degree < 32769 -- or when bytes would exceed
+ *       2 GiB.  Where it is 0 the flag is ignored: the call is then bit-identical to flags == 0 (scratch rules above).
+ *   fsw_embed_cart_split_lines          the lines the split form takes for args (rows x S), 0 where the size query is 0.
+ *   fsw_embed_cart_split_max_lines      the largest line count for which the host layer (fsw_gnn_amd/fsw_embedding.py) sets the flag: with
+ *       more lines the one-workgroup-per-line kernel fills the chip by itself.  At least 16.  The library does what the flag says.
+ * fsw_embed_cart_backward_keys_f32, fsw_embed_cart_generic and fsw_conv_fused_cart_f32 ignore the flag, and so does
+ * fsw_embed_cart_forward_scratch_bytes. */
+#define FSW_CART_SPLIT_LINES 1
+size_t fsw_embed_cart_split_scratch_bytes(const fsw_cart_args* args);
+int64_t fsw_embed_cart_split_lines(const fsw_cart_args* args);
+int64_t fsw_embed_cart_split_max_lines(void);
 /* Scratch of fsw_embed_cart_backward_keys_f32 for the graph and weight mode of args, of which it reads bin_start_host, max_degree, w
  * (NULL or not), tau and S: host values only.  The maximum of two parts, 0 when neither applies:
  *   1. the rows of FSW_LDS_MAX_DEG + 1 .. FSW_HUB_MAX_DEG neighbours (general weights: lines of FSW_LDS_MAX_DEG + 1 ..

@@ -51,10 +51,15 @@ fsw_embed_cart_weighted_backward_scratch_bytes) is driven with the generic kerne
 --giant: the longest rows -- unit weights above 32768 neighbours, general weights from 16384 (csrc/embed_giant_cart.hip,
 csrc/embed_giant_cart_w.hip) --, forward (no_grad) and one training step, S = F = --slices / --freqs: batches of 8 graphs x 24 000
 weighted and 8 x 40 000 unit vertices, the mixed batch 2500 .. 30000 with weights, one cloud of 150 000 and one of 1 000 000 points,
-unit and weighted.  A build without fsw_embed_cart_backward_keys_scratch_bytes (the generic kernel in the backward of these rows) or
+unit and weighted, and 2 and 4 unit clouds of 150 000.  A build without fsw_embed_cart_backward_keys_scratch_bytes (the generic kernel in the backward of these rows) or
 without fsw_embed_cart_forward_scratch_bytes (the generic kernel in both directions) is driven with the scratch
 that kernel needs.
-    python tools/exp_cartesian.py --giant [--workload w24000,u40000,mixed,c150000,c1000000] --steps 3 --warmup 1
+The forward of a unit workload with at most fsw_embed_cart_split_max_lines() lines takes the split form (csrc/embed_split_cart.hip: one line
+over many workgroups); every line of the output names the form.  --form split | giant forces one form for every unit workload (the
+threshold is the host layer's, the library does what the flag says); c150000x2 and c150000x4 are batches of 2 and 4 unit clouds of
+150 000 points (32 and 64 lines).  A build without fsw_embed_cart_split_scratch_bytes has the one-workgroup-per-line kernel only.
+    python tools/exp_cartesian.py --giant [--workload w24000,u40000,mixed,c150000,c150000x2,c150000x4,c1000000] --steps 3 --warmup 1
+    python tools/exp_cartesian.py --giant --workload u40000,c150000,c150000x2,c150000x4 --form split     (and --form giant)
     FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --giant --steps 3 --warmup 1
     rocprofv3 --kernel-trace --stats -d DIR -o giant -- python tools/exp_cartesian.py --giant --workload c150000 --steps 1"""
 import argparse
@@ -87,6 +92,8 @@ ap.add_argument("--hub", action="store_true", help="time the unit-weight hub row
 ap.add_argument("--giant", action="store_true", help="time the longest rows (unit: above 32768 neighbours, weights: from 16384), forward and training step")
 ap.add_argument("--weights", choices=("unit", "uniform", "random"), default="unit",
                 help="--hub: unit weights (the unit hub kernels), or a weight per vertex: 1 / size of its graph, or random in (0.05, 1)")
+ap.add_argument("--form", choices=("auto", "split", "giant"), default="auto",
+                help="--giant: the form of the longest unit-weight rows' forward: the host layer's choice, or one form for every line count")
 ap.add_argument("--tau", type=float, default=1.0, help="--hub: total_mass_pad_thresh of the embedding (> 1: general-weight kernels with w = NULL)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -357,14 +364,26 @@ def giant_leg():
     if not has_giant_bwd:  # the backward of these rows is the generic kernel: its scratch is what the older query says
         drive_without("fsw_embed_cart_backward_keys_scratch_bytes", "_cart_backward_scratch_bytes",
                       lambda self, graph, st: self._cart_scratch_bytes(graph, st, True))
-    print("library %s: forward: %s; backward: %s" % (_lib.LIB_PATH, "kernels of the longest rows" if has_giant else "generic kernel on the longest rows",
-                                                      "kernel of the longest rows" if has_giant_bwd else "generic kernel on the longest rows"), flush=True)
+    has_split = library_exports("fsw_embed_cart_split_scratch_bytes")
+    if not has_split:      # one workgroup per line only: the host layer never asks for the split form
+        for symbol in ("fsw_embed_cart_split_lines", "fsw_embed_cart_split_max_lines"):
+            del _lib._SIGNATURES[symbol]
+        drive_without("fsw_embed_cart_split_scratch_bytes", "_cart_split", lambda self, graph, st: 0)
+    elif args.form != "auto":      # the threshold is the host layer's: move it out of the way
+        top = (1 << 62) if args.form == "split" else 0
+        _lib.lib().fsw_embed_cart_split_max_lines = lambda: top
+    print("library %s: forward: %s; backward: %s; split form: %s" % (
+        _lib.LIB_PATH, "kernels of the longest rows" if has_giant else "generic kernel on the longest rows",
+        "kernel of the longest rows" if has_giant_bwd else "generic kernel on the longest rows",
+        ("--form " + args.form if args.form != "auto" else "up to %d lines" % _lib.lib().fsw_embed_cart_split_max_lines()) if has_split else "none"),
+        flush=True)
     S, F, d = args.slices, args.freqs, 32
     steps, warmup = args.steps, args.warmup
-    workload = "w24000,u40000,mixed,c150000,c1000000" if args.workload == ap.get_default("workload") else args.workload
+    workload = "w24000,u40000,mixed,c150000,c150000x2,c150000x4,c1000000" if args.workload == ap.get_default("workload") else args.workload
     cases = [("w24000", "8 graphs x 24000, weights", [24000] * 8, True), ("u40000", "8 graphs x 40000, unit", [40000] * 8, False),
              ("mixed", "mixed 2500 .. 30000, weights", [2500, 5000, 9000, 12000, 16000, 20000, 25000, 30000], True),
              ("c150000", "one cloud of 150000, unit", [150000], False), ("c150000", "one cloud of 150000, weights", [150000], True),
+             ("c150000x2", "2 clouds of 150000, unit", [150000] * 2, False), ("c150000x4", "4 clouds of 150000, unit", [150000] * 4, False),
              ("c1000000", "one cloud of 1000000, unit", [1000000], False), ("c1000000", "one cloud of 1000000, weights", [1000000], True)]
     torch.manual_seed(7)
     mod = FSW_embedding(d_in=d, nSlices=S, nFreqs=F, collapse_freqs=True, enable_bias=False, learnable_slices=True,
@@ -376,7 +395,7 @@ def giant_leg():
         nv = gi.numel()
         w = (0.05 + 0.95 * torch.rand(nv, generator=torch.Generator().manual_seed(8))).to(dev) if weighted else None
         graph = build_csr(gi.contiguous(), torch.arange(nv, device=dev), w, len(sizes), nv)
-        graph.read_stats()
+        form = "split" if mod._cart_split(graph, graph.read_stats()) > 0 else "one workgroup per line"
         x = torch.randn((nv, d), device=dev)
         xg = x.clone().requires_grad_(True)
         out = torch.empty((len(sizes), S * F), device=dev)
@@ -393,7 +412,8 @@ def giant_leg():
             fwd = bench.timed_ms(lambda: mod.embed_cartesian_into(x, graph, out), steps, dev)
         for _ in range(warmup):
             step()
-        print("%-36s S=%d F=%d  forward %10.3f ms   training step %10.3f ms" % (name, S, F, fwd, bench.timed_ms(step, steps, dev)), flush=True)
+        print("%-36s S=%d F=%d  forward %10.3f ms   training step %10.3f ms   forward form: %s" % (
+            name, S, F, fwd, bench.timed_ms(step, steps, dev), form), flush=True)
         del graph, x, xg, out, G, gi, w
 
 
