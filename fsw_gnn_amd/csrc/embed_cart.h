@@ -1,5 +1,5 @@
 // What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_split_cart.hip, embed_giant_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
-// embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip, embed_giant_cart_bwd.hip) of Cartesian mode share: the degree classes, the
+// embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip, embed_giant_cart_bwd.hip, embed_split_cart_bwd.hip) of Cartesian mode share: the degree classes, the
 // constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
 #pragma once
 #include <algorithm>
@@ -247,5 +247,56 @@ inline int64_t cart_giant_bwd_workgroups(const CartLongMode& m, int64_t held, in
 }
 // embed_giant_cart_bwd.hip: the giant class of the call's mode out of c->scratch (fsw_embed_cart_backward_keys_scratch_bytes)
 int launch_cart_giant_bwd(const fsw_cart_args* c, hipStream_t stream);
+
+// a buffer for `lines` scratch lines of the classes with bwd_line: at most kCartLineMaxWaves of them and 2 GiB (fewer wavefronts then
+// share the work), at least one
+inline size_t cart_line_buffer_bytes(int64_t line_elems, int64_t lines) {
+  const size_t line_bytes = (size_t)line_elems * kCartLineBytes;
+  const size_t cap = (size_t)2 << 30;                            // as embed_global_scratch_bytes
+  const size_t waves = std::min<size_t>((size_t)std::min<int64_t>(lines, kCartLineMaxWaves), cap / line_bytes);
+  return std::max<size_t>(waves, 1) * line_bytes;
+}
+// what the backward of the classes with bwd_line needs (for_each_cart_line_bin); 0 when it launches none: no row that long, or unit
+// weights without a row in the class bins.  Host values only
+inline size_t cart_line_classes_bwd_bytes(const fsw_cart_args* c, const CartLongMode& m) {
+  const int32_t* bs = c->bin_start_host;
+  if (c->max_degree <= m.cls[0].dlo || (m.pad == 0 && bs[m.last().bin_hi + 1] == bs[m.cls[0].bin_lo])) return 0;
+  const int64_t rows = std::max<int64_t>((int64_t)bs[FSW_NUM_BINS] - bs[m.cls[0].bin_lo], 1);
+  return cart_line_buffer_bytes(cart_line_elems(m, std::min<int64_t>(c->max_degree, m.last().dhi)), rows * std::max<int32_t>(c->S, 1));
+}
+
+// ---- split form of the giant class's backward, unit weights (embed_split_cart_bwd.hip; args->flags & FSW_CART_SPLIT_BWD_LINES): every
+// phase of k_cart_giant_bwd<false> is a launch of its own over (line, piece).  Every line owns a scratch region of line_bytes (ping and
+// pong, cart_giant_bwd_line_bytes); the per-tile partial sums of the frequency gradients [lines][ntmax][F] follow the regions ----------
+constexpr int kCartSplitBwdWalk = 256 * 16;                   // ranks of a tile of the walk: 256 threads x kGbVT[0] of k_cart_giant_bwd
+constexpr int64_t kCartSplitBwdMaxLines = 128;                // fsw_embed_cart_split_backward_max_lines: the largest measured line count at which the split form won
+struct CartSplitBwdPlan {
+  int64_t lines;                                              // rows from the giant class's first bin on x S; 0: no split form for this call
+  size_t line_bytes;                                          // cart_giant_bwd_line_bytes: two lines of whole runs
+  int ntmax;                                                  // walk tiles of the longest line
+  size_t partial_offset;                                      // bytes: where the partial sums begin (16-byte aligned)
+  size_t bytes;                                               // fsw_embed_cart_split_backward_scratch_bytes: the rows of the other classes included
+};
+// host values only (bin_start_host, max_degree, w, tau, S, F).  No split form: general weights, no row of the class, or above 2 GiB
+inline CartSplitBwdPlan cart_split_bwd_plan(const fsw_cart_args* c) {
+  CartSplitBwdPlan p = {};
+  if (!c || !c->bin_start_host || !cart_unit_fast(c) || c->S < 1 || c->F < 1) return p;
+  const CartLongMode& m = kCartLong[0];
+  const int64_t rows = cart_giant_rows(c, m);
+  if (rows <= 0) return p;
+  const size_t cap = (size_t)2 << 30;                          // as fsw_embed_cart_backward_keys_scratch_bytes
+  const size_t line_bytes = cart_giant_bwd_line_bytes(m, c->max_degree);
+  const int64_t lines = rows * c->S;
+  if (line_bytes > cap || (size_t)lines > cap / line_bytes) return p;
+  const int64_t ntmax = ceil_div(c->max_degree, (int64_t)kCartSplitBwdWalk);
+  const size_t offset = (size_t)lines * line_bytes;            // a multiple of 16
+  const size_t partial = ((size_t)lines * (size_t)ntmax * (size_t)c->F * sizeof(float) + 15) & ~(size_t)15;   // lines * ntmax < 2^16, F < 2^31
+  if (offset + partial > cap) return p;
+  p.lines = lines; p.line_bytes = line_bytes; p.ntmax = (int)ntmax; p.partial_offset = offset;
+  p.bytes = std::max(offset + partial, cart_line_classes_bwd_bytes(c, m));
+  return p;
+}
+// embed_split_cart_bwd.hip: the giant class of kCartLong[0] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)
+int launch_cart_split_bwd(const fsw_cart_args* c, const CartSplitBwdPlan& p, hipStream_t stream);
 
 }  // namespace fsw

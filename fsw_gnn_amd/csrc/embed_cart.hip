@@ -296,14 +296,6 @@ int cart_check_common(const fsw_cart_args* c) {
 
 using namespace fsw;
 
-// a buffer for `lines` scratch lines: at most kCartLineMaxWaves of them and 2 GiB (fewer wavefronts then share the work), at least one
-static size_t cart_line_buffer_bytes(int64_t line_elems, int64_t lines) {
-  const size_t line_bytes = (size_t)line_elems * kCartLineBytes;
-  const size_t cap = (size_t)2 << 30;                            // as embed_global_scratch_bytes
-  const size_t waves = std::min<size_t>((size_t)std::min<int64_t>(lines, kCartLineMaxWaves), cap / line_bytes);
-  return std::max<size_t>(waves, 1) * line_bytes;
-}
-
 // the backward's scratch for a longest row of max_degree neighbours and long_rows rows from the first class on
 static size_t cart_backward_scratch_bytes(const CartLongMode& m, int64_t max_degree, int64_t long_rows, int32_t S) {
   if (max_degree <= m.cls[0].dlo) return 0;
@@ -350,14 +342,8 @@ extern "C" int64_t fsw_embed_cart_split_max_lines(void) { return kCartSplitMaxLi
 extern "C" size_t fsw_embed_cart_backward_keys_scratch_bytes(const fsw_cart_args* c) {
   if (!c || !c->bin_start_host) return 0;
   const CartLongMode& m = cart_long_mode(cart_unit_fast(c));
-  const int32_t* bs = c->bin_start_host;
   const int32_t S = std::max<int32_t>(c->S, 1);
-  size_t bytes = 0;
-  // unit weights without a row in the class bins launch none of these classes
-  if (c->max_degree > m.cls[0].dlo && !(m.pad == 0 && bs[m.last().bin_hi + 1] == bs[m.cls[0].bin_lo])) {
-    const int64_t rows = std::max<int64_t>((int64_t)bs[FSW_NUM_BINS] - bs[m.cls[0].bin_lo], 1);
-    bytes = cart_line_buffer_bytes(cart_line_elems(m, std::min<int64_t>(c->max_degree, m.last().dhi)), rows * S);
-  }
+  size_t bytes = cart_line_classes_bwd_bytes(c, m);
   const int64_t rows = cart_giant_rows(c, m);
   if (rows > 0) {
     const size_t line_bytes = cart_giant_bwd_line_bytes(m, c->max_degree);
@@ -367,6 +353,11 @@ extern "C" size_t fsw_embed_cart_backward_keys_scratch_bytes(const fsw_cart_args
   }
   return bytes;
 }
+
+// the split form of the longest unit-weight rows' backward (embed_split_cart_bwd.hip, embed_cart.h: cart_split_bwd_plan): host values only
+extern "C" size_t fsw_embed_cart_split_backward_scratch_bytes(const fsw_cart_args* c) { return cart_split_bwd_plan(c).bytes; }
+extern "C" int64_t fsw_embed_cart_split_backward_lines(const fsw_cart_args* c) { return cart_split_bwd_plan(c).lines; }
+extern "C" int64_t fsw_embed_cart_split_backward_max_lines(void) { return kCartSplitBwdMaxLines; }
 
 extern "C" size_t fsw_embed_cart_backward_scratch_bytes(int64_t max_degree, int64_t long_rows, int32_t S) {
   return cart_backward_scratch_bytes(kCartLong[0], max_degree, long_rows, S);

@@ -397,6 +397,13 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
               "fsw_embed_cart_backward_keys_f32: unit weights with tau <= 1 need unit_table and unit_dtable");
   if (c->num_rows == 0) return 0;
   const int32_t* bs = c->bin_start_host;
+  // FSW_CART_SPLIT_BWD_LINES: the giant class in the split form where one exists (lines > 0), refused before any launch when the buffer is short
+  const CartSplitBwdPlan split = (c->flags & FSW_CART_SPLIT_BWD_LINES) ? cart_split_bwd_plan(c) : CartSplitBwdPlan{};
+  if (split.lines > 0) {
+    FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0 && c->scratch_bytes >= split.bytes,
+                "fsw_embed_cart_backward_keys_f32: FSW_CART_SPLIT_BWD_LINES needs a 16-byte aligned scratch buffer of "
+                "fsw_embed_cart_split_backward_scratch_bytes(args) bytes");
+  }
 
   CartBwd t;
   t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
@@ -431,6 +438,8 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
   if (rc) return rc;
   // lines above kCartMaxLine elements (the classes of embed_cart.h: kCartLong): one wavefront per line in a scratch line
   if ((rc = unit_fast ? launch_cart_hub_bwd(c, stream) : launch_cart_hub_w_bwd(c, stream))) return rc;
-  // the giant class (any length): sorted runs + merge path in the scratch lines of c->scratch, one workgroup per line
+  // the giant class (any length): sorted runs + merge path in the scratch lines of c->scratch, one workgroup per line -- or, unit weights
+  // with FSW_CART_SPLIT_BWD_LINES, every line split over the workgroups of a launch per phase
+  if (split.lines > 0) return launch_cart_split_bwd(c, split, stream);
   return launch_cart_giant_bwd(c, stream);
 }

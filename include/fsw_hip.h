@@ -403,7 +403,7 @@ typedef struct {
   const void* bias;      /* NULL or [has_mass + S F] */
   double out_scale;
   int32_t mass_fn;
-  int32_t flags;         /* 0, or FSW_CART_SPLIT_LINES (fsw_embed_cart_f32 only; every other entry point ignores it) */
+  int32_t flags;         /* 0, or bits: FSW_CART_SPLIT_LINES (fsw_embed_cart_f32 only), FSW_CART_SPLIT_BWD_LINES (fsw_embed_cart_backward_keys_f32 only) */
   double mass_scale;
   const void* g;
   int64_t ldg;
@@ -464,6 +464,31 @@ size_t fsw_embed_cart_forward_scratch_bytes(const fsw_cart_args* args);
 size_t fsw_embed_cart_split_scratch_bytes(const fsw_cart_args* args);
 int64_t fsw_embed_cart_split_lines(const fsw_cart_args* args);
 int64_t fsw_embed_cart_split_max_lines(void);
+/* Split form of the longest unit-weight rows' BACKWARD (csrc/embed_split_cart_bwd.hip): args->flags & FSW_CART_SPLIT_BWD_LINES asks
+ * fsw_embed_cart_backward_keys_f32 to run the rows above FSW_HUB_MAX_DEG neighbours (w == NULL and tau <= 1) with every phase -- sorting
+ * runs of FSW_LDS_MAX_DEG packed (key, entry index) words, every merge level, the walk over the sorted line in tiles of 4096 ranks, the
+ * sum of the frequency gradients -- as a launch of its own over (line, piece).  Consecutive launches in the caller's stream are the only
+ * synchronisation.  All other rows run as without the flag.  gkey of these rows is bit-identical to the call without the flag and depends
+ * on the line only (not on S, the other rows or the scratch's content); gfreq differs by the order of summation.
+ *   fsw_embed_cart_split_backward_scratch_bytes  host values only (bin_start_host, max_degree, w, tau, S, F).  With the flag set,
+ *       args->scratch must be 16-byte aligned and hold at least this many bytes, else the call is refused before any launch:
+ *         lines = (rows from the first degree bin of that class on) x S,
+ *         words = max_degree rounded up to whole runs of 2048,   tiles = ceil(max_degree / 4096),
+ *         bytes = lines * words * 16        (every line owns two regions, ping and pong, of 8-byte words)
+ *               + lines * tiles * F * 4     (one partial sum per line, walk tile and frequency), rounded up to a multiple of 16,
+ *       or, where that is larger, what part 1 of fsw_embed_cart_backward_keys_scratch_bytes says for the rows of 2049 .. FSW_HUB_MAX_DEG
+ *       neighbours, which run their kernels out of the same buffer.
+ *       0 when there is nothing to split -- w != NULL, tau > 1, no row in that bin, max_degree < 32769 -- or when the two terms would
+ *       exceed 2 GiB.  Where it is 0 the flag is ignored: the call is then bit-identical to flags without it (scratch rules above).
+ *   fsw_embed_cart_split_backward_lines          the lines the split form takes for args (rows x S), 0 where the size query is 0.
+ *   fsw_embed_cart_split_backward_max_lines      the largest line count for which the host layer (fsw_gnn_amd/fsw_embedding.py) sets
+ *       the flag: the largest measured count at which the split form won.  The library does what the flag says.
+ * fsw_embed_cart_f32, fsw_embed_cart_generic, fsw_conv_fused_cart_f32 and every scratch query above ignore this flag;
+ * fsw_embed_cart_backward_keys_f32 keeps ignoring FSW_CART_SPLIT_LINES. */
+#define FSW_CART_SPLIT_BWD_LINES 2
+size_t fsw_embed_cart_split_backward_scratch_bytes(const fsw_cart_args* args);
+int64_t fsw_embed_cart_split_backward_lines(const fsw_cart_args* args);
+int64_t fsw_embed_cart_split_backward_max_lines(void);
 /* Scratch of fsw_embed_cart_backward_keys_f32 for the graph and weight mode of args, of which it reads bin_start_host, max_degree, w
  * (NULL or not), tau and S: host values only.  The maximum of two parts, 0 when neither applies:
  *   1. the rows of FSW_LDS_MAX_DEG + 1 .. FSW_HUB_MAX_DEG neighbours (general weights: lines of FSW_LDS_MAX_DEG + 1 ..

@@ -58,8 +58,12 @@ The forward of a unit workload with at most fsw_embed_cart_split_max_lines() lin
 over many workgroups); every line of the output names the form.  --form split | giant forces one form for every unit workload (the
 threshold is the host layer's, the library does what the flag says); c150000x2 and c150000x4 are batches of 2 and 4 unit clouds of
 150 000 points (32 and 64 lines).  A build without fsw_embed_cart_split_scratch_bytes has the one-workgroup-per-line kernel only.
+The backward of such a workload takes its own split form (csrc/embed_split_cart_bwd.hip) up to fsw_embed_cart_split_backward_max_lines()
+lines; every line of the output names that form too, --form-bwd split | giant forces one, and a build without
+fsw_embed_cart_split_backward_scratch_bytes has the one-workgroup-per-line backward only.
     python tools/exp_cartesian.py --giant [--workload w24000,u40000,mixed,c150000,c150000x2,c150000x4,c1000000] --steps 3 --warmup 1
     python tools/exp_cartesian.py --giant --workload u40000,c150000,c150000x2,c150000x4 --form split     (and --form giant)
+    python tools/exp_cartesian.py --giant --workload u40000,c150000x2,c150000x4 --form-bwd split         (and --form-bwd giant)
     FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --giant --steps 3 --warmup 1
     rocprofv3 --kernel-trace --stats -d DIR -o giant -- python tools/exp_cartesian.py --giant --workload c150000 --steps 1"""
 import argparse
@@ -94,6 +98,8 @@ ap.add_argument("--weights", choices=("unit", "uniform", "random"), default="uni
                 help="--hub: unit weights (the unit hub kernels), or a weight per vertex: 1 / size of its graph, or random in (0.05, 1)")
 ap.add_argument("--form", choices=("auto", "split", "giant"), default="auto",
                 help="--giant: the form of the longest unit-weight rows' forward: the host layer's choice, or one form for every line count")
+ap.add_argument("--form-bwd", choices=("auto", "split", "giant"), default="auto",
+                help="--giant: the form of the longest unit-weight rows' backward: the host layer's choice, or one form for every line count")
 ap.add_argument("--tau", type=float, default=1.0, help="--hub: total_mass_pad_thresh of the embedding (> 1: general-weight kernels with w = NULL)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -372,11 +378,20 @@ def giant_leg():
     elif args.form != "auto":      # the threshold is the host layer's: move it out of the way
         top = (1 << 62) if args.form == "split" else 0
         _lib.lib().fsw_embed_cart_split_max_lines = lambda: top
-    print("library %s: forward: %s; backward: %s; split form: %s" % (
+    has_split_bwd = library_exports("fsw_embed_cart_split_backward_scratch_bytes")
+    if not has_split_bwd:  # one workgroup per line only: the host layer never asks for the split backward
+        for symbol in ("fsw_embed_cart_split_backward_lines", "fsw_embed_cart_split_backward_max_lines"):
+            del _lib._SIGNATURES[symbol]
+        drive_without("fsw_embed_cart_split_backward_scratch_bytes", "_cart_split_backward", lambda self, graph, st: 0)
+    elif args.form_bwd != "auto":
+        top_bwd = (1 << 62) if args.form_bwd == "split" else 0
+        _lib.lib().fsw_embed_cart_split_backward_max_lines = lambda: top_bwd
+    print("library %s: forward: %s; backward: %s; split form: %s; split backward: %s" % (
         _lib.LIB_PATH, "kernels of the longest rows" if has_giant else "generic kernel on the longest rows",
         "kernel of the longest rows" if has_giant_bwd else "generic kernel on the longest rows",
-        ("--form " + args.form if args.form != "auto" else "up to %d lines" % _lib.lib().fsw_embed_cart_split_max_lines()) if has_split else "none"),
-        flush=True)
+        ("--form " + args.form if args.form != "auto" else "up to %d lines" % _lib.lib().fsw_embed_cart_split_max_lines()) if has_split else "none",
+        ("--form-bwd " + args.form_bwd if args.form_bwd != "auto" else
+         "up to %d lines" % _lib.lib().fsw_embed_cart_split_backward_max_lines()) if has_split_bwd else "none"), flush=True)
     S, F, d = args.slices, args.freqs, 32
     steps, warmup = args.steps, args.warmup
     workload = "w24000,u40000,mixed,c150000,c150000x2,c150000x4,c1000000" if args.workload == ap.get_default("workload") else args.workload
@@ -396,6 +411,7 @@ def giant_leg():
         w = (0.05 + 0.95 * torch.rand(nv, generator=torch.Generator().manual_seed(8))).to(dev) if weighted else None
         graph = build_csr(gi.contiguous(), torch.arange(nv, device=dev), w, len(sizes), nv)
         form = "split" if mod._cart_split(graph, graph.read_stats()) > 0 else "one workgroup per line"
+        form_bwd = "split" if mod._cart_split_backward(graph, graph.read_stats()) > 0 else "one workgroup per line"
         x = torch.randn((nv, d), device=dev)
         xg = x.clone().requires_grad_(True)
         out = torch.empty((len(sizes), S * F), device=dev)
@@ -412,8 +428,8 @@ def giant_leg():
             fwd = bench.timed_ms(lambda: mod.embed_cartesian_into(x, graph, out), steps, dev)
         for _ in range(warmup):
             step()
-        print("%-36s S=%d F=%d  forward %10.3f ms   training step %10.3f ms   forward form: %s" % (
-            name, S, F, fwd, bench.timed_ms(step, steps, dev), form), flush=True)
+        print("%-36s S=%d F=%d  forward %10.3f ms   training step %10.3f ms   forward form: %s   backward form: %s" % (
+            name, S, F, fwd, bench.timed_ms(step, steps, dev), form, form_bwd), flush=True)
         del graph, x, xg, out, G, gi, w
 
 
