@@ -1,4 +1,4 @@
-// What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_split_cart.hip, embed_giant_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
+// What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_split_cart.hip, embed_giant_cart_w.hip, embed_split_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
 // embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip, embed_giant_cart_bwd.hip, embed_split_cart_bwd.hip) of Cartesian mode share: the degree classes, the
 // constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
 #pragma once
@@ -229,6 +229,50 @@ inline CartSplitPlan cart_split_plan(const fsw_cart_args* c) {
 }
 // embed_split_cart.hip: the giant class of kCartLong[0] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)
 int launch_cart_split(const fsw_cart_args* c, const CartSplitPlan& p, hipStream_t stream);
+
+// ---- split form of the giant class's forward, general weights (embed_split_cart_w.hip; args->flags & FSW_CART_SPLIT_W_LINES): every
+// phase of k_cart_mergepath_w is a launch of its own over (line, piece).  Every line owns four block-rounded float lines (keys and
+// weights, ping and pong: cart_giant_line_bytes); behind the regions follow the float64 sums of the weights of every tile of
+// kCartSplitWTile ranks [lines][tiles], the per-tile partial sums [lines][tiles][F] and the float64 partial sums of the rows' masses
+// [rows][nbmax], every part 16-byte aligned -------------------------------------------------------------------------------------------
+constexpr int kCartSplitWTile = kCartGiantWBlk / 2;           // ranks of a tile of the levels and of the readout: half a block (= merge_path.h: kMpTile)
+constexpr int64_t kCartSplitWMaxLines = 256;                  // fsw_embed_cart_split_w_max_lines: the largest measured line count at which the split form won
+static_assert(kCartGiantWBlk % kCartSplitWTile == 0, "tiles must not straddle blocks");
+struct CartSplitWPlan {
+  int64_t lines;                                              // rows from the giant class's first bin on x S; 0: no split form for this call
+  int64_t rows;                                               // lines / S
+  int64_t cap;                                                // elements of each of a line's four float lines: nbmax blocks of kCartGiantWBlk
+  int nbmax, tiles;                                           // blocks / tiles of the longest line
+  size_t tsum_offset, partial_offset, mass_offset;            // bytes: where the tile sums, the partial sums and the mass pieces begin
+  size_t bytes;                                               // fsw_embed_cart_split_w_scratch_bytes
+};
+// host values only (bin_start_host, max_degree, w, tau, S, F).  No split form: unit weights with tau <= 1, no row of the class, or above 2 GiB
+inline CartSplitWPlan cart_split_w_plan(const fsw_cart_args* c) {
+  CartSplitWPlan p = {};
+  if (!c || !c->bin_start_host || cart_unit_fast(c) || c->S < 1 || c->F < 1) return p;
+  const CartLongMode& m = kCartLong[1];
+  const int64_t rows = cart_giant_rows(c, m);
+  if (rows <= 0) return p;
+  const size_t cap = (size_t)2 << 30;                          // as fsw_embed_cart_forward_scratch_bytes
+  const size_t line_bytes = cart_giant_line_bytes(m, c->max_degree);
+  const int64_t lines = rows * c->S;
+  if (line_bytes > cap || (size_t)lines > cap / line_bytes) return p;
+  const int64_t elems = (int64_t)(line_bytes / (4 * sizeof(float)));
+  const int64_t nbmax = elems / kCartGiantWBlk, tiles = elems / kCartSplitWTile;
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t regions = (size_t)lines * line_bytes;           // a multiple of 16
+  const size_t tsum = up16((size_t)lines * (size_t)tiles * sizeof(double));             // lines * tiles <= 2^15
+  if ((size_t)c->F > cap / ((size_t)lines * (size_t)tiles * sizeof(float))) return p;
+  const size_t partial = up16((size_t)lines * (size_t)tiles * (size_t)c->F * sizeof(float));
+  const size_t mass = up16((size_t)rows * (size_t)nbmax * sizeof(double));
+  if (regions + tsum + partial + mass > cap) return p;
+  p.lines = lines; p.rows = rows; p.cap = elems; p.nbmax = (int)nbmax; p.tiles = (int)tiles;
+  p.tsum_offset = regions; p.partial_offset = regions + tsum; p.mass_offset = regions + tsum + partial;
+  p.bytes = regions + tsum + partial + mass;
+  return p;
+}
+// embed_split_cart_w.hip: the giant class of kCartLong[1] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)
+int launch_cart_split_w(const fsw_cart_args* c, const CartSplitWPlan& p, hipStream_t stream);
 
 // ---- backward of the giant class: one workgroup of four wavefronts per (row, slice) line; the line as packed (key, entry index) words
 // in sorted runs of kCartMaxLine (one wavefront's chunk), merged by merge path (merge_path64.h) between two scratch lines -------------

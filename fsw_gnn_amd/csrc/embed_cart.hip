@@ -21,6 +21,7 @@
 //                    in sorted blocks in a scratch line: embed_giant_cart.hip (k_cart_giant: bitonic block sweeps) and
 //                    embed_giant_cart_w.hip (k_cart_mergepath_w: merge path).  Their backward: embed_giant_cart_bwd.hip.
 //                    Unit weights with args->flags & FSW_CART_SPLIT_LINES: embed_split_cart.hip, one line split over many workgroups.
+//                    General weights with args->flags & FSW_CART_SPLIT_W_LINES: embed_split_cart_w.hip, the same.
 // Readout, by summation by parts of the reference's Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t)):
 //   out = (1 + xi) / (pi xi) sum_t sin(2 pi xi c_t) (p_(t) - p_(t+1)),  p_(L) = 0;   xi = 0:  out = sum_t 2 c_t (p_(t) - p_(t+1)).
 //
@@ -337,6 +338,11 @@ extern "C" size_t fsw_embed_cart_split_scratch_bytes(const fsw_cart_args* c) { r
 extern "C" int64_t fsw_embed_cart_split_lines(const fsw_cart_args* c) { return cart_split_plan(c).lines; }
 extern "C" int64_t fsw_embed_cart_split_max_lines(void) { return kCartSplitMaxLines; }
 
+// the split form of the longest general-weight rows (embed_split_cart_w.hip, embed_cart.h: cart_split_w_plan): host values only
+extern "C" size_t fsw_embed_cart_split_w_scratch_bytes(const fsw_cart_args* c) { return cart_split_w_plan(c).bytes; }
+extern "C" int64_t fsw_embed_cart_split_w_lines(const fsw_cart_args* c) { return cart_split_w_plan(c).lines; }
+extern "C" int64_t fsw_embed_cart_split_w_max_lines(void) { return kCartSplitWMaxLines; }
+
 // backward of the tuned entry point: the larger of what the launches of the classes with a scratch line per wavefront need and of one
 // scratch line per workgroup the launcher of the giant class would use (at most 2 GiB, at least one line)
 extern "C" size_t fsw_embed_cart_backward_keys_scratch_bytes(const fsw_cart_args* c) {
@@ -399,6 +405,12 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
     FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0 && c->scratch_bytes >= split.bytes,
                 "fsw_embed_cart_f32: FSW_CART_SPLIT_LINES needs a 16-byte aligned scratch buffer of fsw_embed_cart_split_scratch_bytes(args) bytes");
   }
+  // FSW_CART_SPLIT_W_LINES: the same for general weights (a call has one of the two forms at most: unit weights or not)
+  const CartSplitWPlan split_w = (c->flags & FSW_CART_SPLIT_W_LINES) ? cart_split_w_plan(c) : CartSplitWPlan{};
+  if (split_w.lines > 0) {
+    FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0 && c->scratch_bytes >= split_w.bytes,
+                "fsw_embed_cart_f32: FSW_CART_SPLIT_W_LINES needs a 16-byte aligned scratch buffer of fsw_embed_cart_split_w_scratch_bytes(args) bytes");
+  }
 
   CartTuned t;
   t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
@@ -441,7 +453,8 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   // lines above kCartMaxLine elements (the classes of embed_cart.h: kCartLong): one workgroup of 2 .. 16 wavefronts per line
   if ((rc = unit_fast ? launch_cart_hub(c, stream) : launch_cart_hub_w(c, stream))) return rc;
   // the giant class (any length): sorted blocks in the scratch lines of c->scratch, one workgroup per line -- or, unit weights with
-  // FSW_CART_SPLIT_LINES, every line split over the workgroups of a launch per phase
+  // FSW_CART_SPLIT_LINES (general weights: FSW_CART_SPLIT_W_LINES), every line split over the workgroups of a launch per phase
   if (split.lines > 0) return launch_cart_split(c, split, stream);
+  if (split_w.lines > 0) return launch_cart_split_w(c, split_w, stream);
   return unit_fast ? launch_cart_giant(c, stream) : launch_cart_giant_w(c, stream);
 }

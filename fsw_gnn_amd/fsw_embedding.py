@@ -30,7 +30,8 @@ nowhere.  The library's table (csrc/embed_cart.h: kCartLong) says which rows go 
 sizes (_cart_forward_scratch_bytes, _cart_backward_scratch_bytes).  One policy is the host's (_cart_split): a forward whose unit-weight
 rows above 32768 neighbours make few (row, slice) lines -- one point cloud, one graph under FSW_readout -- asks for their split form
 (csrc/embed_split_cart.hip: every phase a launch over (line, block), so one line fills the chip), and so does its backward
-(_cart_split_backward, csrc/embed_split_cart_bwd.hip).  It needs a HIP device at construction (this
+(_cart_split_backward, csrc/embed_split_cart_bwd.hip); general weights -- a weight tensor, W = 'uniform', total_mass_pad_thresh > 1 --
+have a split form of the forward of their own (_cart_split_w, csrc/embed_split_cart_w.hip).  It needs a HIP device at construction (this
 package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
 differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
 bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
@@ -1019,6 +1020,23 @@ class FSW_embedding(nn.Module):
             return 0
         return int(L.fsw_embed_cart_split_scratch_bytes(ctypes.byref(a)))
 
+    def _cart_split_w(self, graph, st):
+        """The policy of the split form of the longest general-weight rows (csrc/embed_split_cart_w.hip: a weight tensor, W='uniform',
+        total_mass_pad_thresh > 1), decided ONCE per forward on the module's nSlices like _cart_split: bytes of scratch the split form
+        needs, or 0 for the one-workgroup-per-line kernel -- unit weights, no such row, or more than fsw_embed_cart_split_w_max_lines()
+        lines.  Host values only; unit weights leave before the query."""
+        if graph.w is None and self.total_mass_pad_thresh <= 1:
+            return 0
+        a = _lib.CartArgs()
+        a.S, a.F, a.tau, a.max_degree = self.nSlices, self.nFreqs, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
+        a.w = graph.w.data_ptr() if graph.w is not None else None
+        a.bin_start_host = graph.bin_start_host[0].ctypes.data
+        L = _lib.lib()
+        lines = int(L.fsw_embed_cart_split_w_lines(ctypes.byref(a)))
+        if not (0 < lines <= int(L.fsw_embed_cart_split_w_max_lines())):
+            return 0
+        return int(L.fsw_embed_cart_split_w_scratch_bytes(ctypes.byref(a)))
+
     def _cart_split_backward(self, graph, st):
         """The policy of the split form of the longest unit-weight rows' backward (csrc/embed_split_cart_bwd.hip), decided ONCE per
         backward: bytes of scratch the split form needs, or 0 for the one-workgroup-per-line kernel -- no such row, general weights, or
@@ -1037,18 +1055,20 @@ class FSW_embedding(nn.Module):
 
     def _cart_scratch(self, graph, st, backward=False, reuse=None, split_bytes=0):
         """The scratch buffer of the forward (_cart_forward_scratch_bytes) or of the backward (_cart_backward_scratch_bytes), or of
-        split_bytes (_cart_split / _cart_split_backward) if larger; None for 0 bytes; reuse (the forward's buffer) when it is large enough."""
+        split_bytes (_cart_split / _cart_split_w / _cart_split_backward) if larger; None for 0 bytes; reuse (the forward's buffer) when it is large enough."""
         nbytes = max(self._cart_backward_scratch_bytes(graph, st) if backward else self._cart_forward_scratch_bytes(graph, st), split_bytes)
         if reuse is not None and reuse.numel() >= nbytes:
             return reuse
         return torch.empty(nbytes, dtype=torch.uint8, device=graph.rowptr.device) if nbytes else None
 
-    def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass, split=False, split_backward=False):
+    def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass, split=False, split_backward=False, split_w=False):
         """struct fsw_cart_args of the tuned entry points (fsw_embed_cart_f32, fsw_embed_cart_backward_keys_f32) without the
-        output / gradient fields.  split: FSW_CART_SPLIT_LINES, for the forward call only (_cart_split); split_backward:
-        FSW_CART_SPLIT_BWD_LINES, for the backward call only (_cart_split_backward)."""
+        output / gradient fields.  split: FSW_CART_SPLIT_LINES, for the forward call only (_cart_split); split_w: FSW_CART_SPLIT_W_LINES,
+        for the forward call only (_cart_split_w); split_backward: FSW_CART_SPLIT_BWD_LINES, for the backward call only
+        (_cart_split_backward)."""
         a = _cart_args(self, Xp, ldp, fr, S, out_scale, has_mass, self._mass_scale_read(st))
-        a.flags = (_lib.CART_SPLIT_LINES if split else 0) | (_lib.CART_SPLIT_BWD_LINES if split_backward else 0)
+        a.flags = ((_lib.CART_SPLIT_LINES if split else 0) | (_lib.CART_SPLIT_BWD_LINES if split_backward else 0) |
+                   (_lib.CART_SPLIT_W_LINES if split_w else 0))
         a.rowptr, a.col = graph.rowptr.data_ptr(), graph.col.data_ptr()
         a.w = graph.w.data_ptr() if graph.w is not None else None
         a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), graph.bin_start_host[0].ctypes.data
@@ -1062,7 +1082,8 @@ class FSW_embedding(nn.Module):
         """What the tuned Cartesian forward needs and its backward needs again: ONE projection of all S slices at
         ldp = round_up(S, 32) -- the call the generic path makes (_project), so both sort bit-identical keys --, the one
         device->host stats read of the forward (input validation as in prepare()), the unit coefficient table, the form the longest
-        unit-weight rows take ("split": _cart_split) and the scratch of the longest rows."""
+        unit-weight rows take ("split": _cart_split), the form the longest general-weight rows take ("split_w": _cart_split_w) and the
+        scratch of the longest rows."""
         L = _lib.lib()
         S = self.nSlices
         assert X.is_contiguous() and X.dtype == torch.float32 and graph.num_chunks == 1
@@ -1073,9 +1094,10 @@ class FSW_embedding(nn.Module):
                                      None, 0, _lib.ptr(graph.stats_dev), torch.cuda.current_stream(X.device).cuda_stream),
                    "fsw_project_f32")
         st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
-        split_bytes = self._cart_split(graph, st)
+        split_bytes, split_w_bytes = self._cart_split(graph, st), self._cart_split_w(graph, st)    # one of them is 0
         return {"Xp": Xp, "ldp": ldp, "stats": st, "table": self._cart_unit_table(graph, self.freqs.detach().contiguous()),
-                "scratch": self._cart_scratch(graph, st, split_bytes=split_bytes), "split": split_bytes > 0}
+                "scratch": self._cart_scratch(graph, st, split_bytes=max(split_bytes, split_w_bytes)), "split": split_bytes > 0,
+                "split_w": split_w_bytes > 0}
 
     def embed_cartesian_into(self, X, graph: CSRGraph, out, bias=None, serialize_num_slices=None, out_scale=1.0, prepared=None):
         """Tuned float32 Cartesian forward (fsw_embed_cart_f32) of a CSR graph into out [num_rows, d_out] (unit inner stride): the
@@ -1096,14 +1118,14 @@ class FSW_embedding(nn.Module):
             prepared = self.prepare_cartesian(X, graph)
         if prepared is not None:
             Xp, ldp, st, table, scratch = (prepared[k] for k in ("Xp", "ldp", "stats", "table", "scratch"))
-            split = prepared.get("split", False)
+            split, split_w = prepared.get("split", False), prepared.get("split_w", False)
         else:       # chunks of slices: Xp once per forward, refilled by every chunk
             ldp = _round_up(step, 32)
             Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=dev)
             V = self.projVecs.detach()
             table = self._cart_unit_table(graph, fr)
             st = scratch = None
-            split = False
+            split = split_w = False
         for k0 in range(0, S, step):
             k1 = min(S, k0 + step)
             if prepared is None:
@@ -1113,12 +1135,13 @@ class FSW_embedding(nn.Module):
                            "fsw_project_f32")
                 if st is None:
                     st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
-                    split_bytes = self._cart_split(graph, st)    # on all nSlices: every chunk takes the same form
-                    split = split_bytes > 0
-                    scratch = self._cart_scratch(graph, st, split_bytes=split_bytes)
+                    split_bytes, split_w_bytes = self._cart_split(graph, st), self._cart_split_w(graph, st)    # on all nSlices: every chunk takes the same form
+                    split, split_w = split_bytes > 0, split_w_bytes > 0
+                    scratch = self._cart_scratch(graph, st, split_bytes=max(split_bytes, split_w_bytes))
             first = k0 == 0
             col0 = 0 if first else has_mass + k0 * F
-            a = self._cart_tuned_args(graph, st, Xp, ldp, fr, k1 - k0, table, scratch, out_scale, has_mass if first else 0, split=split)
+            a = self._cart_tuned_args(graph, st, Xp, ldp, fr, k1 - k0, table, scratch, out_scale, has_mass if first else 0, split=split,
+                                      split_w=split_w)
             a.out, a.ldo = out.data_ptr() + 4 * col0, out.stride(0)
             a.bias = (bias.data_ptr() + 4 * col0) if bias is not None else None
             _lib.check(L.fsw_embed_cart_f32(ctypes.byref(a), stream), "fsw_embed_cart_f32")

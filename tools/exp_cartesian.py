@@ -65,7 +65,14 @@ fsw_embed_cart_split_backward_scratch_bytes has the one-workgroup-per-line backw
     python tools/exp_cartesian.py --giant --workload u40000,c150000,c150000x2,c150000x4 --form split     (and --form giant)
     python tools/exp_cartesian.py --giant --workload u40000,c150000x2,c150000x4 --form-bwd split         (and --form-bwd giant)
     FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --giant --steps 3 --warmup 1
-    rocprofv3 --kernel-trace --stats -d DIR -o giant -- python tools/exp_cartesian.py --giant --workload c150000 --steps 1"""
+    rocprofv3 --kernel-trace --stats -d DIR -o giant -- python tools/exp_cartesian.py --giant --workload c150000 --steps 1
+--giant --workload splitw: the split form of the longest general-weight rows (csrc/embed_split_cart_w.hip) against the one-workgroup-per-
+line kernel of the SAME library, through the C ABI (fsw_embed_cart_f32 with and without FSW_CART_SPLIT_W_LINES on one projection): one
+weighted cloud of 1 000 000 points, then 1, 2, 4, .. 32 clouds of 150 000 points (16 .. 512 lines at S = 16; the first is the one cloud of 150 000), --weights
+uniform (1 / size of the cloud) | random.  Both forms alternate over --runs runs of --steps calls each, every call on the next of three
+(scratch, output) buffer pairs; the medians and the error of one form against the other are printed:
+    python tools/exp_cartesian.py --giant --workload splitw --weights uniform --steps 20 --warmup 3 --runs 5
+    rocprofv3 --kernel-trace --stats -d DIR -o splitw -- python tools/exp_cartesian.py --giant --workload splitw,c150000 --steps 1 --runs 1"""
 import argparse
 import ctypes
 import os
@@ -378,6 +385,13 @@ def giant_leg():
     elif args.form != "auto":      # the threshold is the host layer's: move it out of the way
         top = (1 << 62) if args.form == "split" else 0
         _lib.lib().fsw_embed_cart_split_max_lines = lambda: top
+    if not library_exports("fsw_embed_cart_split_w_scratch_bytes"):     # general weights: one workgroup per line only
+        for symbol in ("fsw_embed_cart_split_w_lines", "fsw_embed_cart_split_w_max_lines"):
+            del _lib._SIGNATURES[symbol]
+        drive_without("fsw_embed_cart_split_w_scratch_bytes", "_cart_split_w", lambda self, graph, st: 0)
+    elif args.form != "auto":
+        top_w = (1 << 62) if args.form == "split" else 0
+        _lib.lib().fsw_embed_cart_split_w_max_lines = lambda: top_w
     has_split_bwd = library_exports("fsw_embed_cart_split_backward_scratch_bytes")
     if not has_split_bwd:  # one workgroup per line only: the host layer never asks for the split backward
         for symbol in ("fsw_embed_cart_split_backward_lines", "fsw_embed_cart_split_backward_max_lines"):
@@ -410,7 +424,7 @@ def giant_leg():
         nv = gi.numel()
         w = (0.05 + 0.95 * torch.rand(nv, generator=torch.Generator().manual_seed(8))).to(dev) if weighted else None
         graph = build_csr(gi.contiguous(), torch.arange(nv, device=dev), w, len(sizes), nv)
-        form = "split" if mod._cart_split(graph, graph.read_stats()) > 0 else "one workgroup per line"
+        form = "split" if max(mod._cart_split(graph, graph.read_stats()), mod._cart_split_w(graph, graph.read_stats())) > 0 else "one workgroup per line"
         form_bwd = "split" if mod._cart_split_backward(graph, graph.read_stats()) > 0 else "one workgroup per line"
         x = torch.randn((nv, d), device=dev)
         xg = x.clone().requires_grad_(True)
@@ -433,6 +447,69 @@ def giant_leg():
         del graph, x, xg, out, G, gi, w
 
 
+def split_w_leg():
+    """One projection, then fsw_embed_cart_f32 with FSW_CART_SPLIT_W_LINES off and on, alternating."""
+    import statistics
+    L = _lib.lib()
+    S, F, d = args.slices, args.freqs, 32
+    weights = "uniform" if args.weights == "unit" else args.weights
+    print("library %s: split form of general weights against the one-workgroup-per-line kernel, weights %s, S=%d F=%d, host threshold %d lines"
+          % (_lib.LIB_PATH, weights, S, F, L.fsw_embed_cart_split_w_max_lines()), flush=True)
+    torch.manual_seed(7)
+    mod = FSW_embedding(d_in=d, nSlices=S, nFreqs=F, collapse_freqs=True, enable_bias=False, freqs_init='spread', device=dev)
+    fr = mod.freqs.detach().contiguous()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    cases = [[1000000]] + [[150000] * k for k in (1, 2, 4, 8, 16, 32) if k * S <= 512]
+    only = [key for key in args.workload.split(",") if key != "splitw"]      # splitw,c150000x4: that case alone (for a profile)
+    if only:
+        cases = [c for c in cases if ("c%d" % c[0] if len(c) == 1 else "c%dx%d" % (c[0], len(c))) in only]
+    for sizes in cases:
+        gi = torch.cat([torch.full((m,), g, dtype=torch.int64) for g, m in enumerate(sizes)]).to(dev)
+        nv = gi.numel()
+        if weights == "uniform":
+            w = torch.cat([torch.full((m,), 1.0 / m) for m in sizes]).to(dev)
+        else:
+            w = (0.05 + 0.95 * torch.rand(nv, generator=torch.Generator().manual_seed(8))).to(dev)
+        graph = build_csr(gi.contiguous(), torch.arange(nv, device=dev), w, len(sizes), nv)
+        x = torch.randn((nv, d), device=dev)
+        with torch.no_grad():
+            prepared = mod.prepare_cartesian(x, graph)
+        Xp, ldp, st = prepared["Xp"], prepared["ldp"], prepared["stats"]
+        query = mod._cart_tuned_args(graph, st, Xp, ldp, fr, S, None, None, 1.0, 0)
+        nbytes = max(int(L.fsw_embed_cart_forward_scratch_bytes(ctypes.byref(query))), int(L.fsw_embed_cart_split_w_scratch_bytes(ctypes.byref(query))))
+        lines = int(L.fsw_embed_cart_split_w_lines(ctypes.byref(query)))
+        assert lines == len(sizes) * S and nbytes > 0
+        sets = [(torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.empty((len(sizes), S * F), device=dev)) for _ in range(3)]
+        turn = [0]
+
+        def call(flag):
+            scratch, out = sets[turn[0] % len(sets)]
+            turn[0] += 1
+            a = mod._cart_tuned_args(graph, st, Xp, ldp, fr, S, None, scratch, 1.0, 0, split_w=flag)
+            a.out, a.ldo = out.data_ptr(), out.stride(0)
+            _lib.check(L.fsw_embed_cart_f32(ctypes.byref(a), stream), "fsw_embed_cart_f32")
+            return out
+
+        off, on = call(False).clone(), call(True).clone()
+        torch.cuda.synchronize(dev)
+        err = float((on.double() - off.double()).norm() / off.double().norm())
+        ms = {False: [], True: []}
+        for flag in (False, True):
+            for _ in range(args.warmup):
+                call(flag)
+        for _ in range(args.runs):
+            for flag in (False, True):
+                ms[flag].append(bench.timed_ms(lambda: call(flag), args.steps, dev))
+        m_off, m_on = statistics.median(ms[False]), statistics.median(ms[True])
+        print("%2d cloud(s) of %7d, %4d lines: one workgroup per line %8.3f ms (%.3f .. %.3f)   split %8.3f ms (%.3f .. %.3f)   ratio %.2f   "
+              "split against one workgroup per line %.1e" % (len(sizes), sizes[0], lines, m_off, min(ms[False]), max(ms[False]), m_on,
+                                                             min(ms[True]), max(ms[True]), m_off / m_on, err), flush=True)
+        del graph, x, prepared, Xp, sets, gi, w
+
+
+if args.giant and "splitw" in args.workload.split(","):
+    split_w_leg()
+    sys.exit(0)
 if args.giant:
     giant_leg()
     sys.exit(0)
