@@ -12,28 +12,25 @@
 // The sort is stable, so every CSR row keeps its senders in edge-list order: the build is deterministic.
 // rowptr comes from the boundaries of the sorted keys; rows are then bucketed by in-degree so the fused
 // neighbourhood kernels run exact-size sorting networks on runs of equal-degree rows.
+// Scratch: one workspace buffer of fsw_graph_workspace_bytes(rows, edges) bytes, laid out by graph_ws.h (key / value ping-pong, the
+// count table of a pass, the block sums of the device-wide scan -- sized for the longest scan of any entry point, and the scan checks
+// the capacity it is given --, bucket starts, bin counters).
 // (A first version used one global int atomic per edge for the histogram and one for the scatter:
 //  1.13 ms at 10M edges against ~0.3 ms for the sort -- profiles/r01_v1_bench_kernel_stats.csv.)
 #include <algorithm>
 #include <atomic>
 #include "fsw_common.h"
+#include "graph_ws.h"   // the workspace layout and the tile constants it depends on (host only: also built into a CPU test)
 
 namespace fsw {
-
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 16;
-constexpr int kScanTile = kScanThreads * kScanItems;
 
 #ifndef FSW_RS_THREADS
 #define FSW_RS_THREADS 512   // 8 wavefronts x 8 rounds per 4096-edge tile (256 x 16: 0.273 -> 0.253 ms for the build at config 3)
 #endif
 constexpr int kRsThreads = FSW_RS_THREADS;
-constexpr int kRsItems = 4096 / kRsThreads;                      // rounds of 64 consecutive edges per wave
-constexpr int kRsTile = kRsThreads * kRsItems;    // 4096 edges per tile
+constexpr int kRsItems = kRsTile / kRsThreads;                   // rounds of 64 consecutive edges per wave (kRsTile = 4096: graph_ws.h)
+static_assert(kRsThreads * kRsItems == kRsTile, "a tile is a whole number of rounds");
 constexpr int kRsWaves = kRsThreads / kWave;
-constexpr int kRsMaxDigits = 512;                 // 9 bits: the bucket pass of the two-level build (below)
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---- generic device-wide exclusive scan of int32 (three launches) ----------------------------------
 __device__ __forceinline__ int wave_inclusive_scan(int v) {
@@ -106,8 +103,11 @@ __global__ void __launch_bounds__(kScanThreads) k_scan_apply(int32_t* __restrict
   }
 }
 
-static int exclusive_scan_i32(int32_t* data, int64_t n, int32_t* block_sums, hipStream_t stream) {
+// block_sums holds block_sums_cap entries; one per kScanTile elements is needed.  A longer input is refused before any launch.
+static int exclusive_scan_i32(int32_t* data, int64_t n, int32_t* block_sums, int64_t block_sums_cap, hipStream_t stream) {
   const int64_t nb = ceil_div(n, kScanTile);
+  FSW_REQUIRE(nb <= block_sums_cap, "exclusive_scan_i32: %lld elements need %lld block sums, the workspace holds %lld",
+              (long long)n, (long long)nb, (long long)block_sums_cap);
   k_scan_partial<<<(unsigned)nb, kScanThreads, 0, stream>>>(data, n, block_sums);
   FSW_LAUNCH_CHECK();
   k_scan_block_sums<<<1, kScanThreads, 0, stream>>>(block_sums, nb);
@@ -365,7 +365,6 @@ __device__ __forceinline__ unsigned long long match_bin(int bin, bool valid) {
 // overlaps the collective of one node range with the kernels of the next (dist.py).
 constexpr int kBinItems = 8;
 constexpr int kBinRowsPerBlock = 256 * kBinItems;
-constexpr int kMaxRowChunks = 256;
 static_assert(kBinRowsPerBlock == FSW_BIN_BLOCK_ROWS, "include/fsw_hip.h documents the chunk granularity");
 
 __global__ void __launch_bounds__(256) k_bin_count(const int32_t* __restrict__ rowptr, int64_t n, int64_t chunk_rows,
@@ -477,43 +476,6 @@ __global__ void __launch_bounds__(256) k_bin_rows(const int32_t* __restrict__ ro
   }
 }
 
-// ---- workspace ---------------------------------------------------------------------------------------------------
-constexpr size_t kBinTableBytes = sizeof(int32_t) * kMaxRowChunks * FSW_NUM_BINS;
-
-struct GraphWs {
-  uint32_t* keys[2];
-  void* vals[2];
-  int32_t* counts;      // [ndigits][ntiles]
-  int32_t* block_sums;  // scan scratch
-  int32_t* block_sums_big;  // bucket starts of the two-level build (multi-pass case): rows / 2^11 + 2 entries
-  int32_t* bin_count;
-  int32_t* bin_cursor;
-  size_t total;
-};
-
-static GraphWs carve(void* ws, int64_t num_edges, int64_t num_rows = 0) {
-  const size_t E = (size_t)std::max<int64_t>(num_edges, 1);
-  const size_t ntiles = (size_t)ceil_div((int64_t)E, kRsTile);
-  char* p = reinterpret_cast<char*>(ws);
-  GraphWs g;
-  auto take = [&](size_t bytes) {
-    char* q = p;
-    p += align_up(bytes, 256);
-    return q;
-  };
-  g.keys[0] = reinterpret_cast<uint32_t*>(take(4 * E));
-  g.keys[1] = reinterpret_cast<uint32_t*>(take(4 * E));
-  g.vals[0] = take(8 * E);
-  g.vals[1] = take(8 * E);
-  g.counts = reinterpret_cast<int32_t*>(take(4 * (size_t)kRsMaxDigits * ntiles));
-  g.block_sums = reinterpret_cast<int32_t*>(take(4 * (size_t)(ceil_div((int64_t)(kRsMaxDigits * ntiles), kScanTile) + 1)));
-  g.block_sums_big = reinterpret_cast<int32_t*>(take(4 * (size_t)((num_rows >> 10) + 3)));
-  g.bin_count = reinterpret_cast<int32_t*>(take(kBinTableBytes));
-  g.bin_cursor = reinterpret_cast<int32_t*>(take(kBinTableBytes));
-  g.total = (size_t)(p - reinterpret_cast<char*>(ws));
-  return g;
-}
-
 // LSD radix sort of E (key, value) pairs.  first_a / first_b: the int64 arrays the FIRST pass reads directly
 // (key = first_a[e], valid when 0 <= first_a[e] < range_a and 0 <= first_b[e] < range_b; invalid edges get the
 // sentinel key range_a and sort last).  keys_in != NULL: pre-built uint32 keys instead (values from g.vals[*cur]).
@@ -551,7 +513,7 @@ static int radix_sort_pairs(const int64_t* first_a, const int64_t* first_b, cons
       k_rs_upsweep<false><<<(unsigned)ntiles, kRsThreads, 0, stream>>>(nullptr, nullptr, nullptr, kin, num_edges, range_a,
                                                                        range_b, shift, ndigits, g.counts, ntiles, stats);
     FSW_LAUNCH_CHECK();
-    int rc = exclusive_scan_i32(g.counts, (int64_t)ndigits * ntiles, g.block_sums, stream);
+    int rc = exclusive_scan_i32(g.counts, (int64_t)ndigits * ntiles, g.block_sums, g.block_sums_cap, stream);
     if (rc) return rc;
     if (first)
       k_rs_downsweep<true, VAL, EID><<<(unsigned)ntiles, kRsThreads, 0, stream>>>(first_a, first_b, edge_w, nullptr, nullptr, num_edges,
@@ -995,7 +957,7 @@ extern "C" int fsw_graph_build_coalesced(const int64_t* recipients, const int64_
   k_mark_heads<<<edge_blocks, 256, 0, stream>>>(keys, eid, senders, num_edges, num_rows, head);
   FSW_LAUNCH_CHECK();
   FSW_CHECK_HIP(hipMemcpyAsync(pos, head, sizeof(int32_t) * (size_t)num_edges, hipMemcpyDeviceToDevice, stream));
-  if ((rc = exclusive_scan_i32(pos, num_edges, g.block_sums, stream))) return rc;
+  if ((rc = exclusive_scan_i32(pos, num_edges, g.block_sums, g.block_sums_cap, stream))) return rc;
   int32_t* nnz_dev = stats + FSW_STAT_NNZ;
   k_emit_coalesced<<<edge_blocks, 256, 0, stream>>>(keys, eid, head, pos, senders, edge_w, edge_feat, d_edge, num_edges, num_rows,
                                                     keyc, col, w, ef, slot_of_edge, nnz_dev);

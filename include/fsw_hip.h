@@ -108,6 +108,10 @@ const char* fsw_last_error(void); /* host string, valid until the next failing c
  *                the collective of one node range with the kernels of the next this way.                          */
 #define FSW_BIN_BLOCK_ROWS 2048
 #define FSW_MAX_ROW_CHUNKS 256
+/* workspace: one scratch buffer of fsw_graph_workspace_bytes(num_rows, num_edges) bytes for the three builds below (and, with
+ * (num_cols, nnz), for fsw_graph_transpose).  About 24 bytes per edge: key and value ping-pong, the count table of a radix pass,
+ * the block sums of the device-wide scan (sized for the longest scan of any entry point: one int per 4096 edges), bucket starts
+ * and bin counters -- csrc/graph_ws.h.  Query it for every call; a smaller buffer is refused with a status.                    */
 size_t fsw_graph_workspace_bytes(int64_t num_rows, int64_t num_edges);
 int fsw_graph_build(const int64_t* recipients, const int64_t* senders, const float* edge_w,
                     int64_t num_edges, int64_t num_rows, int64_t num_cols, int64_t chunk_rows,
