@@ -80,6 +80,7 @@ _SIGNATURES = {
                                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "fsw_graph_build": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "fsw_graph_build_two_level": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "fsw_graph_build_plan": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.c_int, ctypes.POINTER(c_i32)]),
     "fsw_project_f32": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_vp, ctypes.c_int, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "fsw_gemm_tn_workspace_bytes": (c_sz, [ctypes.c_int, ctypes.c_int]),
     "fsw_gemm_tn_f32": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_f32, c_vp, c_sz, c_vp]),

@@ -21,6 +21,7 @@
 #include <atomic>
 #include "fsw_common.h"
 #include "graph_ws.h"   // the workspace layout and the tile constants it depends on (host only: also built into a CPU test)
+#include "graph_plan.h" // the packed edge word and the plan of the two-level build (host helpers: also built into a CPU test)
 
 namespace fsw {
 
@@ -96,6 +97,25 @@ __global__ void __launch_bounds__(kScanThreads) k_scan_apply(int32_t* __restrict
   }
   int tot;
   int ex = block_exclusive_scan(s, &tot) + block_sums[blockIdx.x];
+#pragma unroll
+  for (int i = 0; i < kScanItems; ++i) {
+    if (base + i < n) data[base + i] = ex;
+    ex += v[i];
+  }
+}
+
+// A table of at most kScanTile elements (the count table of a packed partition pass over a small graph): one workgroup, one launch.
+__global__ void __launch_bounds__(kScanThreads) k_scan_one(int32_t* __restrict__ data, int64_t n) {
+  const int64_t base = (int64_t)threadIdx.x * kScanItems;
+  int v[kScanItems];
+  int s = 0;
+#pragma unroll
+  for (int i = 0; i < kScanItems; ++i) {
+    v[i] = base + i < n ? data[base + i] : 0;
+    s += v[i];
+  }
+  int tot;
+  int ex = block_exclusive_scan(s, &tot);
 #pragma unroll
   for (int i = 0; i < kScanItems; ++i) {
     if (base + i < n) data[base + i] = ex;
@@ -324,6 +344,193 @@ __global__ void __launch_bounds__(kRsThreads) k_rs_downsweep(const int64_t* __re
   }
 }
 
+// ---- packed partition pass: the only pass of the unit-weight two-level build when an edge fits one word (graph_plan.h) ----------
+// The kernels above with two differences: a tile is kPackTile edges, and the downsweep writes ONE uint32 per edge -- the low rb row
+// bits and the sender -- into runs that are twice as long.  The digit (= bucket, the row bits from rb upwards) is not part of the
+// word, so the tile-local reorder keeps it beside the word in LDS (16 bits).
+constexpr int kPackItems = kPackTile / kRsThreads;   // rounds of 64 consecutive edges per wave
+constexpr int kPackAhead = 8;                        // rounds whose loads are in flight together
+static_assert(kRsThreads * kPackItems == kPackTile && kPackItems % kPackAhead == 0, "a packed tile is a whole number of load groups");
+static_assert(kRsMaxDigits <= (1 << 16), "the digit of an edge is kept in 16 bits");
+constexpr size_t kPackLdsBytes = sizeof(int) * (size_t)(kRsWaves + 2) * kRsMaxDigits + (sizeof(uint32_t) + sizeof(uint16_t)) * (size_t)kPackTile;
+
+// key of one edge from its two endpoints (load_key<true> on values already loaded)
+__device__ __forceinline__ uint32_t key_of(int64_t r, int64_t c, int64_t num_rows, int64_t num_cols, int& flags) {
+  if (r < 0 || r >= num_rows || c < 0 || c >= num_cols) {
+    flags |= FSW_FLAG_INDEX_RANGE;
+    return (uint32_t)num_rows;
+  }
+  return (uint32_t)r;
+}
+
+// VEC: both endpoint arrays are 16-byte aligned (a tile starts at an even edge): a lane reads two consecutive edges with one 16-byte
+// load per array.  The histogram needs no order, so which lane counts which edge does not matter.
+template <bool VEC>
+__global__ void __launch_bounds__(kRsThreads) k_pack_upsweep(const int64_t* __restrict__ recipients, const int64_t* __restrict__ senders,
+                                                             int64_t num_edges, int64_t num_rows, int64_t num_cols, int shift, int ndigits,
+                                                             int32_t* __restrict__ counts /* [ndigits][ntiles] */, int64_t ntiles,
+                                                             int32_t* __restrict__ stats) {
+  __shared__ int hist[kRsMaxDigits];
+  for (int d = threadIdx.x; d < ndigits; d += kRsThreads) hist[d] = 0;
+  __syncthreads();
+  const int64_t tile0 = (int64_t)blockIdx.x * kPackTile;
+  const uint32_t mask = (uint32_t)ndigits - 1;
+  int flags = 0;
+  if constexpr (VEC) {
+    constexpr int kPairs = kPackItems / 2, kPairsAhead = kPackAhead / 2;
+    static_assert(kPackItems % 2 == 0 && kPairs % kPairsAhead == 0, "pairs of edges in whole load groups");
+#pragma unroll
+    for (int h = 0; h < kPairs / kPairsAhead; ++h) {
+      uint32_t key[kPairsAhead][2];
+#pragma unroll
+      for (int i = 0; i < kPairsAhead; ++i) {
+        const int64_t e = tile0 + 2 * ((int64_t)(h * kPairsAhead + i) * kRsThreads + threadIdx.x);
+        key[i][0] = key[i][1] = 0xffffffffu;
+        if (e + 1 < num_edges) {
+          const longlong2 r = *reinterpret_cast<const longlong2*>(recipients + e);
+          const longlong2 c = *reinterpret_cast<const longlong2*>(senders + e);
+          key[i][0] = key_of(r.x, c.x, num_rows, num_cols, flags);
+          key[i][1] = key_of(r.y, c.y, num_rows, num_cols, flags);
+        } else if (e < num_edges) {
+          key[i][0] = key_of(recipients[e], senders[e], num_rows, num_cols, flags);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < kPairsAhead; ++i) {
+        const int64_t e = tile0 + 2 * ((int64_t)(h * kPairsAhead + i) * kRsThreads + threadIdx.x);
+        if (e < num_edges) atomicAdd(&hist[(key[i][0] >> shift) & mask], 1);
+        if (e + 1 < num_edges) atomicAdd(&hist[(key[i][1] >> shift) & mask], 1);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int h = 0; h < kPackItems / kPackAhead; ++h) {
+      uint32_t key[kPackAhead];
+#pragma unroll
+      for (int i = 0; i < kPackAhead; ++i) {
+        const int64_t e = tile0 + (int64_t)(h * kPackAhead + i) * kRsThreads + threadIdx.x;
+        key[i] = 0xffffffffu;
+        if (e < num_edges) key[i] = key_of(recipients[e], senders[e], num_rows, num_cols, flags);
+      }
+#pragma unroll
+      for (int i = 0; i < kPackAhead; ++i)
+        if (tile0 + (int64_t)(h * kPackAhead + i) * kRsThreads + threadIdx.x < num_edges) atomicAdd(&hist[(key[i] >> shift) & mask], 1);
+    }
+  }
+  __syncthreads();
+  for (int d = threadIdx.x; d < ndigits; d += kRsThreads) counts[(int64_t)d * ntiles + blockIdx.x] = hist[d];
+  if (flags) atomicOr(&stats[FSW_STAT_FLAGS], flags);
+}
+
+__global__ void __launch_bounds__(kRsThreads) k_pack_downsweep(const int64_t* __restrict__ recipients, const int64_t* __restrict__ senders,
+                                                               int64_t num_edges, int64_t num_rows, int64_t num_cols, int rb, int cb,
+                                                               int nbits, const int32_t* __restrict__ bases /* scanned [ndigits][ntiles] */,
+                                                               int64_t ntiles, uint32_t* __restrict__ words_out) {
+  extern __shared__ int psm[];   // wcnt[kRsWaves][kRsMaxDigits] | dstart[kRsMaxDigits] | gbase[kRsMaxDigits] | sword[kPackTile] | sdig[kPackTile]
+  int* wcnt = psm;                                       // per-wave digit counters, then exclusive wave bases
+  int* dstart = psm + kRsWaves * kRsMaxDigits;           // tile-local exclusive start of each digit
+  int* gbase = dstart + kRsMaxDigits;                    // global base of (this tile, digit)
+  uint32_t* sword = reinterpret_cast<uint32_t*>(gbase + kRsMaxDigits);
+  uint16_t* sdig = reinterpret_cast<uint16_t*>(sword + kPackTile);
+  const int ndigits = 1 << nbits;
+  const uint32_t mask = (uint32_t)ndigits - 1, rmask = (1u << rb) - 1u;
+  const int lane = lane_id(), wv = threadIdx.x >> 6;
+  int* mine = wcnt + wv * kRsMaxDigits;
+  for (int d = threadIdx.x; d < ndigits; d += kRsThreads) {
+#pragma unroll
+    for (int w = 0; w < kRsWaves; ++w) wcnt[w * kRsMaxDigits + d] = 0;
+    gbase[d] = bases[(int64_t)d * ntiles + blockIdx.x];
+  }
+  __syncthreads();
+
+  // wave wv owns kPackItems rounds of 64 consecutive edges (stable order)
+  const int64_t wave0 = (int64_t)blockIdx.x * kPackTile + (int64_t)wv * (kPackItems * kWave);
+  uint32_t word[kPackItems];
+  int dig[kPackItems], rank[kPackItems];
+  int dummy = 0;
+#pragma unroll
+  for (int h = 0; h < kPackItems / kPackAhead; ++h) {
+    uint32_t key[kPackAhead], snd[kPackAhead];
+#pragma unroll
+    for (int u = 0; u < kPackAhead; ++u) {
+      const int64_t e = wave0 + (int64_t)(h * kPackAhead + u) * kWave + lane;
+      key[u] = 0xffffffffu;
+      snd[u] = 0u;
+      if (e < num_edges) {
+        key[u] = load_key<true>(recipients, senders, nullptr, e, num_rows, num_cols, dummy);
+        snd[u] = (uint32_t)senders[e];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kPackAhead; ++u) {
+      const int i = h * kPackAhead + u;
+      const bool ok = wave0 + (int64_t)i * kWave + lane < num_edges;
+      const uint32_t d = (key[u] >> rb) & mask;
+      // an edge with an endpoint out of range: the sentinel row, sender 0 (its sender may hold anything)
+      word[i] = pack_edge(key[u], rmask, cb, (int64_t)key[u] < num_rows ? snd[u] : 0u);
+      dig[i] = (int)d;
+      const unsigned long long peers = match_digit<9>(d, ok);
+      const int leader = __ffsll((long long)peers) - 1;
+      const int below = __popcll(peers & ((1ull << lane) - 1ull));
+      int prev = 0;
+      if (ok && lane == leader) {
+        prev = mine[d];
+        mine[d] = prev + __popcll(peers);
+      }
+      prev = __shfl(prev, leader);
+      rank[i] = prev + below;
+    }
+  }
+  __syncthreads();
+  // per digit: exclusive bases across waves and the tile-local digit start
+  for (int d = threadIdx.x; d < ndigits; d += kRsThreads) {
+    int acc = 0;
+#pragma unroll
+    for (int w = 0; w < kRsWaves; ++w) {
+      const int c = wcnt[w * kRsMaxDigits + d];
+      wcnt[w * kRsMaxDigits + d] = acc;
+      acc += c;
+    }
+    dstart[d] = acc;  // tile total for now
+  }
+  __syncthreads();
+  if (threadIdx.x < kWave) {  // exclusive scan of the tile totals over the digits (<= kRsMaxDigits = 8 per lane)
+    constexpr int kPer = kRsMaxDigits / kWave;
+    int v[kPer], s = 0;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      const int d = lane * kPer + j;
+      v[j] = d < ndigits ? dstart[d] : 0;
+      s += v[j];
+    }
+    int ex = wave_inclusive_scan(s) - s;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      const int d = lane * kPer + j;
+      if (d < ndigits) dstart[d] = ex;
+      ex += v[j];
+    }
+  }
+  __syncthreads();
+  // tile-local reorder through LDS
+#pragma unroll
+  for (int i = 0; i < kPackItems; ++i) {
+    const int64_t e = wave0 + (int64_t)i * kWave + lane;
+    if (e < num_edges) {
+      const int lpos = dstart[dig[i]] + mine[dig[i]] + rank[i];
+      sword[lpos] = word[i];
+      sdig[lpos] = (uint16_t)dig[i];
+    }
+  }
+  __syncthreads();
+  const int64_t tile0 = (int64_t)blockIdx.x * kPackTile;
+  const int count = (int)min((int64_t)kPackTile, num_edges - tile0);
+  for (int i = threadIdx.x; i < count; i += kRsThreads) {
+    const int d = sdig[i];
+    words_out[(int64_t)gbase[d] + (i - dstart[d])] = sword[i];
+  }
+}
+
 // ---- rowptr from the sorted keys, col / w from the sorted values --------------------------------------------
 template <class VAL>
 __global__ void __launch_bounds__(256) k_finish_csr(const uint32_t* __restrict__ keys, const VAL* __restrict__ vals,
@@ -436,6 +643,44 @@ __global__ void __launch_bounds__(kMaxRowChunks) k_bin_offsets(const int32_t* __
   }
 }
 
+// k_bin_offsets without its serial walk (the packed path): one wavefront per chunk.  Lane b holds the count of bin b, a wave scan gives
+// the bin's offset inside the chunk, and the chunk's base is the sum of all counters of the chunks before it (coalesced loads, a
+// wave reduction) -- no thread walks 50 dependent loads, and the chunks do not wait for one thread's scan over them.
+static_assert(FSW_NUM_BINS <= kWave, "one lane per bin");
+__global__ void __launch_bounds__(kWave) k_bin_offsets_wave(const int32_t* __restrict__ bin_count, int32_t* __restrict__ bin_start,
+                                                            int32_t* __restrict__ bin_cursor, int32_t* __restrict__ stats,
+                                                            const int32_t* __restrict__ rowptr, int64_t num_rows) {
+  const int c = blockIdx.x, b = threadIdx.x;
+  if (c == 0 && b == 0) stats[FSW_STAT_NNZ] = rowptr[num_rows];
+  int before = 0;
+  for (int i = b; i < c * FSW_NUM_BINS; i += kWave) before += bin_count[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
+  const int cnt = b < FSW_NUM_BINS ? bin_count[c * FSW_NUM_BINS + b] : 0;
+  const int inc = wave_inclusive_scan(cnt);
+  if (b < FSW_NUM_BINS) {
+    bin_start[c * (FSW_NUM_BINS + 1) + b] = before + inc - cnt;
+    bin_cursor[c * FSW_NUM_BINS + b] = before + inc - cnt;
+  }
+  if (b == FSW_NUM_BINS - 1) bin_start[c * (FSW_NUM_BINS + 1) + FSW_NUM_BINS] = before + inc;
+  // the stats words: sums of the counters over classes of bins
+  int reg = (b >= 1 && b <= FSW_REG_MAX_DEG) ? cnt : 0;
+  int mid = (b >= FSW_BIN_MID0 && b < FSW_BIN_HUB0) ? cnt : 0;
+  int glob = (b >= FSW_BIN_HUB0 && b <= FSW_BIN_GLOBAL) ? cnt : 0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    reg += __shfl_xor(reg, off);
+    mid += __shfl_xor(mid, off);
+    glob += __shfl_xor(glob, off);
+  }
+  if (b == 0) {
+    if (cnt) atomicAdd(&stats[FSW_STAT_NUM_ZERO_DEG], cnt);
+    if (reg) atomicAdd(&stats[FSW_STAT_NUM_REG], reg);
+    if (mid) atomicAdd(&stats[FSW_STAT_NUM_LDS], mid);
+    if (glob) atomicAdd(&stats[FSW_STAT_NUM_GLOBAL], glob);
+  }
+}
+
 // A workgroup places kBinRowsPerBlock consecutive rows: per-bin counts accumulate in LDS over the rounds (a lane's rank
 // is the running count before its round + its rank among its wave peers), then ONE global atomic per bin claims the
 // workgroup's range -- the cursors of a chunk are shared by all its workgroups, so same-address atomics are the cost to
@@ -479,13 +724,7 @@ __global__ void __launch_bounds__(256) k_bin_rows(const int32_t* __restrict__ ro
 // LSD radix sort of E (key, value) pairs.  first_a / first_b: the int64 arrays the FIRST pass reads directly
 // (key = first_a[e], valid when 0 <= first_a[e] < range_a and 0 <= first_b[e] < range_b; invalid edges get the
 // sentinel key range_a and sort last).  keys_in != NULL: pre-built uint32 keys instead (values from g.vals[*cur]).
-// On return *cur selects the ping-pong buffer that holds the result.
-static int key_bits(int64_t range_a) {
-  int keybits = 1;
-  while ((1ll << keybits) <= range_a) ++keybits;  // values 0 .. range_a (sentinel) must fit
-  return keybits;
-}
-
+// On return *cur selects the ping-pong buffer that holds the result.  (key_bits: graph_plan.h -- values 0 .. range_a, the sentinel, must fit.)
 // lo_bit > 0: only the key bits from lo_bit upwards are sorted (the two-level build finishes the low bits bucket by bucket),
 // in passes of up to max_bits bits.
 template <class VAL, bool EID>
@@ -601,14 +840,24 @@ __global__ void __launch_bounds__(256) k_rowptr_from_keys(const uint32_t* __rest
   }
 }
 
+// chunk_rows == 0: one chunk of all rows
+static int64_t one_chunk_if_zero(int64_t num_rows, int64_t chunk_rows) {
+  return chunk_rows > 0 ? chunk_rows : ceil_div(num_rows, kBinRowsPerBlock) * kBinRowsPerBlock;
+}
+
 static int finish_bins(int32_t* rowptr, int64_t num_rows, int64_t chunk_rows, int32_t* perm, int32_t* invperm, int32_t* bin_start,
-                       int32_t* stats, GraphWs& g, hipStream_t stream) {
-  if (chunk_rows <= 0) chunk_rows = ceil_div(num_rows, kBinRowsPerBlock) * kBinRowsPerBlock;   // one chunk
+                       int32_t* stats, GraphWs& g, hipStream_t stream, bool counted = false) {
+  chunk_rows = one_chunk_if_zero(num_rows, chunk_rows);
   const int num_chunks = (int)ceil_div(num_rows, chunk_rows);
   const int row_blocks = (int)ceil_div(num_rows, kBinRowsPerBlock);
-  k_bin_count<<<row_blocks, 256, 0, stream>>>(rowptr, num_rows, chunk_rows, g.bin_count, stats);
-  FSW_LAUNCH_CHECK();
-  k_bin_offsets<<<1, kMaxRowChunks, 0, stream>>>(g.bin_count, bin_start, g.bin_cursor, stats, num_chunks, rowptr, num_rows);
+  if (!counted) {   // counted: bin_count and the maximal degree came from the bucket kernel of the packed two-level build
+    k_bin_count<<<row_blocks, 256, 0, stream>>>(rowptr, num_rows, chunk_rows, g.bin_count, stats);
+    FSW_LAUNCH_CHECK();
+  }
+  if (counted)
+    k_bin_offsets_wave<<<num_chunks, kWave, 0, stream>>>(g.bin_count, bin_start, g.bin_cursor, stats, rowptr, num_rows);
+  else
+    k_bin_offsets<<<1, kMaxRowChunks, 0, stream>>>(g.bin_count, bin_start, g.bin_cursor, stats, num_chunks, rowptr, num_rows);
   FSW_LAUNCH_CHECK();
   k_bin_rows<<<row_blocks, 256, 0, stream>>>(rowptr, num_rows, chunk_rows, g.bin_cursor, perm, invperm);
   FSW_LAUNCH_CHECK();
@@ -628,11 +877,7 @@ static int finish_bins(int32_t* rowptr, int64_t num_rows, int64_t chunk_rows, in
 // L2: they merge there and reach HBM as whole lines.  A bucket of any size is handled (the workgroup just loops longer), so the
 // result never depends on the edge distribution -- but a hub-heavy bucket serialises on its workgroup, which is why the host
 // side keeps the LSD build for skewed graphs (graph.py).
-constexpr int kBucketWaves = 8;
-#ifndef FSW_BUCKET_ROW_BITS
-#define FSW_BUCKET_ROW_BITS 11
-#endif
-constexpr int kBucketMaxRowBits = FSW_BUCKET_ROW_BITS;   // LDS: (kBucketWaves + 1) * 2^bits ints (72 KB at 11, 144 KB at 12)
+// kBucketWaves = 8 wavefronts per bucket, kBucketMaxRowBits = 11 row bits: graph_ws.h (LDS: (kBucketWaves + 1) * 2^bits ints, 72 KB at 11)
 constexpr int kBucketAhead = 8;                          // rounds of 64 edges whose loads are in flight together
 
 template <class VAL>
@@ -779,6 +1024,158 @@ __global__ void __launch_bounds__(kBucketWaves * kWave) k_bucket_rows(const uint
   }
 }
 
+// The bucket kernel of the packed path (graph_plan.h): one word per edge -- row inside the bucket and sender -- read twice instead of a
+// key read twice and a sender; the row of a word is b * R + its row field, which is what the `key < num_rows` test above becomes.
+// Its scan step holds the degree of every row of the bucket in registers, so it also counts the rows' degree bins and the maximal
+// degree (what k_bin_count re-reads rowptr for): one LDS table, then at most one global atomic per non-empty bin.  A bucket is
+// FSW_BIN_BLOCK_ROWS rows, the granularity of a row chunk, so it lies inside ONE chunk; the sentinel row num_rows is never counted.
+static_assert((1 << kBucketMaxRowBits) == FSW_BIN_BLOCK_ROWS, "a bucket of the two-level build is one bin block: it never straddles a row chunk");
+
+__global__ void __launch_bounds__(kBucketWaves * kWave) k_bucket_rows_packed(const uint32_t* __restrict__ words, const int32_t* __restrict__ bstart,
+                                                                             int64_t bstride, int ntable, int64_t num_edges, int64_t num_rows,
+                                                                             int rb, int cb, int32_t* __restrict__ rowptr,
+                                                                             int32_t* __restrict__ col, int stage_cap, int64_t chunk_rows,
+                                                                             int32_t* __restrict__ bin_count, int32_t* __restrict__ stats) {
+  extern __shared__ int bsm[];   // wcnt[kBucketWaves][R] | tot[R] | stage[stage_cap] senders
+  const int R = 1 << rb;
+  int* wcnt = bsm;
+  int* tot = bsm + kBucketWaves * R;
+  uint32_t* stage = reinterpret_cast<uint32_t*>(bsm + (kBucketWaves + 1) * R);
+  __shared__ int wsum[kBucketWaves];
+  __shared__ int lbin[FSW_NUM_BINS];
+  __shared__ int lmax;
+  const int b = blockIdx.x, lane = lane_id(), wv = threadIdx.x >> 6;
+  const int64_t s = bstart[(int64_t)b * bstride];
+  const int64_t e = b + 1 < ntable ? (int64_t)bstart[(int64_t)(b + 1) * bstride] : num_edges;
+  for (int i = threadIdx.x; i < kBucketWaves * R; i += blockDim.x) wcnt[i] = 0;
+  if (threadIdx.x < FSW_NUM_BINS) lbin[threadIdx.x] = 0;
+  if (threadIdx.x == 0) lmax = 0;
+  __syncthreads();
+  // the wave's contiguous part of the bucket, a whole number of 64-edge rounds
+  const int64_t L = ceil_div(e - s, (int64_t)kBucketWaves * kWave) * kWave;
+  const int64_t w0 = min(s + wv * L, e), w1 = min(w0 + L, e);
+  int* mine = wcnt + wv * R;
+  const bool staged = e - s <= stage_cap;   // as in k_bucket_rows: a bucket that fits the staging tile leaves as whole lines
+  {  // kBucketAhead loads in flight (the next group's issued before this group's LDS atomics)
+    uint32_t kn[kBucketAhead];
+#pragma unroll
+    for (int u = 0; u < kBucketAhead; ++u) kn[u] = w0 + lane + u * kWave < w1 ? words[w0 + lane + u * kWave] : 0u;
+    for (int64_t i = w0 + lane; i < w1; i += kBucketAhead * kWave) {
+      uint32_t kk[kBucketAhead];
+#pragma unroll
+      for (int u = 0; u < kBucketAhead; ++u) kk[u] = kn[u];
+      const int64_t nx = i + kBucketAhead * kWave;
+      if (nx - lane < w1) {
+#pragma unroll
+        for (int u = 0; u < kBucketAhead; ++u) kn[u] = nx + u * kWave < w1 ? words[nx + u * kWave] : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < kBucketAhead; ++u)
+        if (i + u * kWave < w1) atomicAdd(&mine[edge_row(kk[u], cb)], 1);
+    }
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    int acc = 0;
+#pragma unroll
+    for (int q = 0; q < kBucketWaves; ++q) {
+      const int c = wcnt[q * R + r];
+      wcnt[q * R + r] = acc;
+      acc += c;
+    }
+    tot[r] = acc;
+  }
+  __syncthreads();
+  {  // exclusive scan of tot[0..R) in place: thread t owns R / blockDim.x consecutive rows; v[j] is the degree of row b * R + r0 + j
+    constexpr int kPerMax = (1 << kBucketMaxRowBits) / (kBucketWaves * kWave);
+    const int per = max(R / (int)blockDim.x, 1);
+    const int r0 = threadIdx.x * per;
+    int v[kPerMax], sum = 0, mx = 0;
+#pragma unroll
+    for (int j = 0; j < kPerMax; ++j) {
+      v[j] = (j < per && r0 + j < R) ? tot[r0 + j] : 0;
+      sum += v[j];
+      // rows below num_rows only: the sentinel row's run (invalid edges) is no degree
+      const bool valid = j < per && r0 + j < R && (int64_t)b * R + r0 + j < num_rows;
+      const int bin = degree_bin(valid ? v[j] : 0);
+      if (valid) mx = max(mx, v[j]);
+      const unsigned long long peers = match_bin(bin, valid);
+      if (valid && lane == __ffsll((long long)peers) - 1) atomicAdd(&lbin[bin], __popcll(peers));   // one LDS atomic per bin and wave
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off));
+    if (lane == 0 && mx) atomicMax(&lmax, mx);
+    const int inc = wave_inclusive_scan(sum);
+    if (lane == kWave - 1) wsum[wv] = inc;
+    __syncthreads();
+    int base = 0;
+#pragma unroll
+    for (int q = 0; q < kBucketWaves; ++q)
+      if (q < wv) base += wsum[q];
+    int ex = base + inc - sum;
+#pragma unroll
+    for (int j = 0; j < kPerMax; ++j)
+      if (j < per && r0 + j < R) {
+        tot[r0 + j] = ex;
+        const int64_t row = (int64_t)b * R + r0 + j;
+        if (row <= num_rows) rowptr[row] = (int32_t)(s + ex);   // row == num_rows: the run of invalid edges (sentinel key) = nnz
+        ex += v[j];
+      }
+    // the barrier above also ordered the LDS atomics on lbin / lmax.  A bucket without a row below num_rows (the sentinel row alone)
+    // has empty bins and touches no counter -- its chunk index may lie behind the last chunk.
+    const int64_t chunk = ((int64_t)b * R) / chunk_rows;
+    if (threadIdx.x < FSW_NUM_BINS && lbin[threadIdx.x]) atomicAdd(&bin_count[chunk * FSW_NUM_BINS + threadIdx.x], lbin[threadIdx.x]);
+    if (threadIdx.x == 0 && lmax) atomicMax(&stats[FSW_STAT_MAX_DEGREE], lmax);
+  }
+  __syncthreads();
+  // the next group's loads are issued before the current group is ranked
+  uint32_t wordn[kBucketAhead];
+  auto load_group = [&](int64_t g) {
+#pragma unroll
+    for (int u = 0; u < kBucketAhead; ++u) {
+      const int64_t i = g + u * kWave + lane;
+      wordn[u] = i < w1 ? words[i] : 0u;
+    }
+  };
+  load_group(w0);
+  const int64_t rows_here = num_rows - (int64_t)b * R;   // rows of this bucket below num_rows (<= 0: none, > R: all)
+  for (int64_t g0 = w0; g0 < w1; g0 += kBucketAhead * kWave) {
+    uint32_t wordv[kBucketAhead];
+#pragma unroll
+    for (int u = 0; u < kBucketAhead; ++u) wordv[u] = wordn[u];
+    if (g0 + kBucketAhead * kWave < w1) load_group(g0 + kBucketAhead * kWave);
+#pragma unroll
+    for (int u = 0; u < kBucketAhead; ++u) {
+      if (g0 + u * kWave >= w1) break;                       // wave-uniform
+      const bool ok = g0 + u * kWave + lane < w1;
+      const uint32_t k = edge_row(wordv[u], cb);
+      const unsigned long long peers = match_digit<kBucketMaxRowBits>(k, ok);
+      const int leader = __ffsll((long long)peers) - 1;
+      const int below = __popcll(peers & ((1ull << lane) - 1ull));
+      int prev = 0;
+      if (ok && lane == leader) {
+        prev = mine[k];
+        mine[k] = prev + __popcll(peers);
+      }
+      prev = __shfl(prev, leader);
+      if (ok && (int64_t)k < rows_here) {
+        const int lpos = tot[k] + prev + below;
+        const uint32_t sender = edge_sender(wordv[u], cb);
+        if (staged)
+          stage[lpos] = sender;
+        else
+          col[s + lpos] = (int32_t)sender;
+      }
+    }
+  }
+  if (staged) {
+    __syncthreads();
+    // valid entries of the bucket: everything below the run of the sentinel row (invalid edges), if that row lives here
+    const int nvalid = (rows_here >= 0 && rows_here < R) ? tot[rows_here] : (int)(e - s);
+    for (int i = threadIdx.x; i < nvalid; i += blockDim.x) col[s + i] = (int32_t)stage[i];
+  }
+}
+
 // first index of every bucket in the sorted keys (buckets = key >> rb): the multi-pass case of the two-level build
 __global__ void __launch_bounds__(256) k_bucket_starts(const uint32_t* __restrict__ keys, int64_t num_edges, int rb, int64_t nbuckets,
                                                        int32_t* __restrict__ bstart) {
@@ -789,28 +1186,23 @@ __global__ void __launch_bounds__(256) k_bucket_starts(const uint32_t* __restric
   }
 }
 
-// shapes the two-level build is meant for: enough rows for a partition pass, buckets that one workgroup finishes quickly
-static bool two_level_ok(int64_t num_rows, int64_t num_edges) {
-  if (num_rows < (1 << 15) || num_edges < (1 << 18)) return false;
-  const int64_t nbuckets = ceil_div(num_rows + 1, (int64_t)1 << kBucketMaxRowBits);
-  return num_edges / nbuckets <= (1 << 16);
-}
-
+// two_level_ok (graph_ws.h) and two_level_plan (graph_plan.h) decide what the build does with a shape, for the build and for fsw_graph_build_plan.
+static_assert(kPartitionBits == 9, "graph_ws.h: the literal handed to radix_sort_pairs below");
 template <class VAL>
 static int sort_and_finish_two_level(const int64_t* recipients, const int64_t* senders, const float* edge_w, int64_t num_edges,
                                      int64_t num_rows, int64_t num_cols, int32_t* rowptr, int32_t* col, float* w, int32_t* stats,
-                                     GraphWs& g, hipStream_t stream) {
-  const int rb = std::min(kBucketMaxRowBits, key_bits(num_rows));
-  const int64_t nbuckets = ceil_div(num_rows + 1, (int64_t)1 << rb);
+                                     GraphWs& g, hipStream_t stream, const TwoLevelPlan& p) {
+  const int rb = p.rb;
+  const int64_t nbuckets = p.nbuckets;
   const int64_t ntiles = ceil_div(num_edges, kRsTile);
   int cur = 0, bits = 0;
-  const int upper = key_bits(num_rows) - rb;
   int rc = radix_sort_pairs<VAL, false>(recipients, senders, edge_w, false, num_edges, num_rows, num_cols, stats, g, &cur, stream, rb, 9, &bits);
   if (rc) return rc;
+  FSW_REQUIRE(bits == p.bits, "fsw_graph_build_two_level: the partition ran passes of %d bits, the plan says %d", bits, p.bits);
   const int32_t* bstart = g.counts;     // single pass: the scanned [digit][tile] table, digit = bucket
   int64_t bstride = ntiles;
   int ntable = 1 << bits;
-  if (bits != upper) {                  // several passes: bucket boundaries from the sorted keys
+  if (bits != p.upper) {                // several passes: bucket boundaries from the sorted keys
     const int blocks = (int)std::min<int64_t>(ceil_div(num_edges + 1, 256), 256 * 32);
     k_bucket_starts<<<blocks, 256, 0, stream>>>(g.keys[cur], num_edges, rb, nbuckets, g.block_sums_big);
     FSW_LAUNCH_CHECK();
@@ -818,18 +1210,44 @@ static int sort_and_finish_two_level(const int64_t* recipients, const int64_t* s
     bstride = 1;
     ntable = (int)nbuckets + 1;
   }
-  // LDS: the tables, and -- when the average bucket (+ 3 %) fits what is left of 160 KB -- a staging tile for the bucket's values
-  // (one workgroup per CU then); without it two workgroups share a CU
-  const size_t tables = sizeof(int) * (size_t)(kBucketWaves + 1) * ((size_t)1 << rb);
-  const size_t room = (size_t)160 * 1024 - 1024 - tables;                      // 1 KB for the static arrays
-  const int64_t avg = ceil_div(num_edges, nbuckets);
-  const int64_t want = avg + avg / 32 + 256;   // random graphs: max bucket ~ avg + 4 sqrt(avg); a larger bucket scatters
-  const int stage_cap = (want * (int64_t)sizeof(VAL) <= (int64_t)room) ? (int)(room / sizeof(VAL)) : 0;
-  const size_t lds = tables + (size_t)stage_cap * sizeof(VAL);
   FSW_SET_MAX_LDS_ONCE((&k_bucket_rows<VAL>), 160 * 1024 - 1024);
-  k_bucket_rows<VAL><<<(unsigned)nbuckets, kBucketWaves * kWave, lds, stream>>>(g.keys[cur], reinterpret_cast<const VAL*>(g.vals[cur]), bstart,
-                                                                              bstride, ntable, num_edges, num_rows, rb, rowptr, col, w,
-                                                                              stage_cap);
+  k_bucket_rows<VAL><<<(unsigned)nbuckets, kBucketWaves * kWave, p.lds, stream>>>(g.keys[cur], reinterpret_cast<const VAL*>(g.vals[cur]), bstart,
+                                                                                bstride, ntable, num_edges, num_rows, rb, rowptr, col, w,
+                                                                                p.stage_cap);
+  FSW_LAUNCH_CHECK();
+  return 0;
+}
+
+// The packed path (graph_plan.h): upsweep, scan and downsweep over tiles of kPackTile edges, one word per edge into keys[1]; the bucket
+// kernel unpacks it and counts the degree bins, so finish_bins skips k_bin_count.
+static int sort_and_finish_packed(const int64_t* recipients, const int64_t* senders, int64_t num_edges, int64_t num_rows, int64_t num_cols,
+                                  int64_t chunk_rows, int32_t* rowptr, int32_t* col, int32_t* stats, GraphWs& g, hipStream_t stream,
+                                  const TwoLevelPlan& p) {
+  const int ndigits = 1 << p.bits;
+  FSW_REQUIRE(p.packed && ndigits <= kRsMaxDigits && (int64_t)ndigits * p.ntiles <= (int64_t)kRsMaxDigits * ceil_div(num_edges, kRsTile),
+              "fsw_graph_build_two_level: the packed count table does not fit the workspace");
+  uint32_t* words = g.keys[1];
+  if (((reinterpret_cast<uintptr_t>(recipients) | reinterpret_cast<uintptr_t>(senders)) & 15) == 0)
+    k_pack_upsweep<true><<<(unsigned)p.ntiles, kRsThreads, 0, stream>>>(recipients, senders, num_edges, num_rows, num_cols, p.rb, ndigits,
+                                                                       g.counts, p.ntiles, stats);
+  else
+    k_pack_upsweep<false><<<(unsigned)p.ntiles, kRsThreads, 0, stream>>>(recipients, senders, num_edges, num_rows, num_cols, p.rb, ndigits,
+                                                                        g.counts, p.ntiles, stats);
+  FSW_LAUNCH_CHECK();
+  if ((int64_t)ndigits * p.ntiles <= kScanTile) {
+    k_scan_one<<<1, kScanThreads, 0, stream>>>(g.counts, (int64_t)ndigits * p.ntiles);
+    FSW_LAUNCH_CHECK();
+  } else if (int rc = exclusive_scan_i32(g.counts, (int64_t)ndigits * p.ntiles, g.block_sums, g.block_sums_cap, stream)) {
+    return rc;
+  }
+  FSW_SET_MAX_LDS_ONCE((&k_pack_downsweep), kPackLdsBytes);
+  k_pack_downsweep<<<(unsigned)p.ntiles, kRsThreads, kPackLdsBytes, stream>>>(recipients, senders, num_edges, num_rows, num_cols, p.rb, p.cb,
+                                                                             p.bits, g.counts, p.ntiles, words);
+  FSW_LAUNCH_CHECK();
+  FSW_SET_MAX_LDS_ONCE((&k_bucket_rows_packed), 160 * 1024 - 1024);
+  k_bucket_rows_packed<<<(unsigned)p.nbuckets, kBucketWaves * kWave, p.lds, stream>>>(words, g.counts, p.ntiles, ndigits, num_edges, num_rows,
+                                                                                     p.rb, p.cb, rowptr, col, p.stage_cap,
+                                                                                     one_chunk_if_zero(num_rows, chunk_rows), g.bin_count, stats);
   FSW_LAUNCH_CHECK();
   return 0;
 }
@@ -880,18 +1298,31 @@ static int graph_build_impl(const int64_t* recipients, const int64_t* senders, c
 
   FSW_CHECK_HIP(hipMemsetAsync(g.bin_count, 0, kBinTableBytes, stream));
   FSW_CHECK_HIP(hipMemsetAsync(stats, 0, sizeof(int32_t) * FSW_NUM_STATS, stream));
+  const bool try_two = two_level && num_edges > 0 && two_level_ok(num_rows, num_edges);
+  const TwoLevelPlan p = try_two ? two_level_plan(num_rows, num_cols, num_edges, edge_w != nullptr) : TwoLevelPlan{};
+  const bool counted = try_two && p.packed;   // the degree bins are counted by the bucket kernel
   if (num_edges == 0) {
     FSW_CHECK_HIP(hipMemsetAsync(rowptr, 0, sizeof(int32_t) * (size_t)(num_rows + 1), stream));
-  } else if (two_level && two_level_ok(num_rows, num_edges)) {
-    int rc = edge_w ? sort_and_finish_two_level<unsigned long long>(recipients, senders, edge_w, num_edges, num_rows, num_cols, rowptr, col, w, stats, g, stream)
-                    : sort_and_finish_two_level<uint32_t>(recipients, senders, edge_w, num_edges, num_rows, num_cols, rowptr, col, w, stats, g, stream);
+  } else if (try_two) {
+    int rc = p.packed ? sort_and_finish_packed(recipients, senders, num_edges, num_rows, num_cols, chunk_rows, rowptr, col, stats, g, stream, p)
+             : edge_w ? sort_and_finish_two_level<unsigned long long>(recipients, senders, edge_w, num_edges, num_rows, num_cols, rowptr, col, w, stats, g, stream, p)
+                      : sort_and_finish_two_level<uint32_t>(recipients, senders, edge_w, num_edges, num_rows, num_cols, rowptr, col, w, stats, g, stream, p);
     if (rc) return rc;
   } else {
     int rc = edge_w ? sort_and_finish<unsigned long long>(recipients, senders, edge_w, num_edges, num_rows, num_cols, rowptr, col, w, stats, g, stream)
                     : sort_and_finish<uint32_t>(recipients, senders, edge_w, num_edges, num_rows, num_cols, rowptr, col, w, stats, g, stream);
     if (rc) return rc;
   }
-  return finish_bins(rowptr, num_rows, chunk_rows, perm, invperm, bin_start, stats, g, stream);
+  return finish_bins(rowptr, num_rows, chunk_rows, perm, invperm, bin_start, stats, g, stream, counted);
+}
+
+// Host only: what fsw_graph_build_two_level does with a shape (GraphPlanWord of graph_plan.h), from the functions the build itself calls.
+extern "C" int fsw_graph_build_plan(int64_t num_rows, int64_t num_cols, int64_t num_edges, int weighted, int32_t* out) {
+  FSW_REQUIRE(out && num_rows >= 1 && num_rows < (1ll << 31) - 1 && num_cols >= 1 && num_cols < (1ll << 31) && num_edges >= 0 &&
+                  num_edges < (1ll << 31) - kRsTile,
+              "fsw_graph_build_plan: null pointer or sizes outside 1 <= rows, cols < 2^31, 0 <= edges < 2^31");
+  graph_plan_words(num_rows, num_cols, num_edges, weighted != 0, out);
+  return 0;
 }
 
 extern "C" int fsw_graph_build(const int64_t* recipients, const int64_t* senders, const float* edge_w, int64_t num_edges,

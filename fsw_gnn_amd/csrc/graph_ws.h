@@ -99,4 +99,25 @@ inline GraphWs carve(void* ws, int64_t num_edges, int64_t num_rows = 0) {
   return g;
 }
 
+// ---- constants of the two-level build that decide which path a shape takes (graph_plan.h: two_level_plan) ----
+constexpr int kBucketWaves = 8;
+#ifndef FSW_BUCKET_ROW_BITS
+#define FSW_BUCKET_ROW_BITS 11
+#endif
+constexpr int kBucketMaxRowBits = FSW_BUCKET_ROW_BITS;   // LDS: (kBucketWaves + 1) * 2^bits ints (72 KB at 11, 144 KB at 12)
+constexpr int kPartitionBits = 9;                        // bits of a partition pass
+
+// shapes the two-level build is meant for: enough rows for a partition pass, buckets that one workgroup finishes quickly
+static bool two_level_ok(int64_t num_rows, int64_t num_edges) {
+  if (num_rows < (1 << 15) || num_edges < (1 << 18)) return false;
+  const int64_t nbuckets = (num_rows + 1 + ((int64_t)1 << kBucketMaxRowBits) - 1) >> kBucketMaxRowBits;
+  return num_edges / nbuckets <= (1 << 16);
+}
+
+// LDS of the bucket kernel that is left for a staging tile beside its tables
+inline size_t bucket_stage_room(size_t tables) {
+  const size_t room = (size_t)160 * 1024 - 1024 - tables;                      // 1 KB for the static arrays
+  return room;
+}
+
 }  // namespace fsw

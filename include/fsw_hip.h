@@ -125,6 +125,13 @@ int fsw_graph_build_two_level(const int64_t* recipients, const int64_t* senders,
                     int64_t num_edges, int64_t num_rows, int64_t num_cols, int64_t chunk_rows,
                     int32_t* rowptr, int32_t* col, float* w, int32_t* perm, int32_t* invperm, int32_t* bin_start,
                     int32_t* stats, void* workspace, size_t workspace_bytes, fsw_stream_t stream);
+/* Host only (no device call): what fsw_graph_build_two_level does with a shape, computed by the code the build runs.
+ * out int32[FSW_GRAPH_PLAN_WORDS]: [0] 1 = partition pass + bucket kernel, 0 = the LSD passes (all other words are then 0);
+ * [1] 1 = one packed uint32 per edge (unit weights, one partition pass, row bits of a bucket + sender bits <= 32);
+ * [2] edges per tile of the partition pass; [3] entries of the bucket kernel's LDS staging tile (0: none);
+ * [4] partition passes; [5] row bits of a bucket; [6] sender bits; [7] buckets.                                          */
+#define FSW_GRAPH_PLAN_WORDS 8
+int fsw_graph_build_plan(int64_t num_rows, int64_t num_cols, int64_t num_edges, int weighted, int32_t* out);
 
 /* Coalescing variant: entries sorted by (recipient, sender), parallel edges merged into ONE entry whose
  * weight (edge_w or 1 per edge) and edge-feature vector are the sums over the duplicates -- exactly what
