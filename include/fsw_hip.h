@@ -152,6 +152,9 @@ int fsw_graph_build_coalesced(const int64_t* recipients, const int64_t* senders,
  * fp32 MFMA (v_mfma_f32_32x32x2_f32), which FSW_PROJECT_EXACT_FP32=1 in the environment selects instead (d <= 128).
  * Replaces torch.tensordot(X, projVecs) (reference fsw_embedding.py:909-913).  Sets
  * FSW_FLAG_X_NONFINITE in stats[FSW_STAT_FLAGS] if X holds a NaN/Inf (stats may be NULL).
+ * The bf16 kernels (d % 4 == 0, d <= 256, 16-byte aligned rows of X, V and W2) need ldp >= 32 * ceil(S / 32), ldp % 4 == 0 and a
+ * 16-byte aligned Xp, and store whole 32-column slabs: columns S .. 32 * ceil(S / 32) - 1 of a row receive 0.0; columns from there on, and
+ * from S on in the generic kernel, are left untouched (tests/test_hip_conv_fused.py).
  * x_copy (nullable): the kernel also stores the X rows it stages to x_copy[i*ld_copy + c] -- this is
  * the right half of FSW_conv's torch.cat((emb, vertex_features)) (reference fsw_conv.py:357-358),
  * written while X is on chip anyway instead of by a separate copy kernel.                          */
