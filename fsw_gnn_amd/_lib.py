@@ -21,6 +21,7 @@ HUB_MAX_DEG = 32768
 CART_SPLIT_LINES = 1          # FSW_CART_SPLIT_LINES: fsw_cart_args.flags, the split form of the longest unit-weight rows (fsw_embed_cart_f32)
 CART_SPLIT_BWD_LINES = 2      # FSW_CART_SPLIT_BWD_LINES: the split form of those rows' backward (fsw_embed_cart_backward_keys_f32)
 CART_SPLIT_W_LINES = 4        # FSW_CART_SPLIT_W_LINES: the split form of the longest general-weight rows (fsw_embed_cart_f32)
+CART_SPLIT_W_BWD_LINES = 8    # FSW_CART_SPLIT_W_BWD_LINES: the split form of those rows' backward (fsw_embed_cart_backward_keys_f32)
 CART_W_MAX_LINE = 16384       # FSW_CART_W_MAX_LINE: Cartesian mode, general weights, longest line (D + 1) of the tuned classes
 BIN_MID0 = REG_MAX_DEG + 1      # first bin above the register path (include/fsw_hip.h: FSW_BIN_MID0)
 NUM_BINS = REG_MAX_DEG + 1 + len(MID_SIZES) + NUM_LDS_BINS + NUM_HUB_BINS + 1
@@ -119,6 +120,9 @@ _SIGNATURES = {
     "fsw_embed_cart_split_w_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs)]),
     "fsw_embed_cart_split_w_lines": (c_i64, [ctypes.POINTER(CartArgs)]),
     "fsw_embed_cart_split_w_max_lines": (c_i64, []),
+    "fsw_embed_cart_split_w_backward_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs)]),
+    "fsw_embed_cart_split_w_backward_lines": (c_i64, [ctypes.POINTER(CartArgs)]),
+    "fsw_embed_cart_split_w_backward_max_lines": (c_i64, []),
     "fsw_embed_cart_backward_keys_scratch_bytes": (c_sz, [ctypes.POINTER(CartArgs)]),
     "fsw_embed_cart_backward_scratch_bytes": (c_sz, [c_i64, c_i64, c_i32]),
     "fsw_embed_cart_weighted_backward_scratch_bytes": (c_sz, [c_i64, c_i64, c_i32]),

@@ -1,5 +1,5 @@
 // What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_split_cart.hip, embed_giant_cart_w.hip, embed_split_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
-// embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip, embed_giant_cart_bwd.hip, embed_split_cart_bwd.hip) of Cartesian mode share: the degree classes, the
+// embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip, embed_giant_cart_bwd.hip, embed_split_cart_bwd.hip, embed_split_cart_w_bwd.hip) of Cartesian mode share: the degree classes, the
 // constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
 #pragma once
 #include <algorithm>
@@ -342,5 +342,48 @@ inline CartSplitBwdPlan cart_split_bwd_plan(const fsw_cart_args* c) {
 }
 // embed_split_cart_bwd.hip: the giant class of kCartLong[0] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)
 int launch_cart_split_bwd(const fsw_cart_args* c, const CartSplitBwdPlan& p, hipStream_t stream);
+
+// ---- split form of the giant class's backward, general weights (embed_split_cart_w_bwd.hip; args->flags & FSW_CART_SPLIT_W_BWD_LINES):
+// every phase of k_cart_giant_bwd<true> is a launch of its own over (line, piece).  Every line owns two regions (ping and pong) of `words`
+// packed words: the line of max_degree + 1 elements rounded up to whole runs; behind the regions follow the float64 mass pieces of the
+// rows [rows][tiles], the float64 sums of the weights of every walk tile [lines][tiles] and the per-tile partial sums of the frequency
+// gradients [lines][tiles][F], every part 16-byte aligned ------------------------------------------------------------------------------
+constexpr int kCartSplitWBwdWalk = 256 * 8;                   // ranks of a tile of the walk: 256 threads x kGbVT[1] of k_cart_giant_bwd = one run
+constexpr int64_t kCartSplitWBwdMaxLines = 256;               // fsw_embed_cart_split_w_backward_max_lines: the largest measured line count at which the split form won
+static_assert(kCartSplitWBwdWalk == kCartMaxLine, "a walk tile is one run: the mass pieces, the tile sums and the partial sums share `tiles`");
+struct CartSplitWBwdPlan {
+  int64_t lines;                                              // rows from the giant class's first bin on x S; 0: no split form for this call
+  int64_t rows;                                               // lines / S
+  int64_t words;                                              // words of each of a line's two regions: (max_degree + 1) in whole runs
+  int tiles;                                                  // runs = walk tiles of the longest line
+  size_t mass_offset, tsum_offset, partial_offset;            // bytes: where the mass pieces, the tile sums and the partial sums begin
+  size_t bytes;                                               // fsw_embed_cart_split_w_backward_scratch_bytes: the rows of the classes below included
+};
+// host values only (bin_start_host, max_degree, w, tau, S, F).  No split form: unit weights with tau <= 1, no row of the class, or above 2 GiB
+inline CartSplitWBwdPlan cart_split_w_bwd_plan(const fsw_cart_args* c) {
+  CartSplitWBwdPlan p = {};
+  if (!c || !c->bin_start_host || cart_unit_fast(c) || c->S < 1 || c->F < 1) return p;
+  const CartLongMode& m = kCartLong[1];
+  const int64_t rows = cart_giant_rows(c, m);
+  if (rows <= 0) return p;
+  const size_t cap = (size_t)2 << 30;                          // as fsw_embed_cart_backward_keys_scratch_bytes
+  const size_t line_bytes = cart_giant_bwd_line_bytes(m, c->max_degree);
+  const int64_t lines = rows * c->S;
+  if (line_bytes > cap || (size_t)lines > cap / line_bytes) return p;
+  const int64_t words = (int64_t)(line_bytes / kCartGiantBwdElemBytes), tiles = words / kCartSplitWBwdWalk;
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t regions = (size_t)lines * line_bytes;           // a multiple of 16
+  const size_t mass = up16((size_t)rows * (size_t)tiles * sizeof(double));               // lines * tiles <= 2^16
+  const size_t tsum = up16((size_t)lines * (size_t)tiles * sizeof(double));
+  if ((size_t)c->F > cap / ((size_t)lines * (size_t)tiles * sizeof(float))) return p;
+  const size_t partial = up16((size_t)lines * (size_t)tiles * (size_t)c->F * sizeof(float));
+  if (regions + mass + tsum + partial > cap) return p;
+  p.lines = lines; p.rows = rows; p.words = words; p.tiles = (int)tiles;
+  p.mass_offset = regions; p.tsum_offset = regions + mass; p.partial_offset = regions + mass + tsum;
+  p.bytes = std::max(regions + mass + tsum + partial, cart_line_classes_bwd_bytes(c, m));
+  return p;
+}
+// embed_split_cart_w_bwd.hip: the giant class of kCartLong[1] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)
+int launch_cart_split_w_bwd(const fsw_cart_args* c, const CartSplitWBwdPlan& p, hipStream_t stream);
 
 }  // namespace fsw

@@ -19,7 +19,8 @@
 //                    (embed_cart_hub_w.hip: k_cart_hub_w), no scratch.
 //   longer lines     (general weights above 16384 elements, any row above 32768; any length) one workgroup per (row, slice), the line
 //                    in sorted blocks in a scratch line: embed_giant_cart.hip (k_cart_giant: bitonic block sweeps) and
-//                    embed_giant_cart_w.hip (k_cart_mergepath_w: merge path).  Their backward: embed_giant_cart_bwd.hip.
+//                    embed_giant_cart_w.hip (k_cart_mergepath_w: merge path).  Their backward: embed_giant_cart_bwd.hip; its split
+//                    forms: embed_split_cart_bwd.hip (unit weights), embed_split_cart_w_bwd.hip (general weights).
 //                    Unit weights with args->flags & FSW_CART_SPLIT_LINES: embed_split_cart.hip, one line split over many workgroups.
 //                    General weights with args->flags & FSW_CART_SPLIT_W_LINES: embed_split_cart_w.hip, the same.
 // Readout, by summation by parts of the reference's Delta_t = 2 w_t sinc(xi w_t) cos(pi xi (2 c_t - w_t)):

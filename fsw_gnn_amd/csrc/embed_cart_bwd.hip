@@ -21,6 +21,8 @@
 //   longer lines     (general weights above 16384 elements, any row above 32768; any length) one workgroup of four wavefronts per
 //                    (row, slice): the packed words in sorted runs in a scratch line, merge path above a run
 //                    (embed_giant_cart_bwd.hip: k_cart_giant_bwd), 16 bytes of scratch per element of the line and workgroup.
+//                    With args->flags & FSW_CART_SPLIT_BWD_LINES (unit weights: embed_split_cart_bwd.hip) or FSW_CART_SPLIT_W_BWD_LINES
+//                    (general weights: embed_split_cart_w_bwd.hip) one line is split over the workgroups of a launch per phase.
 // No float32 row runs on the generic kernel (k_embed_generic, embed_generic.hip).
 // gfreq: the register class sums a workgroup's partials in LDS, the wavefront class across the wavefront; one float atomic per
 // (workgroup resp. wavefront, frequency).
@@ -404,6 +406,13 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
                 "fsw_embed_cart_backward_keys_f32: FSW_CART_SPLIT_BWD_LINES needs a 16-byte aligned scratch buffer of "
                 "fsw_embed_cart_split_backward_scratch_bytes(args) bytes");
   }
+  // FSW_CART_SPLIT_W_BWD_LINES: the same for general weights (a call has one of the two forms at most: unit weights or not)
+  const CartSplitWBwdPlan split_w = (c->flags & FSW_CART_SPLIT_W_BWD_LINES) ? cart_split_w_bwd_plan(c) : CartSplitWBwdPlan{};
+  if (split_w.lines > 0) {
+    FSW_REQUIRE(c->scratch && ((uintptr_t)c->scratch & 15) == 0 && c->scratch_bytes >= split_w.bytes,
+                "fsw_embed_cart_backward_keys_f32: FSW_CART_SPLIT_W_BWD_LINES needs a 16-byte aligned scratch buffer of "
+                "fsw_embed_cart_split_w_backward_scratch_bytes(args) bytes");
+  }
 
   CartBwd t;
   t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
@@ -439,7 +448,8 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
   // lines above kCartMaxLine elements (the classes of embed_cart.h: kCartLong): one wavefront per line in a scratch line
   if ((rc = unit_fast ? launch_cart_hub_bwd(c, stream) : launch_cart_hub_w_bwd(c, stream))) return rc;
   // the giant class (any length): sorted runs + merge path in the scratch lines of c->scratch, one workgroup per line -- or, unit weights
-  // with FSW_CART_SPLIT_BWD_LINES, every line split over the workgroups of a launch per phase
+  // with FSW_CART_SPLIT_BWD_LINES (general weights: FSW_CART_SPLIT_W_BWD_LINES), every line split over the workgroups of a launch per phase
   if (split.lines > 0) return launch_cart_split_bwd(c, split, stream);
+  if (split_w.lines > 0) return launch_cart_split_w_bwd(c, split_w, stream);
   return launch_cart_giant_bwd(c, stream);
 }

@@ -1,6 +1,7 @@
 // Cartesian slice x frequency mode, the longest rows -- unit weights: above FSW_HUB_MAX_DEG neighbours; general weights (w != NULL or
 // tau > 1): lines of more than FSW_CART_W_MAX_LINE elements; any length --: backward with respect to the keys and the frequencies.
 // gfx950.  The forward: embed_giant_cart.hip, embed_giant_cart_w.hip; the classes below: embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip.
+// One line split over many workgroups, a launch per phase: embed_split_cart_bwd.hip (unit weights), embed_split_cart_w_bwd.hip (general).
 //
 // k_cart_giant_bwd<WEIGHTED>: one workgroup of four wavefronts takes ONE (recipient row, slice) line at a time (the forward's
 // persistent, XCD-aware line loop) in its own scratch line: two lines of packed (key, entry index) words (ping, pong), the line

@@ -31,7 +31,8 @@ sizes (_cart_forward_scratch_bytes, _cart_backward_scratch_bytes).  One policy i
 rows above 32768 neighbours make few (row, slice) lines -- one point cloud, one graph under FSW_readout -- asks for their split form
 (csrc/embed_split_cart.hip: every phase a launch over (line, block), so one line fills the chip), and so does its backward
 (_cart_split_backward, csrc/embed_split_cart_bwd.hip); general weights -- a weight tensor, W = 'uniform', total_mass_pad_thresh > 1 --
-have a split form of the forward of their own (_cart_split_w, csrc/embed_split_cart_w.hip).  It needs a HIP device at construction (this
+have split forms of their own in both directions (forward: _cart_split_w, csrc/embed_split_cart_w.hip; backward:
+_cart_split_w_backward, csrc/embed_split_cart_w_bwd.hip).  It needs a HIP device at construction (this
 package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
 differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
 bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
@@ -507,7 +508,8 @@ class _CartEmbedFn(torch.autograd.Function):
 
     Forward: one projection of all S slices (prepare_cartesian) + fsw_embed_cart_f32; the projection, the stats and the unit table
     stay on ctx.  Backward: fsw_embed_cart_backward_keys_f32 (csrc/embed_cart_bwd.hip, tuned kernels for rows of every length; its
-    scratch, _cart_backward_scratch_bytes or what the split form of the longest unit-weight rows needs (_cart_split_backward), is the
+    scratch, _cart_backward_scratch_bytes or what the split form of the longest rows needs (_cart_split_backward for unit weights,
+    _cart_split_w_backward for general weights), is the
     forward's buffer where that is large enough, else a buffer of its own: _cart_scratch) stores the key gradient of every entry,
     [nnz, S], and accumulates the frequency gradients; the store-and-sum pair (graph.sender_major + fsw_segment_sum_rows_f32) sums
     the entries sender by sender without float atomics, then the two GEMMs of _EmbedGraphFn.  bias: None for 'homog' /
@@ -548,10 +550,10 @@ class _CartEmbedFn(torch.autograd.Function):
                 _lib.check(L.fsw_unit_dcoeff_table(_lib.ptr(fr), F, _lib.REG_MAX_DEG, _lib.ptr(dtable), F, stream), "fsw_unit_dcoeff_table")
             gf = torch.zeros(F, dtype=torch.float32, device=dev)
             gkey = torch.empty((nnz, S), dtype=torch.float32, device=dev)      # every entry is stored
-            split_bytes = module._cart_split_backward(graph, st)
-            scratch = module._cart_scratch(graph, st, backward=True, reuse=prepared["scratch"], split_bytes=split_bytes)
+            split_bytes, split_w_bytes = module._cart_split_backward(graph, st), module._cart_split_w_backward(graph, st)    # one of them is 0
+            scratch = module._cart_scratch(graph, st, backward=True, reuse=prepared["scratch"], split_bytes=split_bytes or split_w_bytes)
             a = module._cart_tuned_args(graph, st, prepared["Xp"], ldp, fr, S, table, scratch, out_scale, has_mass,
-                                        split_backward=split_bytes > 0)
+                                        split_backward=split_bytes > 0, split_w_backward=split_w_bytes > 0)
             a.g, a.ldg, a.gkey, a.ldk, a.gfreq = g.data_ptr(), g.stride(0), gkey.data_ptr(), S, gf.data_ptr()
             _lib.check(L.fsw_embed_cart_backward_keys_f32(ctypes.byref(a), _lib.ptr(dtable), F, stream), "fsw_embed_cart_backward_keys_f32")
             if need[0] or need[1]:
@@ -1053,22 +1055,40 @@ class FSW_embedding(nn.Module):
             return 0
         return int(L.fsw_embed_cart_split_backward_scratch_bytes(ctypes.byref(a)))
 
+    def _cart_split_w_backward(self, graph, st):
+        """The policy of the split form of the longest general-weight rows' backward (csrc/embed_split_cart_w_bwd.hip), decided ONCE per
+        backward: bytes of scratch the split form needs, or 0 for the one-workgroup-per-line kernel -- unit weights, no such row, or more
+        than fsw_embed_cart_split_w_backward_max_lines() lines.  Host values only; mirrors _cart_split_w (unit weights leave before the
+        query)."""
+        if graph.w is None and self.total_mass_pad_thresh <= 1:
+            return 0
+        a = _lib.CartArgs()
+        a.S, a.F, a.tau, a.max_degree = self.nSlices, self.nFreqs, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
+        a.w = graph.w.data_ptr() if graph.w is not None else None
+        a.bin_start_host = graph.bin_start_host[0].ctypes.data
+        L = _lib.lib()
+        lines = int(L.fsw_embed_cart_split_w_backward_lines(ctypes.byref(a)))
+        if not (0 < lines <= int(L.fsw_embed_cart_split_w_backward_max_lines())):
+            return 0
+        return int(L.fsw_embed_cart_split_w_backward_scratch_bytes(ctypes.byref(a)))
+
     def _cart_scratch(self, graph, st, backward=False, reuse=None, split_bytes=0):
         """The scratch buffer of the forward (_cart_forward_scratch_bytes) or of the backward (_cart_backward_scratch_bytes), or of
-        split_bytes (_cart_split / _cart_split_w / _cart_split_backward) if larger; None for 0 bytes; reuse (the forward's buffer) when it is large enough."""
+        split_bytes (_cart_split / _cart_split_w / _cart_split_backward / _cart_split_w_backward) if larger; None for 0 bytes; reuse (the forward's buffer) when it is large enough."""
         nbytes = max(self._cart_backward_scratch_bytes(graph, st) if backward else self._cart_forward_scratch_bytes(graph, st), split_bytes)
         if reuse is not None and reuse.numel() >= nbytes:
             return reuse
         return torch.empty(nbytes, dtype=torch.uint8, device=graph.rowptr.device) if nbytes else None
 
-    def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass, split=False, split_backward=False, split_w=False):
+    def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass, split=False, split_backward=False, split_w=False,
+                         split_w_backward=False):
         """struct fsw_cart_args of the tuned entry points (fsw_embed_cart_f32, fsw_embed_cart_backward_keys_f32) without the
         output / gradient fields.  split: FSW_CART_SPLIT_LINES, for the forward call only (_cart_split); split_w: FSW_CART_SPLIT_W_LINES,
         for the forward call only (_cart_split_w); split_backward: FSW_CART_SPLIT_BWD_LINES, for the backward call only
-        (_cart_split_backward)."""
+        (_cart_split_backward); split_w_backward: FSW_CART_SPLIT_W_BWD_LINES, for the backward call only (_cart_split_w_backward)."""
         a = _cart_args(self, Xp, ldp, fr, S, out_scale, has_mass, self._mass_scale_read(st))
         a.flags = ((_lib.CART_SPLIT_LINES if split else 0) | (_lib.CART_SPLIT_BWD_LINES if split_backward else 0) |
-                   (_lib.CART_SPLIT_W_LINES if split_w else 0))
+                   (_lib.CART_SPLIT_W_LINES if split_w else 0) | (_lib.CART_SPLIT_W_BWD_LINES if split_w_backward else 0))
         a.rowptr, a.col = graph.rowptr.data_ptr(), graph.col.data_ptr()
         a.w = graph.w.data_ptr() if graph.w is not None else None
         a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), graph.bin_start_host[0].ctypes.data

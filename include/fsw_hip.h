@@ -417,7 +417,7 @@ typedef struct {
   const void* bias;      /* NULL or [has_mass + S F] */
   double out_scale;
   int32_t mass_fn;
-  int32_t flags;         /* 0, or bits: FSW_CART_SPLIT_LINES, FSW_CART_SPLIT_W_LINES (fsw_embed_cart_f32 only), FSW_CART_SPLIT_BWD_LINES (fsw_embed_cart_backward_keys_f32 only) */
+  int32_t flags;         /* 0, or bits: FSW_CART_SPLIT_LINES, FSW_CART_SPLIT_W_LINES (fsw_embed_cart_f32 only), FSW_CART_SPLIT_BWD_LINES, FSW_CART_SPLIT_W_BWD_LINES (fsw_embed_cart_backward_keys_f32 only) */
   double mass_scale;
   const void* g;
   int64_t ldg;
@@ -530,6 +530,38 @@ int64_t fsw_embed_cart_split_backward_max_lines(void);
 size_t fsw_embed_cart_split_w_scratch_bytes(const fsw_cart_args* args);
 int64_t fsw_embed_cart_split_w_lines(const fsw_cart_args* args);
 int64_t fsw_embed_cart_split_w_max_lines(void);
+/* Split form of the longest GENERAL-WEIGHT rows' BACKWARD (csrc/embed_split_cart_w_bwd.hip): args->flags & FSW_CART_SPLIT_W_BWD_LINES asks
+ * fsw_embed_cart_backward_keys_f32 to run the rows of FSW_CART_W_MAX_LINE neighbours and more (w != NULL or tau > 1: lines of max_degree + 1
+ * elements with the pad element) with every phase -- the rows' masses, sorting runs of FSW_LDS_MAX_DEG packed (key, entry index) words, every
+ * merge level, the sums of the weights of the tiles of 2048 ranks, the walk over the sorted line tile by tile, the sum of the frequency
+ * gradients -- as a launch of its own over (line, piece).  Consecutive launches in the caller's stream are the only synchronisation.  All
+ * other rows run as without the flag (the shorter rows that share the class's first degree bin included).  gkey of these rows depends on
+ * the line only (not on S, the other rows or the scratch's content).  It is NOT bit-identical to the call without the flag: the row mass
+ * and the cumulative weights are added in another float64 order; both are within the library's bound of the float64 value.  gfreq differs
+ * by the order of summation.
+ *   fsw_embed_cart_split_w_backward_scratch_bytes  host values only (bin_start_host, max_degree, w, tau, S, F).  With the flag set,
+ *       args->scratch must be 16-byte aligned and hold at least this many bytes, else the call is refused before any launch:
+ *         rows = rows from the first degree bin of that class on,   lines = rows x S,
+ *         words = max_degree + 1 rounded up to whole runs of 2048,   tiles = words / 2048,
+ *         bytes = lines * words * 16        (every line owns two regions, ping and pong, of 8-byte words)
+ *               + rows * tiles * 8          (the float64 partial sums of the rows' masses, one per run)
+ *               + lines * tiles * 8         (the float64 sum of the weights of every walk tile)
+ *               + lines * tiles * F * 4     (one partial sum per line, walk tile and frequency),
+ *       every part rounded up to a multiple of 16, so that each starts 16-byte aligned,
+ *       or, where that is larger, what part 1 of fsw_embed_cart_backward_keys_scratch_bytes says for the lines of FSW_LDS_MAX_DEG + 1 ..
+ *       FSW_CART_W_MAX_LINE elements, which run their kernels out of the same buffer.
+ *       0 when there is nothing to split -- w == NULL and tau <= 1, no row in that bin, max_degree < FSW_CART_W_MAX_LINE, args == NULL --
+ *       or when the four parts would exceed 2 GiB.  Where it is 0 the flag is ignored: the call is then bit-identical to the same flags
+ *       without it (scratch rules above).
+ *   fsw_embed_cart_split_w_backward_lines          the lines the split form takes for args (rows x S), 0 where the size query is 0.
+ *   fsw_embed_cart_split_w_backward_max_lines      the largest line count for which the host layer (fsw_gnn_amd/fsw_embedding.py) sets
+ *       the flag: the largest measured count at which the split form won.  At least 16.  The library does what the flag says.
+ * fsw_embed_cart_f32, fsw_embed_cart_generic, fsw_conv_fused_cart_f32 and every scratch query above ignore this flag;
+ * FSW_CART_SPLIT_BWD_LINES keeps meaning unit weights only: fsw_embed_cart_split_backward_* return 0 for general weights. */
+#define FSW_CART_SPLIT_W_BWD_LINES 8
+size_t fsw_embed_cart_split_w_backward_scratch_bytes(const fsw_cart_args* args);
+int64_t fsw_embed_cart_split_w_backward_lines(const fsw_cart_args* args);
+int64_t fsw_embed_cart_split_w_backward_max_lines(void);
 /* Scratch of fsw_embed_cart_backward_keys_f32 for the graph and weight mode of args, of which it reads bin_start_host, max_degree, w
  * (NULL or not), tau and S: host values only.  The maximum of two parts, 0 when neither applies:
  *   1. the rows of FSW_LDS_MAX_DEG + 1 .. FSW_HUB_MAX_DEG neighbours (general weights: lines of FSW_LDS_MAX_DEG + 1 ..

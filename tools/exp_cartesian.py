@@ -61,9 +61,15 @@ threshold is the host layer's, the library does what the flag says); c150000x2 a
 The backward of such a workload takes its own split form (csrc/embed_split_cart_bwd.hip) up to fsw_embed_cart_split_backward_max_lines()
 lines; every line of the output names that form too, --form-bwd split | giant forces one, and a build without
 fsw_embed_cart_split_backward_scratch_bytes has the one-workgroup-per-line backward only.
+--giant --weights uniform | random: 1, 2, 4, 8, 16 and 32 clouds of 150 000 points (16 .. 512 lines at S = 16) and one cloud of 1 000 000
+with a weight per point -- 1 / size of the cloud, or random in (0.05, 1) --: the forward takes the split form of general weights
+(csrc/embed_split_cart_w.hip), the backward its own (csrc/embed_split_cart_w_bwd.hip) up to
+fsw_embed_cart_split_w_backward_max_lines() lines; --form and --form-bwd force one form here too, and a build without
+fsw_embed_cart_split_w_backward_scratch_bytes has the one-workgroup-per-line backward only.
     python tools/exp_cartesian.py --giant [--workload w24000,u40000,mixed,c150000,c150000x2,c150000x4,c1000000] --steps 3 --warmup 1
     python tools/exp_cartesian.py --giant --workload u40000,c150000,c150000x2,c150000x4 --form split     (and --form giant)
     python tools/exp_cartesian.py --giant --workload u40000,c150000x2,c150000x4 --form-bwd split         (and --form-bwd giant)
+    python tools/exp_cartesian.py --giant --weights uniform [--workload c150000,c150000x16,c1000000] --form-bwd split   (and giant)
     FSW_HIP_LIBRARY=_variants/libfsw_hip_parent.so python tools/exp_cartesian.py --giant --steps 3 --warmup 1
     rocprofv3 --kernel-trace --stats -d DIR -o giant -- python tools/exp_cartesian.py --giant --workload c150000 --steps 1
 --giant --workload splitw: the split form of the longest general-weight rows (csrc/embed_split_cart_w.hip) against the one-workgroup-per-
@@ -106,7 +112,7 @@ ap.add_argument("--weights", choices=("unit", "uniform", "random"), default="uni
 ap.add_argument("--form", choices=("auto", "split", "giant"), default="auto",
                 help="--giant: the form of the longest unit-weight rows' forward: the host layer's choice, or one form for every line count")
 ap.add_argument("--form-bwd", choices=("auto", "split", "giant"), default="auto",
-                help="--giant: the form of the longest unit-weight rows' backward: the host layer's choice, or one form for every line count")
+                help="--giant: the form of the longest rows' backward (unit and general weights): the host layer's choice, or one form for every line count")
 ap.add_argument("--tau", type=float, default=1.0, help="--hub: total_mass_pad_thresh of the embedding (> 1: general-weight kernels with w = NULL)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -400,12 +406,22 @@ def giant_leg():
     elif args.form_bwd != "auto":
         top_bwd = (1 << 62) if args.form_bwd == "split" else 0
         _lib.lib().fsw_embed_cart_split_backward_max_lines = lambda: top_bwd
-    print("library %s: forward: %s; backward: %s; split form: %s; split backward: %s" % (
+    has_split_w_bwd = library_exports("fsw_embed_cart_split_w_backward_scratch_bytes")
+    if not has_split_w_bwd:  # general weights: one workgroup per line only in the backward
+        for symbol in ("fsw_embed_cart_split_w_backward_lines", "fsw_embed_cart_split_w_backward_max_lines"):
+            del _lib._SIGNATURES[symbol]
+        drive_without("fsw_embed_cart_split_w_backward_scratch_bytes", "_cart_split_w_backward", lambda self, graph, st: 0)
+    elif args.form_bwd != "auto":
+        top_w_bwd = (1 << 62) if args.form_bwd == "split" else 0
+        _lib.lib().fsw_embed_cart_split_w_backward_max_lines = lambda: top_w_bwd
+    print("library %s: forward: %s; backward: %s; split form: %s; split backward: %s; split backward of general weights: %s" % (
         _lib.LIB_PATH, "kernels of the longest rows" if has_giant else "generic kernel on the longest rows",
         "kernel of the longest rows" if has_giant_bwd else "generic kernel on the longest rows",
         ("--form " + args.form if args.form != "auto" else "up to %d lines" % _lib.lib().fsw_embed_cart_split_max_lines()) if has_split else "none",
         ("--form-bwd " + args.form_bwd if args.form_bwd != "auto" else
-         "up to %d lines" % _lib.lib().fsw_embed_cart_split_backward_max_lines()) if has_split_bwd else "none"), flush=True)
+         "up to %d lines" % _lib.lib().fsw_embed_cart_split_backward_max_lines()) if has_split_bwd else "none",
+        ("--form-bwd " + args.form_bwd if args.form_bwd != "auto" else
+         "up to %d lines" % _lib.lib().fsw_embed_cart_split_w_backward_max_lines()) if has_split_w_bwd else "none"), flush=True)
     S, F, d = args.slices, args.freqs, 32
     steps, warmup = args.steps, args.warmup
     workload = "w24000,u40000,mixed,c150000,c150000x2,c150000x4,c1000000" if args.workload == ap.get_default("workload") else args.workload
@@ -414,6 +430,11 @@ def giant_leg():
              ("c150000", "one cloud of 150000, unit", [150000], False), ("c150000", "one cloud of 150000, weights", [150000], True),
              ("c150000x2", "2 clouds of 150000, unit", [150000] * 2, False), ("c150000x4", "4 clouds of 150000, unit", [150000] * 4, False),
              ("c1000000", "one cloud of 1000000, unit", [1000000], False), ("c1000000", "one cloud of 1000000, weights", [1000000], True)]
+    if args.weights != "unit":      # every cloud workload with a weight per point
+        cases = [("c150000" if k == 1 else "c150000x%d" % k, "%d cloud(s) of 150000, %s" % (k, args.weights), [150000] * k, True)
+                 for k in (1, 2, 4, 8, 16, 32)] + [("c1000000", "one cloud of 1000000, %s" % args.weights, [1000000], True)]
+        if args.workload == ap.get_default("workload"):
+            workload = ",".join(key for key, _name, sizes, _w in cases if len(sizes) * S <= 256)
     torch.manual_seed(7)
     mod = FSW_embedding(d_in=d, nSlices=S, nFreqs=F, collapse_freqs=True, enable_bias=False, learnable_slices=True,
                         learnable_freqs=True, freqs_init='spread', device=dev)
@@ -423,9 +444,12 @@ def giant_leg():
         gi = torch.cat([torch.full((m,), g, dtype=torch.int64) for g, m in enumerate(sizes)]).to(dev)
         nv = gi.numel()
         w = (0.05 + 0.95 * torch.rand(nv, generator=torch.Generator().manual_seed(8))).to(dev) if weighted else None
+        if weighted and args.weights == "uniform":
+            w = torch.cat([torch.full((m,), 1.0 / m) for m in sizes]).to(dev)
         graph = build_csr(gi.contiguous(), torch.arange(nv, device=dev), w, len(sizes), nv)
         form = "split" if max(mod._cart_split(graph, graph.read_stats()), mod._cart_split_w(graph, graph.read_stats())) > 0 else "one workgroup per line"
-        form_bwd = "split" if mod._cart_split_backward(graph, graph.read_stats()) > 0 else "one workgroup per line"
+        form_bwd = "split" if max(mod._cart_split_backward(graph, graph.read_stats()),
+                                  mod._cart_split_w_backward(graph, graph.read_stats())) > 0 else "one workgroup per line"
         x = torch.randn((nv, d), device=dev)
         xg = x.clone().requires_grad_(True)
         out = torch.empty((len(sizes), S * F), device=dev)
