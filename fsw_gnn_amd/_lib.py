@@ -129,6 +129,7 @@ _SIGNATURES = {
     "fsw_conv_fused_cart_lds_bytes": (c_sz, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "fsw_conv_fused_cart_f32": (ctypes.c_int, [ctypes.POINTER(CartArgs), c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_i64, ctypes.c_int,
                                                ctypes.c_int, c_f32, c_vp, c_i64, c_vp]),
+    "fsw_edge_keys_f32": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_i64, ctypes.c_int, c_vp, c_i64, c_vp]),
     "fsw_segcumsum_workspace_bytes": (c_sz, [c_i64]),
     "fsw_segcumsum": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, c_i64, ctypes.c_int, c_vp, c_sz, c_vp]),
     # legacy ABI, exact reference signatures (reference fsw_embedding.py:2952-2977)

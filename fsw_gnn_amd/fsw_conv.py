@@ -55,7 +55,7 @@ class FSW_conv(_Base):
                  dropout_final=0, dropout_hidden=0,
                  self_loop_weight=0, edge_weighting='unit',
                  device=None, dtype=torch.float32,
-                 config=None, embed_slices=None, embed_freqs=None):
+                 config=None, embed_slices=None, embed_freqs=None, cartesian_edge_features=False):
         if _HAVE_PYG:
             super().__init__(aggr=None)
         else:
@@ -76,7 +76,7 @@ class FSW_conv(_Base):
                     learnable_vertex_degree_encoding_scale, homog_degree_encoding, vertex_degree_pad_thresh,
                     concat_self, message_weight_vs_self, bias, mlp_layers, mlp_hidden_dim, mlp_activation_final,
                     mlp_activation_hidden, mlp_init, batchNorm_final, batchNorm_hidden, dropout_final, dropout_hidden,
-                    self_loop_weight, edge_weighting, device, dtype, embed_slices=None, embed_freqs=None):
+                    self_loop_weight, edge_weighting, device, dtype, embed_slices=None, embed_freqs=None, cartesian_edge_features=False):
         # Cartesian embedding (an extension beyond the reference): embed_slices slices, each read out at embed_freqs
         # frequencies -- FSW_embedding(nSlices, nFreqs, collapse_freqs=True) instead of embed_dim (slice, frequency) pairs
         cartesian = embed_slices is not None or embed_freqs is not None
@@ -158,7 +158,8 @@ class FSW_conv(_Base):
                                        total_mass_encoding_method=method,
                                        total_mass_pad_thresh=vertex_degree_pad_thresh,
                                        minimize_slice_coherence=True, freqs_init='spread',
-                                       enable_bias=embedding_bias, device=device, dtype=dtype)
+                                       enable_bias=embedding_bias, device=device, dtype=dtype,
+                                       cartesian_edge_features=cartesian_edge_features)
         device = device if device is not None else self.fsw_embed.get_device()
         self.to(device=device, dtype=dtype)
 
@@ -264,7 +265,7 @@ class FSW_conv(_Base):
         if sp is not None:
             return self._forward_slice_parallel(sp, x, vertex_features, edge_index, edge_features, needs_grad)
         if emb_mod.cartesian_mode:
-            return self._forward_cartesian(x, vertex_features, edge_index, needs_grad)
+            return self._forward_cartesian(x, vertex_features, edge_index, needs_grad, edge_features)
         graph = self.build_graph(edge_index, n, edge_features if self.edgefeat_dim > 0 else None)
         E = self.embed_dim
         scale = self._message_scale
@@ -318,16 +319,20 @@ class FSW_conv(_Base):
             emb_mod.embed_into(x, graph, buf, out_scale=scale, x_copy=xc)   # X stored by the projection kernel
         return self._tail_buffer(buf)
 
-    def _forward_cartesian(self, x, vertex_features, edge_index, needs_grad):
+    def _forward_cartesian(self, x, vertex_features, edge_index, needs_grad, edge_features=None):
         """float32 layer with a Cartesian embedding (embed_slices x embed_freqs): training through _CartEmbedFn and the usual tail;
         inference through ONE kernel for the embedding and the first Linear layer (csrc/conv_fused.hip: k_conv_fused_cart) when the
         configuration is fusable and no row has more than REG_MAX_DEG neighbours, else embed_cartesian_into + the torch tail.
-        Finishing only the long rows next to the fused kernel (_finish_long_rows) is not done here: DESIGN.md."""
+        Finishing only the long rows next to the fused kernel (_finish_long_rows) is not done here: DESIGN.md.
+        Edge features (edgefeat_dim > 0, a layer built with cartesian_edge_features=True): the coalesced graph of build_graph, the embedding on the keys of its entries
+        (FSW_embedding.prepare_cartesian), never the fused kernel (_fusable), training through _CartEdgeEmbedFn."""
         emb_mod = self.fsw_embed
         n = x.shape[0]
-        graph = self.build_graph(edge_index, n)
+        has_ef = self.edgefeat_dim > 0
+        graph = self.build_graph(edge_index, n, edge_features if has_ef else None)
         if needs_grad:
-            return self._tail(emb_mod.embed_cartesian_autograd(x, graph), vertex_features)
+            ef_in = edge_features.reshape(edge_index.shape[1], -1) if has_ef else None
+            return self._tail(emb_mod.embed_cartesian_autograd(x, graph, edge_feat=ef_in), vertex_features)
         scale = self._message_scale
         prepared = emb_mod.prepare_cartesian(x, graph)
         bsh = graph.bin_start_host[0]

@@ -33,7 +33,12 @@ rows above 32768 neighbours make few (row, slice) lines -- one point cloud, one 
 (_cart_split_backward, csrc/embed_split_cart_bwd.hip); general weights -- a weight tensor, W = 'uniform', total_mass_pad_thresh > 1 --
 have split forms of their own in both directions (forward: _cart_split_w, csrc/embed_split_cart_w.hip; backward:
 _cart_split_w_backward, csrc/embed_split_cart_w_bwd.hip).  It needs a HIP device at construction (this
-package has no CPU path in any mode) and does not take edge features (d_edge > 0 raises NotImplementedError).  Two deliberate
+package has no CPU path in any mode).  Edge features (d_edge > 0) in Cartesian mode are opt-in (cartesian_edge_features=True; the
+constructor raises NotImplementedError without it, as it always did): the coalescing build as in diagonal mode, then
+fsw_edge_keys_f32 (csrc/edge_keys.hip) stores the key of every CSR entry once, K[e, s] = Xp[col[e], s] + <ef[e], projVecs[s, d_in:]>
+(prepare_cartesian / _edge_keys), and the same tuned kernels run on K with the identity as their column array in both directions
+(_CartEdgeEmbedFn; every serialize_num_slices chunk forms its own K); float64 modules and calls whose W or X_edge requires grad give
+the generic kernel the same keys (_GenericEmbedFn).  Two deliberate
 differences from the reference: sparse-COO W works (same result as dense W), and collapsed + total mass +
 bias works with the bias of shape (S*F + 1,) that generate_embedding_parameters creates.
 """
@@ -369,7 +374,8 @@ class _GenericEmbedFn(torch.autograd.Function):
 
       fsw_embed_generic (csrc/embed_generic.hip): out [num_rows, has_mass + S], slice s read out at frequency s.
       fsw_embed_cart_generic (the same kernel; arguments checked in csrc/embed_cart.hip): out [num_rows, has_mass + S F], column has_mass + s F + f = (slice s,
-        frequency f); bias flattened, gkey one column per slice, gf one entry per frequency; efvals is always None (no edge features).
+        frequency f); bias flattened, gkey one column per slice, gf one entry per frequency; edge features: the kernel has no edge term, so it
+        runs on the keys of the entries, Xp[col] + Ke, with the identity as its col (forward()).
 
     Callers: every float64 module (the float64 build of the path, reference test_conv.py:24), float32 modules whose weights or
     sparse edge features require a gradient (the tuned float32 backward kernels treat W as a constant), and Cartesian mode under
@@ -418,9 +424,16 @@ class _GenericEmbedFn(torch.autograd.Function):
             out = torch.empty((csr.num_rows, module.d_out), dtype=X.dtype, device=X.device)
             ms = float(mass_scale.detach()) if mass_scale is not None else 1.0
             b = bias.detach().contiguous() if bias is not None else None
+            ctx.key_col = {}
+            if module.cartesian_mode and Ke is not None:
+                # fsw_embed_cart_generic has no edge term: it gets the key of every entry, K = Xp[col] + Ke [nnz, S], as its Xp and
+                # the identity as its col (a launch field); gkey is then dL/dK and backward() below applies unchanged
+                Xp, ldp, Ke = (Xp[csr.col.long(), :S] + Ke).contiguous(), S, None
+                ctx.key_ident = torch.arange(max(csr.nnz, 1), dtype=torch.int32, device=X.device)
+                ctx.key_col = {"col": ctx.key_ident.data_ptr()}
             ctx.aux = (Xp, ldp, Ke, wv)
             _GenericEmbedFn.launch(module, csr, ctx.aux, fr, out_scale, ms, out=out.data_ptr(), ldo=out.stride(0),
-                                   bias=b.data_ptr() if b is not None else None)
+                                   bias=b.data_ptr() if b is not None else None, **ctx.key_col)
         ctx.module, ctx.csr, ctx.out_scale, ctx.mass_scale_value = module, csr, float(out_scale), ms
         ctx.has_ef, ctx.has_w = efvals is not None, wvals is not None
         ctx.save_for_backward(X, V, freqs, efvals if efvals is not None else X.new_zeros(0))
@@ -430,7 +443,7 @@ class _GenericEmbedFn(torch.autograd.Function):
     def key_grads(ctx, g, gkey, gf, gw):
         """The entry point in backward mode: stores gkey [nnz, S], accumulates gf [nFreqs] and gw [nnz] (each nullable)."""
         freqs = ctx.saved_tensors[2]
-        fields = {}
+        fields = dict(ctx.key_col)      # Cartesian mode with edge features: the identity col that goes with the key array (forward)
         if gw is not None:
             # The reference pads no row unless the mass of SOME row is below the threshold (`if (W_pad > 0).any()`, fsw_embedding.py:790):
             # without a deficient row there is no pad element and no clamp on the path of the weights, so a row with m == tau exactly
@@ -587,6 +600,89 @@ class _CartEmbedFn(torch.autograd.Function):
         return gX, gV, gfreqs, gbias, gscale, None, None, None
 
 
+class _CartEdgeEmbedFn(torch.autograd.Function):
+    """_CartEmbedFn for a graph with edge features (d_edge > 0, the coalescing build): the same tuned kernels in both directions, run on
+    the key of every CSR entry, K[e, s] = Xp[col[e], s] + <ef[e], projVecs[s, d_in:]> (prepare_cartesian: fsw_edge_keys_f32), with the
+    identity as their column array.  The gkey [nnz, S] the backward kernels store is then dL/dK, and from it
+      gXp = the rows of gkey summed by the graph's own col (the store-and-sum pair on graph.sender_major(), no float atomics),
+      gX = gXp . V[:, :d_in],   gprojVecs = [gXp^T . X | gkey^T . ef],
+      g edge_feat[i] = gkey[slot_of_edge[i]] . V[:, d_in:] (merged parallel edges each receive their slot's gradient, dropped edges 0),
+    as _EmbedGraphFn does in diagonal mode.  gfreqs, gbias and the total-mass scale as in _CartEmbedFn.  edge_feat: the per-input-edge
+    tensor the graph was coalesced from (needs graph.slot_of_edge when it requires grad), or None."""
+
+    @staticmethod
+    def forward(ctx, X, projVecs, freqs, bias, mass_scale, edge_feat, module, graph, out_scale):
+        with torch.no_grad():
+            prepared = module.prepare_cartesian(X, graph)
+            out = torch.empty((graph.num_rows, module.d_out), dtype=X.dtype, device=X.device)
+            module.embed_cartesian_into(X, graph, out, bias.detach().reshape(-1) if bias is not None else None, out_scale=out_scale,
+                                        prepared=prepared)
+        ctx.module, ctx.graph, ctx.prepared, ctx.out_scale = module, graph, prepared, float(out_scale)
+        ctx.bias_shape = bias.shape if bias is not None else None
+        ctx.num_edge_rows = 0 if edge_feat is None else edge_feat.shape[0]
+        ctx.save_for_backward(X, projVecs, freqs)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        module, graph, prepared, out_scale = ctx.module, ctx.graph, ctx.prepared, ctx.out_scale
+        X, V, freqs = ctx.saved_tensors
+        L = _lib.lib()
+        S, F, has_mass, d_in = module.nSlices, module.nFreqs, module.total_mass_encoding_dim, module.d_in
+        g = g.contiguous()
+        dev = X.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        st = prepared["stats"]
+        nnz = st[_lib.STAT_NNZ]
+        need = ctx.needs_input_grad
+        gX = gV = gfreqs = gbias = gscale = gEf = None
+        if nnz > 0 and (need[0] or need[1] or need[2] or need[5]):
+            fr = freqs.detach().contiguous()
+            Vd = V.detach()
+            gf = torch.zeros(F, dtype=torch.float32, device=dev)
+            gkey = torch.empty((nnz, S), dtype=torch.float32, device=dev)      # every entry is stored
+            split_w_bytes = module._cart_split_w_backward(graph, st)          # a coalesced graph carries weights: general-weight kernels
+            scratch = module._cart_scratch(graph, st, backward=True, reuse=prepared["scratch"], split_bytes=split_w_bytes)
+            a = module._cart_tuned_args(graph, st, prepared["Xp"], prepared["ldp"], fr, S, None, scratch, out_scale, has_mass,
+                                        split_w_backward=split_w_bytes > 0, col=prepared["col"])
+            a.g, a.ldg, a.gkey, a.ldk, a.gfreq = g.data_ptr(), g.stride(0), gkey.data_ptr(), S, gf.data_ptr()
+            _lib.check(L.fsw_embed_cart_backward_keys_f32(ctypes.byref(a), None, F, stream), "fsw_embed_cart_backward_keys_f32")
+            if need[0] or need[1]:
+                ldg = _round_up(S, 32)
+                gXp = torch.zeros((X.shape[0], ldg), dtype=torch.float32, device=dev)
+                cptr, order = graph.sender_major()
+                _lib.check(L.fsw_segment_sum_rows_f32(_lib.ptr(gkey), S, _lib.ptr(cptr), _lib.ptr(order), graph.num_cols, nnz, S,
+                                                      _lib.ptr(gXp), ldg, stream), "fsw_segment_sum_rows_f32")
+                if need[0]:
+                    gX = _grad_x(L, gXp, S, ldg, Vd[:, :d_in], stream)
+                if need[1]:
+                    gV = torch.cat([gemm_tn(gXp[:, :S], X.detach()), gkey.t() @ graph.ef[:nnz]], dim=1)
+            if need[5]:
+                assert graph.slot_of_edge is not None, 'the gradient of the edge features needs a graph built with want_slots=True'
+                slot = graph.slot_of_edge[:ctx.num_edge_rows].long()
+                gslots = gkey @ Vd[:, d_in:]
+                gEf = torch.where((slot >= 0)[:, None], gslots[slot.clamp(min=0)], torch.zeros((), device=dev))
+            if need[2]:
+                gfreqs = gf
+        if need[0] and gX is None:
+            gX = torch.zeros_like(X)
+        if need[1] and gV is None:
+            gV = torch.zeros_like(V)
+        if need[2] and gfreqs is None:
+            gfreqs = torch.zeros_like(freqs)
+        if need[5] and gEf is None:
+            gEf = torch.zeros((ctx.num_edge_rows, module.d_edge), dtype=X.dtype, device=dev)
+        if need[3]:
+            gbias = (out_scale * g.sum(dim=0)).reshape(ctx.bias_shape)
+        if need[4]:
+            deg = (graph.rowptr[1:] - graph.rowptr[:-1]).long()
+            rows = torch.repeat_interleave(torch.arange(graph.num_rows, device=dev), deg)
+            m = torch.zeros(graph.num_rows, dtype=torch.float32, device=dev).index_add_(0, rows, graph.w[:rows.numel()])
+            gscale = (out_scale * (g[:, 0] * _mass_f(module.total_mass_encoding_function, m)).sum()).reshape(())
+        return gX, gV, gfreqs, gbias, gscale, gEf, None, None, None
+
+
 class FSW_embedding(nn.Module):
     def __init__(self,
                  d_in, d_out=None, nSlices=None, nFreqs=None, collapse_freqs=False,
@@ -603,7 +699,8 @@ class FSW_embedding(nn.Module):
                  device=None, dtype=torch.float32,
                  load_custom_cuda_lib=True,
                  report=False, user_warnings=True,
-                 report_on_coherence_minimization=False):
+                 report_on_coherence_minimization=False,
+                 cartesian_edge_features=False):
         super().__init__()
         self.user_warnings = user_warnings
         # reference fsw_embedding.py:195-206 loads its CUDA library here; this build cannot run without its
@@ -665,9 +762,11 @@ class FSW_embedding(nn.Module):
             if self.device_new.type != 'cuda':
                 raise NotImplementedError("fsw_gnn_amd: Cartesian mode needs a HIP device ('cuda'), got device=%s; this package has "
                                           "no CPU path in any mode" % self.device_new)
-            if d_edge > 0:
-                raise NotImplementedError("fsw_gnn_amd: Cartesian mode with edge features (d_edge > 0) is not implemented (the "
-                                          "reference lists the combination as untested)")
+            # opt-in: without the keyword the constructor refuses as it always did (callers that rely on the refusal keep it; the
+            # reference runs the combination through its dense-W path only and lists it as untested)
+            if d_edge > 0 and not cartesian_edge_features:
+                raise NotImplementedError("fsw_gnn_amd: Cartesian mode with edge features (d_edge > 0) is opt-in: pass "
+                                          "cartesian_edge_features=True (the reference lists the combination as untested)")
         assert dtype.is_floating_point and (not dtype.is_complex), \
             'dtype must be real floating-point; instead got dtype=%s' % (dtype)
         if dtype not in (torch.float32, torch.float64):
@@ -894,9 +993,11 @@ class FSW_embedding(nn.Module):
 
         if self.cartesian_mode:
             # float32 calls run on the tuned kernels, under autograd with their own backward; the generic kernel keeps float64
-            # modules and gradients of the weights (a W that requires grad selects it, whatever else does)
-            generic = self.get_dtype() == torch.float64 or (torch.is_grad_enabled() and torch.is_tensor(W) and W.requires_grad)
-            out = self._forward_cartesian(Xf, rec, snd, wvals, num_rows, generic, needs_grad, serialize_num_slices)
+            # modules and gradients of the weights or of X_edge (a W or X_edge that requires grad selects it, whatever else does: the
+            # rule of the diagonal mode above)
+            generic = self.get_dtype() == torch.float64 or (torch.is_grad_enabled() and (
+                (torch.is_tensor(W) and W.requires_grad) or (self.d_edge > 0 and X_edge.requires_grad)))
+            out = self._forward_cartesian(Xf, rec, snd, wvals, num_rows, generic, needs_grad, serialize_num_slices, efvals)
             return out.reshape(out_shape + ((self.d_out,) if self.collapse_freqs else (self.nSlices, self.nFreqs)))
         if generic and num_rows > 0 and Xf.shape[0] > 0:
             if self.d_out == 0:
@@ -932,10 +1033,11 @@ class FSW_embedding(nn.Module):
         P = _GenericEmbedFn.apply(Xf, self.projVecs, self.freqs, bias if plain else None, scale, wvals, efvals, self, csr, 1.0)
         return P if plain else self._homog_epilogue(P, 1.0, bias)
 
-    def _forward_cartesian(self, Xf, rec, snd, wvals, num_rows, generic, train, serialize_num_slices):
+    def _forward_cartesian(self, Xf, rec, snd, wvals, num_rows, generic, train, serialize_num_slices, efvals=None):
         """Cartesian mode: [num_rows, has_mass + S F], column has_mass + s F + f = (slice s, frequency f).  generic: the generic
-        kernel (float64 modules, gradients of W); otherwise the tuned float32 kernels (csrc/embed_cart.hip), under autograd
-        (train) with their backward (_CartEmbedFn, csrc/embed_cart_bwd.hip)."""
+        kernel (float64 modules, gradients of W or X_edge); otherwise the tuned float32 kernels (csrc/embed_cart.hip), under autograd
+        (train) with their backward (_CartEmbedFn, csrc/embed_cart_bwd.hip).  efvals [nnz, d_edge]: the edge features of the entries
+        (d_edge > 0): the coalescing build, as in diagonal mode, and the kernels on the key of every entry (_edge_keys)."""
         dev, dt = Xf.device, Xf.dtype
         S, F = self.nSlices, self.nFreqs
         if num_rows == 0 or self.d_out == 0:
@@ -950,8 +1052,11 @@ class FSW_embedding(nn.Module):
             Z = torch.zeros((num_rows, self.d_out), dtype=dt, device=dev)
             return Z + bias if bias is not None else Z
         if generic:
-            return self._forward_generic(Xf.contiguous(), rec, snd, wvals, None, num_rows, bias)
-        graph = build_csr(rec, snd, wvals.detach().contiguous() if wvals is not None else None, num_rows, Xf.shape[0])
+            return self._forward_generic(Xf.contiguous(), rec, snd, wvals, efvals, num_rows, bias)
+        if self.d_edge > 0:
+            graph = build_csr_coalesced(rec, snd, wvals.detach().contiguous(), efvals.detach().contiguous(), num_rows, Xf.shape[0])
+        else:
+            graph = build_csr(rec, snd, wvals.detach().contiguous() if wvals is not None else None, num_rows, Xf.shape[0])
         if train:
             return self.embed_cartesian_autograd(Xf.contiguous(), graph)
         with torch.no_grad():
@@ -960,12 +1065,18 @@ class FSW_embedding(nn.Module):
                                       serialize_num_slices)
             return out if plain else self._homog_epilogue(out, 1.0, bias.detach() if bias is not None else None)
 
-    def embed_cartesian_autograd(self, X, graph, out_scale=1.0):
+    def embed_cartesian_autograd(self, X, graph, out_scale=1.0, edge_feat=None):
         """Differentiable float32 Cartesian embedding of a CSR graph, [num_rows, d_out] collapsed (training path of forward() and of
         FSW_conv / FSW_readout with embed_slices / embed_freqs): see _CartEmbedFn.  'homog' / 'homog_alt': the 'plain' embedding
-        without bias from the kernels, then the epilogue out of place so that autograd differentiates it (as embed_autograd does)."""
+        without bias from the kernels, then the epilogue out of place so that autograd differentiates it (as embed_autograd does).
+        A graph with edge features (d_edge > 0, the coalescing build) goes through _CartEdgeEmbedFn; edge_feat: the per-input-edge
+        feature tensor the graph was coalesced from (its gradient is routed back through graph.slot_of_edge), or None."""
         scale = self.total_mass_encoding_scale if self.encode_total_mass else None
         plain = self.plain_mass
+        if graph.ef is not None:
+            P = _CartEdgeEmbedFn.apply(X, self.projVecs, self.freqs, self.bias if (plain and self.enable_bias) else None, scale, edge_feat,
+                                       self, graph, out_scale)
+            return P if plain else self._homog_epilogue(P, out_scale, self.bias.reshape(-1) if self.enable_bias else None)
         P = _CartEmbedFn.apply(X, self.projVecs, self.freqs, self.bias if (plain and self.enable_bias) else None, scale, self, graph,
                                out_scale)
         return P if plain else self._homog_epilogue(P, out_scale, self.bias.reshape(-1) if self.enable_bias else None)
@@ -1081,15 +1192,17 @@ class FSW_embedding(nn.Module):
         return torch.empty(nbytes, dtype=torch.uint8, device=graph.rowptr.device) if nbytes else None
 
     def _cart_tuned_args(self, graph, st, Xp, ldp, fr, S, table, scratch, out_scale, has_mass, split=False, split_backward=False, split_w=False,
-                         split_w_backward=False):
+                         split_w_backward=False, col=None):
         """struct fsw_cart_args of the tuned entry points (fsw_embed_cart_f32, fsw_embed_cart_backward_keys_f32) without the
         output / gradient fields.  split: FSW_CART_SPLIT_LINES, for the forward call only (_cart_split); split_w: FSW_CART_SPLIT_W_LINES,
         for the forward call only (_cart_split_w); split_backward: FSW_CART_SPLIT_BWD_LINES, for the backward call only
-        (_cart_split_backward); split_w_backward: FSW_CART_SPLIT_W_BWD_LINES, for the backward call only (_cart_split_w_backward)."""
+        (_cart_split_backward); split_w_backward: FSW_CART_SPLIT_W_BWD_LINES, for the backward call only (_cart_split_w_backward).
+        col: the column array the kernels gather Xp by, the graph's by default; with edge features Xp is the key array of _edge_keys
+        (one row per CSR entry) and col the identity (_identity_col) -- everything else still comes from the graph."""
         a = _cart_args(self, Xp, ldp, fr, S, out_scale, has_mass, self._mass_scale_read(st))
         a.flags = ((_lib.CART_SPLIT_LINES if split else 0) | (_lib.CART_SPLIT_BWD_LINES if split_backward else 0) |
                    (_lib.CART_SPLIT_W_LINES if split_w else 0) | (_lib.CART_SPLIT_W_BWD_LINES if split_w_backward else 0))
-        a.rowptr, a.col = graph.rowptr.data_ptr(), graph.col.data_ptr()
+        a.rowptr, a.col = graph.rowptr.data_ptr(), (col if col is not None else graph.col).data_ptr()
         a.w = graph.w.data_ptr() if graph.w is not None else None
         a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), graph.bin_start_host[0].ctypes.data
         a.num_rows, a.max_degree = graph.num_rows, st[_lib.STAT_MAX_DEGREE]
@@ -1115,9 +1228,42 @@ class FSW_embedding(nn.Module):
                    "fsw_project_f32")
         st = self._checked_stats(graph)   # one device->host read per forward (flags + degree bins)
         split_bytes, split_w_bytes = self._cart_split(graph, st), self._cart_split_w(graph, st)    # one of them is 0
-        return {"Xp": Xp, "ldp": ldp, "stats": st, "table": self._cart_unit_table(graph, self.freqs.detach().contiguous()),
+        col = None
+        assert (graph.ef is None) == (self.d_edge == 0), 'edge features must be given exactly when d_edge > 0'
+        if graph.ef is not None:
+            # edge features: the sort kernels run on the key of every CSR entry, K [nnz, ldk], gathered by the identity; the backward
+            # reads the same K, so both directions see bit-identical keys
+            Xp, ldp = self._edge_keys(graph, st, Xp, ldp, 0, S)
+            col = self._identity_col(graph, st)
+        return {"Xp": Xp, "ldp": ldp, "col": col, "stats": st, "table": self._cart_unit_table(graph, self.freqs.detach().contiguous()),
                 "scratch": self._cart_scratch(graph, st, split_bytes=max(split_bytes, split_w_bytes)), "split": split_bytes > 0,
                 "split_w": split_w_bytes > 0}
+
+    def _edge_keys(self, graph, st, Xp, ldp, k0, k1, K=None):
+        """(K, ldk): K[e, s] = Xp[col[e], s] + <ef[e], projVecs[k0 + s, d_in:]> for the st[STAT_NNZ] entries of a coalesced graph with edge
+        features and the slices k0 .. k1 - 1 whose projection Xp holds (fsw_edge_keys_f32, csrc/edge_keys.hip: the float32 fma chain of
+        the diagonal edge-feature kernels).  ldk = the slices rounded up to 4 floats: the Cartesian kernels ask ldp >= S of their key
+        array and nothing else (cart_check_common), and rows of whole 16 bytes give the key kernel its 16-byte accesses.  Called after
+        the stats read, which has validated the column indices the kernel trusts.  K: a buffer to fill again (chunks of slices)."""
+        S, nnz = k1 - k0, st[_lib.STAT_NNZ]
+        ldk = _round_up(S, 4)
+        if K is None:
+            K = torch.empty((max(nnz, 1), ldk), dtype=torch.float32, device=Xp.device)
+        assert K.shape == (max(nnz, 1), ldk) and 0 <= nnz <= graph.col.numel() and graph.ef.shape[1] == self.d_edge
+        V = self.projVecs.detach()
+        _lib.check(_lib.lib().fsw_edge_keys_f32(_lib.ptr(graph.col), nnz, _lib.ptr(Xp), ldp, _lib.ptr(graph.ef), self.d_edge,
+                                                V.data_ptr() + 4 * (k0 * V.stride(0) + self.d_in), V.stride(0), S, _lib.ptr(K), ldk,
+                                                torch.cuda.current_stream(Xp.device).cuda_stream), "fsw_edge_keys_f32")
+        return K, ldk
+
+    @staticmethod
+    def _identity_col(graph, st):
+        """int32 0 .. nnz - 1, the column array that goes with the key array of _edge_keys; kept on the graph."""
+        ident = getattr(graph, "_identity_col", None)
+        n = max(st[_lib.STAT_NNZ], 1)
+        if ident is None or ident.numel() < n:
+            ident = graph._identity_col = torch.arange(n, dtype=torch.int32, device=graph.col.device)
+        return ident
 
     def embed_cartesian_into(self, X, graph: CSRGraph, out, bias=None, serialize_num_slices=None, out_scale=1.0, prepared=None):
         """Tuned float32 Cartesian forward (fsw_embed_cart_f32) of a CSR graph into out [num_rows, d_out] (unit inner stride): the
@@ -1139,6 +1285,7 @@ class FSW_embedding(nn.Module):
         if prepared is not None:
             Xp, ldp, st, table, scratch = (prepared[k] for k in ("Xp", "ldp", "stats", "table", "scratch"))
             split, split_w = prepared.get("split", False), prepared.get("split_w", False)
+            keys, ldk, col = Xp, ldp, prepared.get("col")
         else:       # chunks of slices: Xp once per forward, refilled by every chunk
             ldp = _round_up(step, 32)
             Xp = torch.empty((X.shape[0], ldp), dtype=torch.float32, device=dev)
@@ -1146,6 +1293,8 @@ class FSW_embedding(nn.Module):
             table = self._cart_unit_table(graph, fr)
             st = scratch = None
             split = split_w = False
+            keys, ldk, col = Xp, ldp, None
+            assert (graph.ef is None) == (self.d_edge == 0), 'edge features must be given exactly when d_edge > 0'
         for k0 in range(0, S, step):
             k1 = min(S, k0 + step)
             if prepared is None:
@@ -1158,10 +1307,14 @@ class FSW_embedding(nn.Module):
                     split_bytes, split_w_bytes = self._cart_split(graph, st), self._cart_split_w(graph, st)    # on all nSlices: every chunk takes the same form
                     split, split_w = split_bytes > 0, split_w_bytes > 0
                     scratch = self._cart_scratch(graph, st, split_bytes=max(split_bytes, split_w_bytes))
+                if graph.ef is not None:      # every chunk forms its own keys from its own Xp and its rows of projVecs[:, d_in:]
+                    refill = keys if (keys is not Xp and keys.shape[1] == _round_up(k1 - k0, 4)) else None
+                    keys, ldk = self._edge_keys(graph, st, Xp, ldp, k0, k1, K=refill)
+                    col = self._identity_col(graph, st)
             first = k0 == 0
             col0 = 0 if first else has_mass + k0 * F
-            a = self._cart_tuned_args(graph, st, Xp, ldp, fr, k1 - k0, table, scratch, out_scale, has_mass if first else 0, split=split,
-                                      split_w=split_w)
+            a = self._cart_tuned_args(graph, st, keys, ldk, fr, k1 - k0, table, scratch, out_scale, has_mass if first else 0, split=split,
+                                      split_w=split_w, col=col)
             a.out, a.ldo = out.data_ptr() + 4 * col0, out.stride(0)
             a.bias = (bias.data_ptr() + 4 * col0) if bias is not None else None
             _lib.check(L.fsw_embed_cart_f32(ctypes.byref(a), stream), "fsw_embed_cart_f32")

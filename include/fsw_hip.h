@@ -598,6 +598,16 @@ size_t fsw_conv_fused_cart_lds_bytes(int S, int F, int has_mass);
 int fsw_conv_fused_cart_f32(const fsw_cart_args* args, const float* Wq, int64_t ldw, const float* lin_bias, int Hout,
                             const float* Yin, int64_t ldyin, int yin_by_node, int act, float slope, float* Y, int64_t ldy,
                             fsw_stream_t stream);
+/* Cartesian mode with edge features (csrc/edge_keys.hip): the key of every CSR entry, stored once,
+ *   K[e*ldk + s] = Xp[col[e]*ldp + s] followed by key = fmaf(efeat[e*d_edge + q], Ve[s*ldve + q], key) for q = 0 .. d_edge - 1 in
+ *   that order, in float32 -- the rounding rule of the diagonal edge-feature kernels (fsw_embed_args.efeat above).
+ * The Cartesian entry points then run unchanged on (Xp := K, ldp := ldk, col := the identity 0 .. nnz - 1), and the gkey [nnz, S] their
+ * backward stores is dL/dK: no field of fsw_cart_args and no kernel of theirs knows about edge features.  Ve = projVecs[:, d_in:] read
+ * in place (ldve = d_in + d_edge).  Columns S .. ldk - 1 of K are not written.  Any S >= 1, d_edge >= 1, 0 <= nnz < 2^31 (nnz == 0:
+ * no launch); needs ldp >= S, ldk >= S, ldve >= d_edge.  The entries of col are trusted (fsw_graph_build_coalesced validated them).
+ * A streaming kernel: nnz * (4 + 4 d_edge + 8 S) bytes. */
+int fsw_edge_keys_f32(const int32_t* col, int64_t nnz, const float* Xp, int64_t ldp, const float* efeat, int d_edge, const float* Ve,
+                      int64_t ldve, int S, float* K, int64_t ldk, fsw_stream_t stream);
 
 /* ---- stand-alone segmented cumulative sum --------------------------------------------------------
  * Replaces segcumsum / segcumsum_cuda (reference fsw_embedding.py:2795-3012): inclusive scan of

@@ -78,7 +78,12 @@ weighted cloud of 1 000 000 points, then 1, 2, 4, .. 32 clouds of 150 000 points
 uniform (1 / size of the cloud) | random.  Both forms alternate over --runs runs of --steps calls each, every call on the next of three
 (scratch, output) buffer pairs; the medians and the error of one form against the other are printed:
     python tools/exp_cartesian.py --giant --workload splitw --weights uniform --steps 20 --warmup 3 --runs 5
-    rocprofv3 --kernel-trace --stats -d DIR -o splitw -- python tools/exp_cartesian.py --giant --workload splitw,c150000 --steps 1 --runs 1"""
+    rocprofv3 --kernel-trace --stats -d DIR -o splitw -- python tools/exp_cartesian.py --giant --workload splitw,c150000 --steps 1 --runs 1
+--conv --edge-features D: the Cartesian layer with D features per edge (the keys of the CSR entries from csrc/edge_keys.hip, then the
+tuned Cartesian kernels) against its diagonal workaround, the same layer with every slice repeated F times, alternating over --runs runs;
+--edge-keys: fsw_edge_keys_f32 alone at 10M entries against a device-to-device copy of the same byte count:
+    python tools/exp_cartesian.py --conv --edge-features 4 [--train]
+    python tools/exp_cartesian.py --edge-keys --edge-features 4 --slices 16"""
 import argparse
 import ctypes
 import os
@@ -105,6 +110,12 @@ ap.add_argument("--generic", action="store_true", help="--train: the generic Car
 ap.add_argument("--conv", action="store_true", help="time the FSW_conv layer (diagonal / Cartesian unfused / Cartesian fused)")
 ap.add_argument("--forms", default="unfused,fused", help="--conv: forms to time, alternating over the runs (--train: diag, cart)")
 ap.add_argument("--runs", type=int, default=5, help="--conv: runs of every form")
+ap.add_argument("--edge-features", type=int, default=0, metavar="D",
+                help="--conv: D features per edge; times the Cartesian layer (form cart) against its diagonal workaround, the same layer "
+                     "with every slice repeated F times (form diag), alternating over the runs")
+ap.add_argument("--edge-keys", action="store_true",
+                help="time fsw_edge_keys_f32 at 10M entries, --slices slices, --edge-features (default 4) features against a "
+                     "device-to-device copy of the same byte count, alternating over the runs")
 ap.add_argument("--hub", action="store_true", help="time the unit-weight hub rows (2049 .. 32768 neighbours), forward and training step")
 ap.add_argument("--giant", action="store_true", help="time the longest rows (unit: above 32768 neighbours, weights: from 16384), forward and training step")
 ap.add_argument("--weights", choices=("unit", "uniform", "random"), default="unit",
@@ -176,6 +187,76 @@ def train_leg():
             mod(xc, Wc).backward(G)
 
         print("train pc: %d clouds x %d points d_in=3 S=64 F=16 W=uniform, %s: %.3f ms/step" % (B, npts, path, step_ms(step)), flush=True)
+
+
+def edge_keys_leg():
+    """fsw_edge_keys_f32 (csrc/edge_keys.hip) against a device-to-device copy that moves the same bytes, nnz (4 + 4 d_edge + 8 S)."""
+    L = _lib.lib()
+    nnz, n, S, D = 10_000_000, 1_000_000, args.slices, args.edge_features or 4
+    ldp, ldk = (S + 31) // 32 * 32, (S + 3) // 4 * 4
+    torch.manual_seed(7)
+    col = torch.randint(0, n, (nnz,), device=dev, dtype=torch.int32)
+    Xp, ef, V = torch.randn((n, ldp), device=dev), torch.randn((nnz, D), device=dev), torch.randn((S, 8 + D), device=dev)
+    K = torch.empty((nnz, ldk), device=dev)
+    nbytes = nnz * (4 + 4 * D + 8 * S)
+    src = torch.empty(nbytes // 8, dtype=torch.float32, device=dev).normal_()
+    dst = torch.empty_like(src)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+
+    def keys():
+        _lib.check(L.fsw_edge_keys_f32(_lib.ptr(col), nnz, _lib.ptr(Xp), ldp, _lib.ptr(ef), D, V.data_ptr() + 4 * 8, V.stride(0), S,
+                                       _lib.ptr(K), ldk, stream), "fsw_edge_keys_f32")
+
+    print("edge keys: nnz=%d senders=%d S=%d d_edge=%d ldp=%d ldk=%d, %.3f GB per call" % (nnz, n, S, D, ldp, ldk, nbytes / 1e9))
+    for run in range(args.runs):
+        for name, fn in (("keys", keys), ("copy", lambda: dst.copy_(src))):
+            for _ in range(args.warmup if run == 0 else 1):
+                fn()
+            ms = bench.timed_ms(fn, args.reps, dev)
+            print("run %d  %-5s %8.3f ms  %.2f TB/s" % (run, name, ms, nbytes / 1e9 / ms), flush=True)
+
+
+def conv_edge_leg():
+    """The Cartesian layer with edge features against its diagonal workaround (every slice repeated F times, the frequencies tiled S
+    times: the same function), on the benchmark's graph."""
+    from fsw_gnn_amd import FSW_conv
+    n, E, d = bench.N_NODES, bench.N_EDGES, bench.D_FEAT
+    S, F, D = args.slices, args.freqs, args.edge_features
+    x, ei = bench.make_inputs(n, E, dev)
+    torch.manual_seed(7)
+    ef = torch.randn((E, D), device=dev)
+    cart = FSW_conv(d, d, edgefeat_dim=D, embed_slices=S, embed_freqs=F, cartesian_edge_features=True, learnable_embedding=args.train, device=dev)
+    diag = FSW_conv(d, d, edgefeat_dim=D, embed_dim=S * F + 1, learnable_embedding=args.train, device=dev)
+    sd = cart.state_dict()
+    sd["fsw_embed.projVecs"] = sd["fsw_embed.projVecs"].repeat_interleave(F, dim=0)
+    sd["fsw_embed.freqs"] = sd["fsw_embed.freqs"].repeat(S)
+    diag.load_state_dict(sd)
+    layers = {"cart": cart, "diag": diag}
+    print("conv with %d edge features, config 3: n=%d E=%d in=out=%d S=%d F=%d (K = %d)%s" % (
+        D, n, E, d, S, F, S * F + 1, ", training step" if args.train else ""))
+    with torch.no_grad():
+        ya, yb = cart(x, ei, ef), diag(x, ei, ef)
+        print("cart against diag: %.2e" % float((ya - yb).norm() / yb.norm()))
+        del ya, yb
+    if args.train:
+        xg = x.clone().requires_grad_(True)
+        G = torch.randn((n, d), device=dev)
+    for run in range(args.runs):
+        for form, layer in layers.items():
+            if args.train:
+                def step():
+                    layer.zero_grad(set_to_none=True)
+                    xg.grad = None
+                    layer(xg, ei, ef).backward(G)
+                for _ in range(args.warmup if run == 0 else 1):
+                    step()
+                ms = bench.timed_ms(step, args.steps, dev)
+            else:
+                with torch.no_grad():
+                    for _ in range(args.warmup if run == 0 else 1):
+                        layer(x, ei, ef)
+                    ms = bench.timed_ms(lambda: layer(x, ei, ef), args.reps, dev)
+            print("run %d  %-8s %8.3f ms" % (run, form, ms), flush=True)
 
 
 def conv_leg():
@@ -539,6 +620,12 @@ if args.giant:
     sys.exit(0)
 if args.hub:
     hub_leg()
+    sys.exit(0)
+if args.edge_keys:
+    edge_keys_leg()
+    sys.exit(0)
+if args.conv and args.edge_features > 0:
+    conv_edge_leg()
     sys.exit(0)
 if args.conv:
     conv_leg()
