@@ -276,8 +276,267 @@ __device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c)
   c = (__bf16)(r - (float)b);
 }
 
+// With the weights as the A operand and X as the B operand of v_mfma_f32_32x32x16_bf16 the accumulators hold C^T: lane (fr, fh) owns
+// row fr of the 32 x 32 block and its columns 8 q + 4 fh + {0..3} in registers 4 q .. 4 q + 3.  Stored like that, one 16-byte store
+// instruction touches 32 rows with 32 bytes each.  quad_transpose exchanges the four register quads among the four lanes of a quad
+// (rows 4 a + b, b = 0..3; two butterfly stages of quad_perm DPP moves, no LDS): afterwards lane (4 a + b, fh) holds in registers
+// 4 k .. 4 k + 3 the columns 8 b + 4 fh + {0..3} of row 4 a + k, so store instruction k writes eight whole 128-byte rows.
+template <int CTRL>
+__device__ __forceinline__ float quad_perm(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ void quad_transpose(f32x16& acc, int lane) {
+  const bool b0 = lane & 1, b1 = lane & 2;
+#pragma unroll
+  for (int s = 0; s < 4; s += 2)                      // lanes b and b ^ 1: quad_perm [1, 0, 3, 2]
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float lo = acc[4 * s + j], hi = acc[4 * s + 4 + j];
+      const float got = quad_perm<0xB1>(b0 ? lo : hi);
+      acc[4 * s + j] = b0 ? got : lo;
+      acc[4 * s + 4 + j] = b0 ? hi : got;
+    }
+#pragma unroll
+  for (int s = 0; s < 2; ++s)                         // lanes b and b ^ 2: quad_perm [2, 3, 0, 1]
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float lo = acc[4 * s + j], hi = acc[4 * s + 8 + j];
+      const float got = quad_perm<0x4E>(b1 ? lo : hi);
+      acc[4 * s + j] = b1 ? got : lo;
+      acc[4 * s + 8 + j] = b1 ? hi : got;
+    }
+}
+// the value of lane K of every quad
+template <int K>
+__device__ __forceinline__ int quad_bcast(int v) { return __builtin_amdgcn_mov_dpp(v, K * 0x55, 0xF, 0xF, true); }
+
+template <int KS, bool FAST>
+__global__ void __launch_bounds__(768) k_project_bf3(const float* __restrict__ X, int64_t n, int d, int64_t ldx,
+                                                     const float* __restrict__ V, int S, int64_t ldv,
+                                                     float* __restrict__ Xp, int64_t ldp, int32_t* __restrict__ stats,
+                                                     float* __restrict__ x_copy, int64_t ld_copy,
+                                                     const float* __restrict__ W2, int H2, int64_t ldw2,
+                                                     const float* __restrict__ b2, float* __restrict__ Y2, int64_t ldy2,
+                                                     const int32_t* __restrict__ row_map, int64_t ntiles, int nslab_waves,
+                                                     int nsl1, int y2_vec) {
+  // Operand roles: the weight planes are the matrix instruction's A operand and the X planes its B operand (both register layouts
+  // are the same shape: lane (fr, fh) holds eight k-values of index fr), so the accumulators hold C^T and a wave stores its
+  // 32 x 32 block of C straight from them: quad_transpose, then four 16-byte stores per lane, each instruction eight whole
+  // 128-byte rows.  No staging tile in LDS, and the stores of a wave do not wait for the workgroup's barrier.
+  // FAST (the launcher's choice): every wave of the grid has a slab, n is a multiple of 32 and every Y2 slab lies inside H2 with
+  // 16-byte aligned rows, so each wave issues exactly four 16-byte stores per tile in straight-line code.  Only then is the wait
+  // for the next tile's X loads at the top of the next iteration a counted one (vmcnt(4)) that leaves these stores in flight:
+  // wherever a store sits behind a condition the compiler has to assume the path without it and drains everything (vmcnt(0)).
+  // KS <= 8 (d <= 128): up to 12 slab waves keep their whole slab of [V; W2] in registers (24 KS registers each); d <= 256 runs
+  // k_project_bf3_staged below.
+  static_assert(KS <= 8, "k_project_bf3: d <= 128");
+  constexpr int B3_LD = 16 * KS + 8;
+  constexpr int NQ = 3;                   // float4 of an X tile per thread (32 rows x 4 KS float4 over >= 384 threads)
+  // LDS: A planes [2][3][32][B3_LD] bf16 | bias per column of the workgroup's slabs [nslab_waves][32] float
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  typedef __bf16 (*APlanes)[3][BS_ROWS][B3_LD];
+  APlanes As = reinterpret_cast<APlanes>(smem);
+  float* btab = reinterpret_cast<float*>(smem + sizeof(__bf16) * 2 * 3 * BS_ROWS * B3_LD);
+
+  const int lane = lane_id();
+  // wave-uniform, and through readfirstlane the compiler knows it: slab, second and the output block's address stay scalar
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fr = lane & 31, fh = lane >> 5;
+  // slabs 0 .. nsl1-1 cover the S projection columns, the following slabs the H2 columns of the second block
+  // (each block starts on a slab boundary so that the 16-byte stores of both are aligned)
+  const int slab = blockIdx.y * nslab_waves + wv;
+  const int nsl2 = (H2 + 31) >> 5;
+  const bool slab_active = FAST || (wv < nslab_waves && slab < nsl1 + nsl2);
+  const bool second = slab >= nsl1;
+  const int c = second ? (slab - nsl1) * 32 + fr : slab * 32 + fr;       // column inside its block
+  const bool col_ok = slab_active && (second ? c < H2 : c < S);
+
+  // weight slab as MFMA A operands: lane (fr, fh), k-step s holds W[c][16 s + 8 fh + j], j = 0..7, in three planes
+  bf16x8 bw[3][KS];
+  {
+    const float* wrow = col_ok ? (second ? W2 + (int64_t)c * ldw2 : V + (int64_t)c * ldv) : nullptr;
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = 16 * s + 8 * fh + j;
+        const float v = (wrow && k < d) ? wrow[k] : 0.f;
+        __bf16 h1, h2, h3;
+        split3(v, h1, h2, h3);
+        bw[0][s][j] = h1;
+        bw[1][s][j] = h2;
+        bw[2][s][j] = h3;
+      }
+  }
+  // bias per column of the slab (zeros for the Xp slabs) in LDS: a lane reads the float4 of its four columns once per tile, right
+  // before its stores, so no register holds it across the matrix phase
+  if (wv < nslab_waves && fh == 0) btab[wv * 32 + fr] = (col_ok && second && b2) ? b2[c] : 0.f;
+
+  for (int i = threadIdx.x; i < 2 * 3 * BS_ROWS * B3_LD / 2; i += blockDim.x) reinterpret_cast<uint32_t*>(smem)[i] = 0u;   // k padding
+  __syncthreads();
+
+  const int d4 = d >> 2;
+  const int per_tile = BS_ROWS * d4;
+  // i / d4, i / w1, i / w2 for the element indices i < 32 * 96 of a tile: multiply-shift instead of a division by a run-time value
+  // (~35 instructions each, eleven of them per thread and tile: the s_memtime stamps of tools/exp_project_stamps.py put the address
+  // arithmetic of the load / split / write-out phases at 46 % of a tile).  Exact for i * divisor < 2^20.
+  auto magic = [](int dv) { return dv > 0 ? (unsigned)(((1u << 20) + dv - 1) / dv) : 0u; };
+  auto fdiv = [](int i, unsigned m) { return (int)(((unsigned)i * m) >> 20); };
+  const unsigned m_d4 = magic(d4);
+  int nonfinite = 0;
+  struct TileRegs {
+    float4 q[NQ];
+  };
+  auto load_tile = [&](int64_t tile, TileRegs& t) {
+    const int64_t row0 = tile * BS_ROWS;
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      t.q[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      const int i = threadIdx.x + u * blockDim.x;
+      if (i < per_tile) {
+        const int r = fdiv(i, m_d4), c4 = i - r * d4;
+        if (row0 + r < n) t.q[u] = *reinterpret_cast<const float4*>(X + (row0 + r) * ldx + 4 * c4);
+      }
+    }
+  };
+  auto store_tile = [&](int buf, int64_t tile, const TileRegs& t) {
+    const int64_t row0 = tile * BS_ROWS;
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      const int i = threadIdx.x + u * blockDim.x;
+      if (i < per_tile) {
+        const int r = fdiv(i, m_d4), c4 = i - r * d4;
+        const float v[4] = {t.q[u].x, t.q[u].y, t.q[u].z, t.q[u].w};
+        bf16x4 p1, p2, p3;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          nonfinite |= !(fabsf(v[j]) <= 3.402823466e38f);
+          __bf16 h1, h2, h3;
+          split3(v[j], h1, h2, h3);
+          p1[j] = h1;
+          p2[j] = h2;
+          p3[j] = h3;
+          if (blockIdx.y == 0 && x_copy && row0 + r < n) x_copy[(row0 + r) * ld_copy + 4 * c4 + j] = v[j];
+        }
+        *reinterpret_cast<bf16x4*>(&As[buf][0][r][4 * c4]) = p1;
+        *reinterpret_cast<bf16x4*>(&As[buf][1][r][4 * c4]) = p2;
+        *reinterpret_cast<bf16x4*>(&As[buf][2][r][4 * c4]) = p3;
+      }
+    }
+  };
+  // Y2 row of tile row fr: every lane reads its own entry of the row map (identity without one), one tile ahead
+  const bool use_map = row_map && slab_active && second;
+  auto load_rmap = [&](int64_t tile) {
+    const int64_t r = tile * BS_ROWS + fr;
+    return (use_map && r < n) ? row_map[r] : (int)r;
+  };
+
+  // software pipeline, two tiles deep: registers hold tile t+1 (loaded during iteration t-1) and go to LDS at the top
+  // of iteration t; the HBM loads of tile t+2 are issued right after and have the whole iteration to land.  One barrier
+  // per tile orders the double-buffered A planes; a wave's output stores are its own business.
+  int64_t tile = blockIdx.x;
+  TileRegs tr;
+  int rm_next = 0;
+  if (tile < ntiles) {
+    rm_next = load_rmap(tile);
+    load_tile(tile, tr);
+    store_tile(0, tile, tr);
+  }
+  if (tile + gridDim.x < ntiles) load_tile(tile + gridDim.x, tr);
+  __syncthreads();
+  int buf = 0;                                           // A buffer of the current tile
+#if FSW_PROJECT_STAMPS
+  unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long stamp_last = clock64();
+#endif
+  // (written out inline: the same statements through two lambdas -- next tile in, matrix block -- compiled to a loop that measured
+  // 0.70-0.72 ms against 0.65-0.68 ms for this one)
+  for (; tile < ntiles; tile += gridDim.x) {
+    const int64_t next = tile + gridDim.x, next2 = next + gridDim.x;
+    const int rm = rm_next;
+    if (next < ntiles) store_tile(buf ^ 1, next, tr);
+    FSW_STAMP(0);                                        // waited for the tile's loads, split, wrote the A planes
+    // the map entry goes out in front of the X loads: the wait at the top of the next iteration covers it and stays a counted one
+    // (this tile's output stores are younger than both)
+    if (next < ntiles) rm_next = load_rmap(next);
+    if (next2 < ntiles) load_tile(next2, tr);
+    FSW_STAMP(1);                                        // loads of tile t + 2 issued
+    if (slab_active) {
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      if (!(FSW_PROJECT_ABL & 1)) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&As[buf][0][fr][16 * s + 8 * fh]);
+          const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(&As[buf][1][fr][16 * s + 8 * fh]);
+          const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(&As[buf][2][fr][16 * s + 8 * fh]);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[0][s], a3, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[1][s], a2, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[2][s], a1, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[0][s], a2, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[1][s], a1, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[0][s], a1, acc, 0, 0, 0);
+        }
+      }
+      FSW_STAMP(2);                                      // matrix instructions issued
+      // registers 4 k .. 4 k + 3 now: row 4 (fr >> 2) + k of the tile, columns 8 (fr & 3) + 4 fh + {0..3} of the slab
+      quad_transpose(acc, lane);
+      const int cq = 8 * (fr & 3) + 4 * fh;
+      const float4 b = *reinterpret_cast<const float4*>(btab + wv * 32 + cq);
+      const int64_t grow = tile * BS_ROWS + (fr & ~3);
+      const int rmk[4] = {quad_bcast<0>(rm), quad_bcast<1>(rm), quad_bcast<2>(rm), quad_bcast<3>(rm)};   // Y2 rows of the quad's tile rows
+      const int cc = (second ? (slab - nsl1) * 32 : slab * 32) + cq;
+      float* const out = second ? Y2 : Xp;
+      const int64_t ldo = second ? ldy2 : ldp;
+      if (FAST && !(FSW_PROJECT_ABL & 2)) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int64_t row = second ? (int64_t)rmk[k] : grow + k;
+          *reinterpret_cast<float4*>(out + row * ldo + cc) =
+              make_float4(acc[4 * k] + b.x, acc[4 * k + 1] + b.y, acc[4 * k + 2] + b.z, acc[4 * k + 3] + b.w);
+        }
+      } else if (!(FSW_PROJECT_ABL & 2)) {
+        // Xp rows are padded to ldp >= 32 ceil(S/32): all 32 columns of the slab are stored, exact zeros past S
+        const bool vec_ok = !second || (y2_vec && cc + 3 < H2);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (grow + k >= n) continue;
+          float* prow = out + (second ? (int64_t)rmk[k] : grow + k) * ldo;
+          const float e[4] = {acc[4 * k] + b.x, acc[4 * k + 1] + b.y, acc[4 * k + 2] + b.z, acc[4 * k + 3] + b.w};
+          if (vec_ok) {
+            *reinterpret_cast<float4*>(prow + cc) = make_float4(e[0], e[1], e[2], e[3]);
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (cc + j < H2) prow[cc + j] = e[j];
+          }
+        }
+      }
+      FSW_STAMP(3);                                      // output stores issued from the accumulators
+    }
+    __syncthreads();
+    FSW_STAMP(4);                                        // barrier (the next tile's A planes are complete, this tile's are free)
+#if FSW_PROJECT_STAMPS
+    stamp_sum[7] += 1;
+#endif
+    buf ^= 1;
+  }
+  if (stats && nonfinite) atomicOr(&stats[FSW_STAT_FLAGS], FSW_FLAG_X_NONFINITE);
+#if FSW_PROJECT_STAMPS
+  if (lane == 0 && blockIdx.x < 1024 && blockIdx.y == 0 && wv < 12)
+    for (int i = 0; i < 8; ++i) g_proj_stamps[blockIdx.x][wv][i] += stamp_sum[i];
+#endif
+}
+
+// ---- the same kernel with the C tile staged through LDS: 128 < d <= 256 (KS = 16) ---------------------------------------------
+// At KS = 16 the weight slab takes 192 of the 256 registers and half of the workgroup's waves have no slab: they only move X and,
+// in this form, share the write-out of the C tile, which the slab waves leave in an LDS staging tile (sixteen 4-byte LDS writes
+// per lane, read back as float4 by all waves behind the barrier, whole rows to global memory).  Storing from the accumulators as
+// above puts the whole store on the slab waves, the critical path of a tile, and the kernel no longer fits its registers (72 bytes
+// of scratch): 1.57-1.59 against 1.50-1.52 ms per million rows at d = 256.  So this width keeps the staged form.
 template <int KS>
-__global__ void __launch_bounds__(KS <= 8 ? 768 : 512) k_project_bf3(const float* __restrict__ X, int64_t n, int d, int64_t ldx,
+__global__ void __launch_bounds__(KS <= 8 ? 768 : 512) k_project_bf3_staged(const float* __restrict__ X, int64_t n, int d, int64_t ldx,
                                                      const float* __restrict__ V, int S, int64_t ldv,
                                                      float* __restrict__ Xp, int64_t ldp, int32_t* __restrict__ stats,
                                                      float* __restrict__ x_copy, int64_t ld_copy,
@@ -491,13 +750,15 @@ __global__ void __launch_bounds__(KS <= 8 ? 768 : 512) k_project_bf3(const float
 // With one or two 32-column slabs the workgroup kernel above has one or two wavefronts on the matrix pipe and six helpers, one
 // workgroup per CU, and a barrier per 32 rows: 0.24 ms for 32 slices of the 1M x 128 input, which it only has to read once (0.1 ms).
 // Here every WAVEFRONT is on its own: it keeps the slab's three bf16 planes in registers, reads its 32-row tile of X straight from
-// global memory in the matrix instruction's A layout (lane (r, h), k-step s: X[row0 + r][16 s + 8 h .. + 7] = two 16-byte loads; a
-// 64-byte segment per row and k-step over the two h lanes), splits it in registers and stores C from the accumulators (two whole
-// 128-byte lines per instruction).  No LDS, no barrier; blockIdx.y = slab.
+// global memory in the matrix instruction's operand layout (lane (r, h), k-step s: X[row0 + r][16 s + 8 h .. + 7] = two 16-byte
+// loads; a 64-byte segment per row and k-step over the two h lanes), splits it in registers and stores C from the accumulators.
+// As in k_project_bf3 the weights are the A operand and X the B operand and the block goes out after quad_transpose: four 16-byte
+// stores per lane, eight whole 128-byte rows each, instead of sixteen 4-byte ones (xp_vec = 0, rows of Xp not 16-byte aligned:
+// scalar stores of the same entries).  No LDS, no barrier; blockIdx.y = slab.
 template <int KS>
 __global__ void __launch_bounds__(256, 2) k_project_narrow(const float* __restrict__ X, int64_t n, int d, int64_t ldx,
                                                            const float* __restrict__ V, int S, int64_t ldv, float* __restrict__ Xp,
-                                                           int64_t ldp, int32_t* __restrict__ stats, int64_t ntiles) {
+                                                           int64_t ldp, int32_t* __restrict__ stats, int64_t ntiles, int xp_vec) {
   const int lane = lane_id();
   const int fr = lane & 31, fh = lane >> 5;
   const int slab = blockIdx.y;
@@ -547,23 +808,34 @@ __global__ void __launch_bounds__(256, 2) k_project_narrow(const float* __restri
         a2[j] = h2;
         a3[j] = h3;
       }
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, bw[0][s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bw[1][s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[2][s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bw[0][s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[1][s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bw[0][s], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[0][s], a3, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[1][s], a2, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[2][s], a1, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[0][s], a2, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[1][s], a1, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw[0][s], a1, acc, 0, 0, 0);
     }
+    // registers 4 k .. 4 k + 3 now: row 4 (fr >> 2) + k of the tile, columns 8 (fr & 3) + 4 fh + {0..3} of the slab
+    quad_transpose(acc, lane);
+    float* prow = Xp + (row0 + (fr & ~3)) * ldp + slab * 32 + 8 * (fr & 3) + 4 * fh;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int64_t R = row0 + (r & 3) + 8 * (r >> 2) + 4 * fh;   // C/D map of the 32x32 MFMA
-      if (R < n) Xp[R * ldp + c] = acc[r];
+    for (int k = 0; k < 4; ++k, prow += ldp) {
+      if (row0 + (fr & ~3) + k >= n) continue;
+      if (xp_vec) {
+        *reinterpret_cast<float4*>(prow) = make_float4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) prow[j] = acc[4 * k + j];
+      }
     }
   }
   if (stats && nonfinite) atomicOr(&stats[FSW_STAT_FLAGS], FSW_FLAG_X_NONFINITE);
 }
 
-static size_t bf3_lds_bytes(int nwaves, int ks, int cbufs) {
+static size_t bf3_lds_bytes(int nwaves, int ks) {
+  return sizeof(__bf16) * 2 * 3 * BS_ROWS * (16 * ks + 8) + sizeof(float) * nwaves * 32;   // A planes | bias table
+}
+static size_t bf3_staged_lds_bytes(int nwaves, int ks, int cbufs) {
   return sizeof(__bf16) * 2 * 3 * BS_ROWS * (16 * ks + 8) + sizeof(float) * cbufs * BS_ROWS * (nwaves * 32 + 4) + sizeof(int) * 3 * BS_ROWS;
 }
 
@@ -594,9 +866,10 @@ static int project_launch(const float* X, int64_t n, int d, int64_t ldx, const f
     if (!exact && S <= FSW_PROJECT_NARROW_MAX && H2 == 0 && !x_copy && d % 16 == 0 && d <= 128 && ldp >= (int64_t)nsl1 * 32) {
       const int64_t ntiles = ceil_div(n, BS_ROWS);
       dim3 grid((unsigned)std::min<int64_t>(ceil_div(ntiles, 4), 512), (unsigned)nsl1);   // two workgroups of four wavefronts per CU
-      if (d <= 32) k_project_narrow<2><<<grid, 256, 0, stream>>>(X, n, d, ldx, V, S, ldv, Xp, ldp, stats, ntiles);
-      else if (d <= 64) k_project_narrow<4><<<grid, 256, 0, stream>>>(X, n, d, ldx, V, S, ldv, Xp, ldp, stats, ntiles);
-      else k_project_narrow<8><<<grid, 256, 0, stream>>>(X, n, d, ldx, V, S, ldv, Xp, ldp, stats, ntiles);
+      const int xp_vec = (ldp % 4 == 0 && (uintptr_t)Xp % 16 == 0) ? 1 : 0;
+      if (d <= 32) k_project_narrow<2><<<grid, 256, 0, stream>>>(X, n, d, ldx, V, S, ldv, Xp, ldp, stats, ntiles, xp_vec);
+      else if (d <= 64) k_project_narrow<4><<<grid, 256, 0, stream>>>(X, n, d, ldx, V, S, ldv, Xp, ldp, stats, ntiles, xp_vec);
+      else k_project_narrow<8><<<grid, 256, 0, stream>>>(X, n, d, ldx, V, S, ldv, Xp, ldp, stats, ntiles, xp_vec);
       FSW_LAUNCH_CHECK();
       return 0;
     }
@@ -607,7 +880,6 @@ static int project_launch(const float* X, int64_t n, int d, int64_t ldx, const f
     const int64_t ntiles = ceil_div(n, BS_ROWS);
     dim3 grid((unsigned)std::min<int64_t>(ntiles, 256), (unsigned)ngroups);
     const int threads = std::max(nwaves, 8) * 64;
-    constexpr int cbufs = 2;   // C staging tiles: double buffered
     if (exact) {
       // FSW_PROJECT_EXACT_FP32=1: exact-fp32 MFMA kernel instead of bf16x3 (same accuracy class, 2.7x the matrix cycles)
 #define FSW_LAUNCH_BS(KQ)                                                                                                   \
@@ -622,18 +894,45 @@ static int project_launch(const float* X, int64_t n, int d, int64_t ldx, const f
                   "fsw_project: Xp must be 16-byte aligned with ldp >= 32*ceil(S/32), ldp %% 4 == 0");
       const int y2_vec = (H2 > 0 && ldy2 % 4 == 0 && (uintptr_t)Y2 % 16 == 0) ? 1 : 0;
       const int ks = d <= 32 ? 2 : d <= 64 ? 4 : d <= 128 ? 8 : 16;
-      const size_t lds = bf3_lds_bytes(nwaves, ks, cbufs);
-#define FSW_LAUNCH_BF3(KS)                                                                                                  \
+      if (ks == 16) {   // 128 < d <= 256: the staged kernel
+        constexpr int cbufs = 2;   // C staging tiles: double buffered
+        const size_t lds = bf3_staged_lds_bytes(nwaves, ks, cbufs);
+        FSW_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_project_bf3_staged<16>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_project_bf3_staged<16><<<grid, threads, lds, stream>>>(X, n, d, ldx, V, S, ldv, Xp, ldp, stats, x_copy, ld_copy, W2, H2, ldw2,
+                                                                 b2, Y2, ldy2, row_map, ntiles, nwaves, nsl1, y2_vec, cbufs);
+        FSW_LAUNCH_CHECK();
+        return 0;
+      }
+      const size_t lds = bf3_lds_bytes(nwaves, ks);
+      // Rows [r0, r0 + nr) with the kernel FAST or not.  Without a row map the Y2 rows are the X rows, so Y2 moves with r0.
+#define FSW_LAUNCH_BF3(KS, FAST, r0, nr)                                                                                    \
   do {                                                                                                                      \
-    FSW_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_project_bf3<KS>),                                     \
+    const int64_t r0_ = (r0), nr_ = (nr);                                                                                   \
+    const int64_t ntiles_ = ceil_div(nr_, BS_ROWS);                                                                         \
+    dim3 grid_((unsigned)std::min<int64_t>(ntiles_, 256), (unsigned)ngroups);                                               \
+    FSW_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_project_bf3<KS, FAST>),                               \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                               \
-    k_project_bf3<KS><<<grid, threads, lds, stream>>>(X, n, d, ldx, V, S, ldv, Xp, ldp, stats, x_copy, ld_copy, W2, H2, ldw2, \
-                                                      b2, Y2, ldy2, row_map, ntiles, nwaves, nsl1, y2_vec, cbufs);          \
+    k_project_bf3<KS, FAST><<<grid_, threads, lds, stream>>>(                                                               \
+        X + r0_ * ldx, nr_, d, ldx, V, S, ldv, Xp + r0_ * ldp, ldp, stats, x_copy ? x_copy + r0_ * ld_copy : nullptr, ld_copy, W2, H2, \
+        ldw2, b2, (Y2 && !row_map) ? Y2 + r0_ * ldy2 : Y2, ldy2, row_map ? row_map + r0_ : nullptr, ntiles_, nwaves, nsl1, y2_vec);   \
   } while (0)
-      if (ks == 2) FSW_LAUNCH_BF3(2);
-      else if (ks == 4) FSW_LAUNCH_BF3(4);
-      else if (ks == 8) FSW_LAUNCH_BF3(8);
-      else FSW_LAUNCH_BF3(16);
+      // The straight-line store path (k_project_bf3<KS, true>) takes the whole 32-row tiles when every wave of the grid has a slab
+      // (>= 8 slab waves per workgroup, all column groups full) and every Y2 slab is whole with 16-byte aligned rows; the general
+      // kernel takes the n % 32 rows that are left in a launch of its own, or everything.
+      const bool fast_ok = nwaves >= 8 && nslabs == ngroups * nwaves && (H2 == 0 || (H2 % 32 == 0 && y2_vec));
+      const int64_t n_fast = fast_ok ? n / BS_ROWS * BS_ROWS : 0;
+      if (n_fast > 0) {
+        if (ks == 2) FSW_LAUNCH_BF3(2, true, 0, n_fast);
+        else if (ks == 4) FSW_LAUNCH_BF3(4, true, 0, n_fast);
+        else FSW_LAUNCH_BF3(8, true, 0, n_fast);
+        FSW_LAUNCH_CHECK();
+      }
+      if (n_fast < n) {
+        if (ks == 2) FSW_LAUNCH_BF3(2, false, n_fast, n - n_fast);
+        else if (ks == 4) FSW_LAUNCH_BF3(4, false, n_fast, n - n_fast);
+        else FSW_LAUNCH_BF3(8, false, n_fast, n - n_fast);
+      }
 #undef FSW_LAUNCH_BF3
     }
     FSW_LAUNCH_CHECK();

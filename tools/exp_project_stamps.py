@@ -24,17 +24,17 @@ reps = 5
 ms = bench.timed_ms(lambda: conv.fsw_embed.prepare(x, graph, linear2=lin2), reps, dev)   # timed_ms runs reps + 1 calls
 L.fsw_debug_project_stamps(buf)
 a = np.ctypeslib.as_array(buf).reshape(1024, 12, 8).astype(np.float64)
-names = ["0 wait loads + split + A planes", "1 issue loads t+2", "2 issue matrix instr", "3 drain acc -> staging", "4 barrier",
-         "5 staging -> output stores", "6 loop tail"]
+names = ["0 wait loads + split + A planes", "1 issue loads t+2", "2 issue matrix instr", "3 acc + bias -> output stores", "4 barrier"]
+NP = len(names)
 print("projection (instrumented): %.3f ms per call" % ms)
 for w in range(12):
     it = a[:, w, 7].sum()
     if it == 0:
         continue
-    per = a[:, w, :7].sum(axis=0) / it
-    print("wave %2d: %7.0f cycles per tile | " % (w, per.sum()) + "  ".join("%s %6.0f" % (names[i].split()[0], per[i]) for i in range(7)))
+    per = a[:, w, :NP].sum(axis=0) / it
+    print("wave %2d: %7.0f cycles per tile | " % (w, per.sum()) + "  ".join("%s %6.0f" % (names[i].split()[0], per[i]) for i in range(NP)))
 it = a[:, :, 7].sum()
-per = a[:, :, :7].sum(axis=(0, 1)) / it
+per = a[:, :, :NP].sum(axis=(0, 1)) / it
 print("all waves: %.0f cycles per tile iteration (s_memtime ticks)" % per.sum())
-for i in range(7):
+for i in range(NP):
     print("   %-34s %8.0f  %5.1f %%" % (names[i], per[i], 100.0 * per[i] / per.sum()))
