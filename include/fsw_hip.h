@@ -157,15 +157,29 @@ int fsw_graph_build_coalesced(const int64_t* recipients, const int64_t* senders,
  * from S on in the generic kernel, are left untouched (tests/test_hip_conv_fused.py).
  * x_copy (nullable): the kernel also stores the X rows it stages to x_copy[i*ld_copy + c] -- this is
  * the right half of FSW_conv's torch.cat((emb, vertex_features)) (reference fsw_conv.py:357-358),
- * written while X is on chip anyway instead of by a separate copy kernel.                          */
+ * written while X is on chip anyway instead of by a separate copy kernel.
+ * Non-finite and very large inputs.  A NaN or Inf in X[i, k] makes every entry of row i of Xp (and of Y2) non-finite, a NaN or Inf in
+ * V[j, k] every entry of column j; all other entries are what they would be without it.  Which non-finite value comes back is not
+ * specified: under bf16 x 3 an Inf becomes NaN (its second plane is Inf - Inf), and a finite magnitude above the largest bf16
+ * (about 3.39e38) rounds to Inf in the first plane and then does the same.  Only FSW_FLAG_X_NONFINITE reports it, and only for X.
+ * bf16 has fp32's exponent range, so scaling X by 2^a and V by 2^b scales every entry by exactly 2^(a+b) as long as no plane
+ * (down to 2^-18 of its entry) and no product leaves fp32's normal range.                                                     */
 int fsw_project_f32(const float* X, int64_t n, int d, int64_t ldx, const float* V, int S, int64_t ldv,
                     float* Xp, int64_t ldp, float* x_copy, int64_t ld_copy, int32_t* stats, fsw_stream_t stream);
 
 /* ---- C[M, N] = beta * C + A^T . B for tall row-major A [K, lda >= M], B [K, ldb >= N] (K in the millions, M x N at most 16 blocks
  * of 64 x 64): the weight-gradient shape of the backward pass -- gV = gXp^T . X (reference fsw_embedding.py:909-913 differentiated by
- * torch.autograd) and the first Linear layer's gW (fsw_conv.py:361).  Exact fp32 products and sums (v_mfma_f32_32x32x2_f32); the K
- * axis is split over the grid, the partial results are summed in a fixed order (no float atomics: bitwise reproducible).
- * workspace: fsw_gemm_tn_workspace_bytes(M, N).                                                                            */
+ * torch.autograd) and the first Linear layer's gW (fsw_conv.py:361).  bf16 x 3 like the projection (six v_mfma_f32_32x32x16_bf16 per
+ * 16 rows, fp32 accumulation); FSW_GEMM_TN_EXACT_FP32=1 in the environment selects exact fp32 products and sums
+ * (v_mfma_f32_32x32x2_f32) instead.  The K axis is split over the grid: G = min(512, max(1, K / 512)) workgroups, workgroup g takes
+ * the rows [g per, min((g + 1) per, K)) with per = ceil(K / G) rounded up to a multiple of 16 (of 2 in the exact form); the partial
+ * results are summed in a fixed order (no float atomics: bitwise reproducible, whatever the workspace held).
+ * K: any K >= 1 (K = 0 is refused, as are lda < M, ldb < N, ldc < N, a null pointer and more than 16 blocks).  beta = 0: C is not read.
+ * workspace: G * M * N * sizeof(float) bytes are used; fsw_gemm_tn_workspace_bytes(M, N) is that for G = 512, enough for every K.
+ * Non-finite and very large inputs: a NaN or Inf in A[k, m] makes every entry of row m of C non-finite, one in B[k, n] every entry
+ * of column n, all other entries are unaffected; under bf16 x 3 an Inf becomes NaN, and a finite magnitude above the largest bf16
+ * (about 3.39e38) rounds to Inf in the first plane and then does the same.  Scaling A by 2^a and B by 2^b scales C by exactly
+ * 2^(a+b) as long as no plane and no sum leaves fp32's normal range (tests/test_hip_dense_matrix.py).                          */
 size_t fsw_gemm_tn_workspace_bytes(int M, int N);
 int fsw_gemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t K, int M, int N, float* C, int64_t ldc, float beta,
                     void* workspace, size_t workspace_bytes, fsw_stream_t stream);
