@@ -7,4 +7,4 @@ All computation runs in hand-written HIP kernels (csrc/, libfsw_hip.so, C ABI in
 """
 from .fsw_embedding import FSW_embedding, segcumsum  # noqa: F401
 from .fsw_conv import FSW_conv, FSW_readout  # noqa: F401
-from .graph import CSRGraph, build_csr  # noqa: F401
+from .graph import CSRGraph, build_csr, import_csr  # noqa: F401

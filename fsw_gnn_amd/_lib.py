@@ -29,6 +29,7 @@ NUM_STATS = 8
 STAT_FLAGS, STAT_MAX_DEGREE, STAT_NUM_ZERO, STAT_NUM_REG, STAT_NUM_LDS, STAT_NUM_GLOBAL, STAT_NNZ, STAT_USER = 0, 1, 2, 3, 4, 5, 6, 7
 BIN_BLOCK_ROWS, MAX_ROW_CHUNKS = 2048, 256
 FLAG_INDEX_RANGE, FLAG_W_NONFINITE, FLAG_W_NEGATIVE, FLAG_X_NONFINITE = 1, 2, 4, 8
+FLAG_CSR_MALFORMED, FLAG_CSR_COL_ORDER, FLAG_W_NONUNIT = 16, 32, 64   # fsw_graph_import_csr
 
 c_i64, c_i32, c_f32, c_vp, c_sz = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
@@ -82,6 +83,9 @@ _SIGNATURES = {
     "fsw_graph_build": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "fsw_graph_build_two_level": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "fsw_graph_build_plan": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.c_int, ctypes.POINTER(c_i32)]),
+    "fsw_graph_import_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "fsw_graph_import_csr": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_i64, c_i64, c_i64, c_i64, c_f32, ctypes.c_int, ctypes.c_int,
+                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "fsw_project_f32": (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_vp, ctypes.c_int, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "fsw_gemm_tn_workspace_bytes": (c_sz, [ctypes.c_int, ctypes.c_int]),
     "fsw_gemm_tn_f32": (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_f32, c_vp, c_sz, c_vp]),

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from .coherence import minimize_mutual_coherence
 from .fsw_embedding import FSW_embedding, LinearSplitTallFn, LinearTallFn, GEMM_TN_MIN_ROWS
-from .graph import BuildHint, build_csr, build_csr_coalesced
+from .graph import BuildHint, build_csr, build_csr_coalesced, import_csr
 
 try:  # optional dependency, exactly the names the reference imports (fsw_conv.py:4-9)
     from torch_geometric.nn import MessagePassing as _Base
@@ -164,6 +164,60 @@ class FSW_conv(_Base):
         self.to(device=device, dtype=dtype)
 
     # ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _csr_adjacency(edge_index, num_vertices):
+        """None for an edge list [2, E]; for a CSR adjacency (row i lists the senders to vertex i, PyG's adj_t) the tuple
+        (rowptr, col, values or None, tensor_form), after the host-side checks of its shape and dtypes (no device is touched).
+        Two forms: a tuple (rowptr, col) -- structure only, unit weights, repeated columns are parallel edges -- and a torch.sparse_csr
+        tensor [n, n] whose values are the entries' weights (the edge multiplicities of the reference's coalesced adj)."""
+        if isinstance(edge_index, (tuple, list)):
+            assert len(edge_index) == 2 and all(torch.is_tensor(t) for t in edge_index), \
+                'a CSR adjacency in tuple form is (rowptr, col): two index tensors'
+            rowptr, col = edge_index
+            assert rowptr.dtype in (torch.int32, torch.int64) and col.dtype == rowptr.dtype, \
+                'rowptr and col of a CSR adjacency must both be int32 or both be int64 (got %s, %s)' % (rowptr.dtype, col.dtype)
+            assert rowptr.dim() == 1 and col.dim() == 1 and rowptr.numel() == num_vertices + 1, \
+                'a CSR adjacency (rowptr, col) needs rowptr of shape (num_vertices + 1,) and a 1-D col'
+            return rowptr, col, None, False
+        if torch.is_tensor(edge_index) and edge_index.layout != torch.strided:
+            assert edge_index.layout == torch.sparse_csr, \
+                "edge_index has the unsupported layout '%s': pass an edge list [2, E], a tuple (rowptr, col) or a torch.sparse_csr tensor [n, n]" % (edge_index.layout,)
+            assert edge_index.dim() == 2 and edge_index.dense_dim() == 0 and tuple(edge_index.shape) == (num_vertices, num_vertices), \
+                'a torch.sparse_csr adjacency must be 2-D [num_vertices, num_vertices] without batch dimensions'
+            if edge_index.requires_grad:
+                raise NotImplementedError("fsw_gnn_amd: gradients of the values of a torch.sparse_csr adjacency are not implemented")
+            return edge_index.crow_indices(), edge_index.col_indices(), edge_index.values(), True
+        return None
+
+    def build_graph_csr(self, csr, num_vertices, edge_features=None):
+        """CSRGraph of a CSR adjacency (_csr_adjacency) by graph.import_csr: no sort.  Self loops and 'gcn' weighting as build_graph
+        applies them to an edge list, with the same entries in the same places.  With edge features the adjacency is the
+        coalesced one (strictly increasing columns in every row); the loop's weight is added to an existing diagonal entry and its
+        feature row stays, a new diagonal entry carries zero features.  The tensor form reads the import's stats once (one extra
+        host wait) to drop the weight array of a unit adjacency, which then takes the unit kernels; the tuple form never waits.
+        cache_graph does not apply: a CSR adjacency is imported on every call."""
+        rowptr, col, vals, tensor_form = csr
+        sl = float(self.self_loop_weight) if self.self_loop_weight > 0 else 0.0
+        gcn = self.edge_weighting == 'gcn'
+        w = vals.detach().to(torch.float32).contiguous() if vals is not None else None
+        if edge_features is not None:
+            ef = edge_features.detach().reshape(col.numel(), -1).to(torch.float32)
+            graph = import_csr(rowptr, col, w, num_vertices, num_vertices, self_loop_weight=sl, gcn=gcn, strict_cols=True, want_slots=True)
+            if graph.w is None:                       # the kernels of the coalesced graph read a weight per entry
+                graph.w = torch.ones(graph.col.numel(), dtype=torch.float32, device=col.device)
+            if sl:
+                graph.ef = torch.zeros((graph.col.numel(), ef.shape[1]), dtype=torch.float32, device=ef.device)
+                graph.ef.index_copy_(0, graph.slot_of_edge[:ef.shape[0]].long(), ef)
+            else:
+                graph.ef = ef.contiguous() if ef.shape[0] else torch.zeros((1, ef.shape[1]), dtype=torch.float32, device=ef.device)
+            return graph
+        graph = import_csr(rowptr, col, w, num_vertices, num_vertices, self_loop_weight=sl, gcn=gcn,
+                           want_invperm=self._fusable() and not self.fsw_embed.cartesian_mode)
+        if tensor_form and not sl and not gcn:
+            if not (graph.read_stats()[_lib.STAT_FLAGS] & _lib.FLAG_W_NONUNIT):
+                graph.w = None
+        return graph
+
     def build_graph(self, edge_index, num_vertices, edge_features=None, chunk_rows=0):
         """edge_index [2, E] int64 (row 0 = sender, row 1 = recipient) -> CSRGraph.
 
@@ -224,8 +278,21 @@ class FSW_conv(_Base):
         return src, dst, w, ef
 
     def forward(self, vertex_features, edge_index, edge_features=None):
-        """vertex_features [n, in_channels], edge_index [2, E] long -> [n, out_channels] (fsw_conv.py:331-369)."""
+        """vertex_features [n, in_channels], edge_index [2, E] long -> [n, out_channels] (fsw_conv.py:331-369).
+
+        edge_index may also be a CSR adjacency whose row i lists the senders to vertex i (PyG's adj_t), imported without the sort
+        of the edge-list path: a tuple (rowptr, col) of int32 / int64 tensors (unit weights; repeated columns are parallel edges;
+        no host wait) or a torch.sparse_csr tensor [n, n] whose values are the entries' weights (one extra host wait: the import's
+        stats are read once so that a unit adjacency keeps the unit kernels).  edge_features are then [nnz, edgefeat_dim], aligned
+        with the CSR entries, and every row's columns must be strictly increasing.  Not with enable_slice_parallel /
+        enable_node_parallel; cache_graph does not apply (the adjacency is imported on every call)."""
         emb_mod = self.fsw_embed
+        csr = self._csr_adjacency(edge_index, vertex_features.size(0))
+        if csr is not None:
+            if getattr(self, '_node_parallel', False) or getattr(self, '_slice_parallel', None) is not None:
+                raise NotImplementedError("fsw_gnn_amd: a CSR adjacency under enable_slice_parallel / enable_node_parallel is not "
+                                          "implemented; pass the edge list")
+            return self._forward_csr(vertex_features, csr, edge_features)
         assert vertex_features.dtype == emb_mod.get_dtype(), 'vertex_features has incorrect dtype (expected %s, got %s)' % (emb_mod.get_dtype(), vertex_features.dtype)
         assert vertex_features.device == emb_mod.get_device(), 'vertex_features has incorrect device (expected %s, got %s)' % (emb_mod.get_device(), vertex_features.device)
         assert edge_index.device == emb_mod.get_device(), 'edge_index has incorrect device (expected %s, got %s)' % (emb_mod.get_device(), edge_index.device)
@@ -267,12 +334,18 @@ class FSW_conv(_Base):
         if emb_mod.cartesian_mode:
             return self._forward_cartesian(x, vertex_features, edge_index, needs_grad, edge_features)
         graph = self.build_graph(edge_index, n, edge_features if self.edgefeat_dim > 0 else None)
+        ef_in = edge_features.reshape(edge_index.shape[1], -1) if self.edgefeat_dim > 0 else None
+        return self._forward_graph(x, vertex_features, graph, needs_grad, ef_in)
+
+    def _forward_graph(self, x, vertex_features, graph, needs_grad, ef_in):
+        """The float32 diagonal-mode layer on a built (or imported) graph; ef_in: the edge-feature rows the graph was made from."""
+        emb_mod = self.fsw_embed
+        n = x.shape[0]
         E = self.embed_dim
         scale = self._message_scale
 
         if needs_grad:
             # training path: differentiable embedding (HIP forward + backward kernels), the tail through torch autograd
-            ef_in = edge_features.reshape(edge_index.shape[1], -1) if self.edgefeat_dim > 0 else None
             emb = emb_mod.embed_autograd(x, graph, edge_feat=ef_in)
             return self._tail(emb, vertex_features)
 
@@ -319,7 +392,47 @@ class FSW_conv(_Base):
             emb_mod.embed_into(x, graph, buf, out_scale=scale, x_copy=xc)   # X stored by the projection kernel
         return self._tail_buffer(buf)
 
-    def _forward_cartesian(self, x, vertex_features, edge_index, needs_grad, edge_features=None):
+    def _forward_csr(self, vertex_features, csr, edge_features):
+        """forward() for a CSR adjacency: the argument checks of the edge-list call, then the same paths on the imported graph."""
+        emb_mod = self.fsw_embed
+        rowptr, col, vals, _ = csr
+        nnz = col.numel()
+        assert vertex_features.dtype == emb_mod.get_dtype(), 'vertex_features has incorrect dtype (expected %s, got %s)' % (emb_mod.get_dtype(), vertex_features.dtype)
+        assert vertex_features.device == emb_mod.get_device(), 'vertex_features has incorrect device (expected %s, got %s)' % (emb_mod.get_device(), vertex_features.device)
+        assert rowptr.device == emb_mod.get_device() and col.device == emb_mod.get_device(), 'the CSR adjacency is on the wrong device (expected %s)' % (emb_mod.get_device(),)
+        if self.edgefeat_dim > 0:
+            assert edge_features is not None, 'Edge features must be provided since edgefeat_dim > 0'
+            if self.edgefeat_dim == 1:
+                assert tuple(edge_features.shape) in {(nnz,), (nnz, 1)}, 'edge_features should have the shape (nnz, edegfeat_dim) (or optionally (nnz,) in the case edgefeat_dim=1)'
+            else:
+                assert tuple(edge_features.shape) == (nnz, self.edgefeat_dim), 'edge_features must have the shape (nnz, edgefeat_dim), aligned with the CSR entries'
+            assert edge_features.dtype == vertex_features.dtype and edge_features.device == vertex_features.device
+        else:
+            assert edge_features is None, 'Edge features should not be provided since edgefeat_dim = 0'
+        if vertex_features.device.type != 'cuda':
+            raise RuntimeError("fsw_gnn_amd: forward needs tensors on a HIP device ('cuda'); there is no CPU path")
+        n = vertex_features.size(0)
+        if n == 0:
+            return torch.zeros((0, self.out_channels), dtype=vertex_features.dtype, device=vertex_features.device)
+        has_ef = self.edgefeat_dim > 0
+        if emb_mod.get_dtype() == torch.float64:
+            # float64 layers run the generic kernels on the reference's coalesced COO adjacency: the entries as an edge list, by torch ops
+            crow = rowptr.long()
+            rec = torch.repeat_interleave(torch.arange(n, device=crow.device, dtype=torch.int64), crow[1:] - crow[:-1])
+            assert rec.numel() == nnz, 'CSR adjacency is malformed (crow_indices must start at 0, be non-decreasing and end at nnz)'
+            adj, x_edge = self.adjacency_coo(torch.stack((col.long(), rec)), edge_features if has_ef else None, n, vertex_features.dtype,
+                                             edge_w=vals)
+            return self._tail(emb_mod(vertex_features, W=adj, X_edge=x_edge, graph_mode=True), vertex_features)
+        needs_grad = torch.is_grad_enabled() and (vertex_features.requires_grad or any(p.requires_grad for p in self.parameters())
+                                                  or (edge_features is not None and edge_features.requires_grad))
+        x = vertex_features.contiguous()
+        graph = self.build_graph_csr(csr, n, edge_features if has_ef else None)
+        ef_in = edge_features.reshape(nnz, -1) if has_ef else None
+        if emb_mod.cartesian_mode:
+            return self._forward_cartesian(x, vertex_features, None, needs_grad, edge_features, graph=graph, ef_in=ef_in)
+        return self._forward_graph(x, vertex_features, graph, needs_grad, ef_in)
+
+    def _forward_cartesian(self, x, vertex_features, edge_index, needs_grad, edge_features=None, graph=None, ef_in=None):
         """float32 layer with a Cartesian embedding (embed_slices x embed_freqs): training through _CartEmbedFn and the usual tail;
         inference through ONE kernel for the embedding and the first Linear layer (csrc/conv_fused.hip: k_conv_fused_cart) when the
         configuration is fusable and no row has more than REG_MAX_DEG neighbours, else embed_cartesian_into + the torch tail.
@@ -329,9 +442,10 @@ class FSW_conv(_Base):
         emb_mod = self.fsw_embed
         n = x.shape[0]
         has_ef = self.edgefeat_dim > 0
-        graph = self.build_graph(edge_index, n, edge_features if has_ef else None)
-        if needs_grad:
+        if graph is None:                            # an edge list; a CSR adjacency comes with its imported graph (_forward_csr)
+            graph = self.build_graph(edge_index, n, edge_features if has_ef else None)
             ef_in = edge_features.reshape(edge_index.shape[1], -1) if has_ef else None
+        if needs_grad:
             return self._tail(emb_mod.embed_cartesian_autograd(x, graph, edge_feat=ef_in), vertex_features)
         scale = self._message_scale
         prepared = emb_mod.prepare_cartesian(x, graph)
@@ -389,13 +503,13 @@ class FSW_conv(_Base):
         _lib.check(rc, "fsw_conv_fused_cart_f32")
         return next_module
 
-    def adjacency_coo(self, edge_index, edge_features, num_vertices, dtype):
+    def adjacency_coo(self, edge_index, edge_features, num_vertices, dtype, edge_w=None):
         """Coalesced COO adjacency adj[recipient, sender] and edge-feature tensor exactly as the reference builds them
         (FSW_conv.edge_index_to_adj, fsw_conv.py:384-447): parallel edges summed, optional self loops, 'gcn' weighting by the
         weighted in-degrees; differentiable in edge_features (torch's coalesce)."""
         dev = edge_index.device
         inds = edge_index.flip(0)
-        vals = torch.ones(edge_index.shape[1], device=dev, dtype=dtype)
+        vals = torch.ones(edge_index.shape[1], device=dev, dtype=dtype) if edge_w is None else edge_w.to(dtype)   # edge_w: a weight per edge
         if self.self_loop_weight > 0:
             loops = torch.arange(num_vertices, device=dev).reshape(1, num_vertices).repeat(2, 1)
             inds = torch.cat((inds, loops), dim=1)
@@ -766,11 +880,28 @@ class FSW_conv(_Base):
 
 @register_pooling('fsw_readout')
 class FSW_readout(FSW_conv):
-    def forward(self, vertex_features, graph_index=None, batch_size=None):
-        """Global pooling: every vertex sends to the node of its graph (reference fsw_conv.py:451-517)."""
+    def forward(self, vertex_features, graph_index=None, batch_size=None, ptr=None):
+        """Global pooling: every vertex sends to the node of its graph (reference fsw_conv.py:451-517).
+
+        ptr [batch_size + 1] int32 / int64 (PyG's batch.ptr) replaces graph_index: graph g owns the vertices ptr[g] .. ptr[g + 1] - 1.
+        The segments are imported as they are (graph.import_csr with col[e] = e): no sort, no host wait for batch_size."""
         assert self.edgefeat_dim == 0, 'edgefeat_dim should equal zero in a global readout layer'
         num_vertices = vertex_features.shape[0]
-        if graph_index is None:
+        if ptr is not None:
+            assert graph_index is None, 'give either graph_index or ptr, not both'
+            assert torch.is_tensor(ptr) and ptr.dtype in (torch.int32, torch.int64), 'ptr must be an int32 or int64 tensor'
+            assert ptr.dim() == 1 and ptr.numel() >= 1, 'ptr should be of shape (batch_size + 1,)'
+            assert batch_size is None or batch_size == ptr.numel() - 1, 'batch_size must equal ptr.numel() - 1'
+            batch_size = ptr.numel() - 1
+            if self.fsw_embed.get_dtype() == torch.float64 and batch_size > 0:
+                # float64 layers take the reference's COO adjacency below: graph_index from ptr by torch ops
+                p64 = ptr.long()
+                graph_index = torch.repeat_interleave(torch.arange(batch_size, device=ptr.device, dtype=torch.int64), p64[1:] - p64[:-1])
+                assert graph_index.numel() == num_vertices, 'ptr must start at 0, be non-decreasing and end at num_vertices'
+                ptr = None
+            else:
+                graph_index = ptr                     # for the device check below
+        elif graph_index is None:
             assert batch_size is None, 'batch_size must be None when graph_index is None'
             graph_index = torch.zeros(num_vertices, device=vertex_features.device, dtype=torch.int64)
         else:
@@ -789,7 +920,10 @@ class FSW_readout(FSW_conv):
             adj = torch.sparse_coo_tensor(torch.stack((graph_index, src)), torch.ones(num_vertices, dtype=torch.float64, device=src.device),
                                           size=(batch_size, num_vertices)).coalesce()
             return self._mlp_or_dim_reduct(emb_mod(vertex_features, W=adj, graph_mode=True))
-        graph = build_csr(graph_index.contiguous(), src, None, batch_size, num_vertices)
+        if ptr is not None:
+            graph = import_csr(ptr, None, None, batch_size, num_vertices)
+        else:
+            graph = build_csr(graph_index.contiguous(), src, None, batch_size, num_vertices)
         needs_grad = torch.is_grad_enabled() and (vertex_features.requires_grad or any(p.requires_grad for p in self.parameters()))
         if emb_mod.cartesian_mode:
             # the same two embedding calls as FSW_conv's: segments of up to 2048 vertices on the wavefront class, up to 32768 on the

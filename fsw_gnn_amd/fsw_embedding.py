@@ -55,7 +55,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .coherence import minimize_mutual_coherence
-from .graph import CSRGraph, build_csr, build_csr_coalesced
+from .graph import CSRGraph, build_csr, build_csr_coalesced, import_csr
 
 version = "0.1-mi355x"
 
@@ -315,6 +315,27 @@ def _check_finite_nonnegative(Xf, wvals):
         if wvals is not None:
             assert bool(torch.isfinite(wvals).all()), "All entries of W must be finite"
             assert bool((wvals >= 0).all()), "All entries of W must be nonnegative"
+
+
+def _csr_rec_snd(csr, num_rows):
+    """(rec, snd) int64 of the entries of a CSR adjacency (crow_indices, col_indices), for the generic kernels."""
+    crow, col = csr[0].long(), csr[1].long()
+    rec = torch.repeat_interleave(torch.arange(num_rows, device=crow.device, dtype=torch.int64), crow[1:] - crow[:-1])
+    assert rec.numel() == col.numel(), CSR_MALFORMED_MESSAGE
+    return rec.contiguous(), col.contiguous()
+
+
+def _import_csr_graph(csr, wvals, efvals, num_rows, num_cols):
+    """The graph of a torch.sparse_csr W (float32): graph.import_csr; with edge features the columns must be strictly increasing in
+    every row (the coalesced adjacency), and the feature rows are the entries' own (no self loops here: the positions are kept)."""
+    graph = import_csr(csr[0], csr[1], wvals.detach().contiguous(), num_rows, num_cols, strict_cols=efvals is not None)
+    if efvals is not None:
+        graph.ef = efvals.detach().contiguous() if efvals.shape[0] else torch.zeros((1, efvals.shape[1]), dtype=efvals.dtype, device=efvals.device)
+    return graph
+
+
+CSR_MALFORMED_MESSAGE = "CSR adjacency is malformed (crow_indices must start at 0, be non-decreasing and end at nnz)"
+CSR_COL_ORDER_MESSAGE = "with edge features the CSR adjacency must have strictly increasing column indices in every row"
 
 
 class SimpleCSR:
@@ -889,6 +910,24 @@ class FSW_embedding(nn.Module):
         self.load_state_dict(sd)
         return self
 
+    def _check_csr_arguments(self, X, W, X_edge, graph_mode):
+        """Host-side checks of a call whose W (or X_edge) has a compressed sparse layout; nothing here touches a device."""
+        supported = ("Supported sparse layouts: torch.sparse_coo (coalesced), and torch.sparse_csr with graph_mode=True, a 2-D W "
+                     "[nRecipients, n] without batch dimensions and X [n, d_in]")
+        assert torch.is_tensor(W) and W.layout == torch.sparse_csr, \
+            "Sparse W has an unsupported sparsity layout '%s'. %s." % (getattr(W, 'layout', type(W)), supported)
+        assert graph_mode, "A torch.sparse_csr W needs graph_mode=True. %s." % supported
+        assert W.dim() == 2 and X.dim() == 2 and W.dense_dim() == 0, \
+            "A torch.sparse_csr W must be 2-D [nRecipients, n] with X [n, d_in]: batch dimensions are not supported. %s." % supported
+        assert W.shape[1] == X.shape[0], "Shape mismatch between X and W: a torch.sparse_csr W [nRecipients, n] needs X [n, d_in]"
+        if self.d_edge > 0:
+            assert torch.is_tensor(X_edge) and X_edge.layout == torch.sparse_csr, \
+                "With a torch.sparse_csr W, X_edge must be torch.sparse_csr too (values [nnz, d_edge], or [nnz] when d_edge == 1)"
+            assert tuple(X_edge.shape[:2]) == tuple(W.shape), "X_edge must have the sparse shape of W"
+        if W.requires_grad or (torch.is_tensor(X_edge) and X_edge.requires_grad):
+            raise NotImplementedError("fsw_gnn_amd: gradients of a torch.sparse_csr W or X_edge are not implemented; pass them in the "
+                                      "COO layout (torch.sparse_coo), which the generic kernels differentiate")
+
     def get_device(self):
         return self.projVecs.device
 
@@ -901,6 +940,11 @@ class FSW_embedding(nn.Module):
 
         X (<batch>, n, d_in); W (<batch>, n) | 'unit' | 'uniform'; graph_mode: W (<batch>, nRecipients, n) dense or
         coalesced torch.sparse_coo, X shared by the recipients.  Returns (<batch>, [nRecipients,] d_out).
+
+        Beyond the reference, graph_mode also takes a 2-D torch.sparse_csr W [nRecipients, n] (X [n, d_in], no batch dimensions):
+        the adjacency is imported as it is, without the sort of the other layouts (graph.import_csr).  With d_edge > 0, X_edge is
+        then torch.sparse_csr with the indices of W and values [nnz, d_edge], and every row's columns must be strictly increasing.
+        Gradients of a CSR W / X_edge are not implemented (NotImplementedError: use the COO layout).
         """
         assert self.total_mass_pad_thresh > 0, 'total_mass_pad_thresh must be positive'
         if self.d_edge > 0:
@@ -913,6 +957,9 @@ class FSW_embedding(nn.Module):
             assert (X_edge is None) or (X_edge.numel() == 0), 'X_edge should be None or empty since d_edge == 0'
         assert torch.is_tensor(X), 'X must be a pytorch tensor. Instead got type %s' % (type(X))
         assert torch.is_tensor(W) or W in {'unit', 'uniform'}, "W must be a pytorch tensor, 'unit' or 'uniform'"
+        csr_in = torch.is_tensor(W) and W.layout not in (torch.strided, torch.sparse_coo)
+        if csr_in or (torch.is_tensor(X_edge) and X_edge.layout not in (torch.strided, torch.sparse_coo)):
+            self._check_csr_arguments(X, W, X_edge, graph_mode)     # host-side only: raises before any device is touched
         assert X.dtype == self.get_dtype(), ("X has the wrong dtype. Expected %s, got %s" % (self.get_dtype(), X.dtype))
         assert X.device == self.get_device(), ("X is on the wrong device. Expected %s, got %s" % (self.get_device(), X.device))
         if X.device.type != 'cuda':
@@ -925,9 +972,7 @@ class FSW_embedding(nn.Module):
         if torch.is_tensor(W):
             assert W.dtype == self.get_dtype(), ("W has the wrong dtype. Expected %s, got %s" % (self.get_dtype(), W.dtype))
             assert W.device == self.get_device(), ("W is on the wrong device. Expected %s, got %s" % (self.get_device(), W.device))
-            if W.is_sparse or W.layout != torch.strided:
-                assert W.layout == torch.sparse_coo, ("Sparse W has an unsupported sparsity layout '%s'. Only the COO "
-                                                      "layout (torch.sparse_coo) is currently supported." % (W.layout))
+            if W.is_sparse:
                 assert W.is_coalesced(), 'Sparse W must be coalesced'
                 assert W.dense_dim() == 0, 'W.dense_dim() must be zero'
         assert len(X.shape) >= 2, "X must be a tensor of order at least 2"
@@ -970,7 +1015,19 @@ class FSW_embedding(nn.Module):
                 "Shape mismatch between X and W: When graph_mode=True, if W.shape = (b1,b2,...,bk,nRecipients,n) then X.shape should be (b1,b2,...,bk,n,d_in)"
             B = int(np.prod(batch_dims)) if batch_dims else 1
             efvals = None
-            if W.is_sparse:
+            if csr_in:
+                # the adjacency by recipient as the caller holds it: imported without a sort (graph.import_csr); rec / snd are only
+                # made for the generic kernels (float64 modules), with torch ops
+                idx = None
+                csr = (W.crow_indices(), W.col_indices())
+                wvals = W.values()
+                if self.d_edge > 0:
+                    assert X_edge.values().shape[0] == wvals.shape[0], 'Sparse X_edge must have the same number of values() as W'
+                    if fsw_embedding_basic_safety_checks:
+                        assert torch.equal(X_edge.crow_indices(), csr[0]) and torch.equal(X_edge.col_indices(), csr[1]), \
+                            'Sparse X_edge must have the same nonzero pattern as W'
+                    efvals = X_edge.values().reshape(wvals.shape[0], -1)
+            elif W.is_sparse:
                 idx, wvals = W.indices(), W.values()
                 if self.d_edge > 0:
                     assert X_edge.is_coalesced() and X_edge.values().shape[0] == wvals.shape[0], \
@@ -985,11 +1042,16 @@ class FSW_embedding(nn.Module):
                     efvals = X_edge[tuple(idx)].reshape(wvals.shape[0], -1)
             if self.d_edge > 0:
                 assert efvals.shape[1] == self.d_edge, 'X_edge must carry d_edge features per edge'
-            b = _flat_batch_index(idx, batch_dims) if batch_dims else 0
-            rec = (b * nR + idx[-2]).contiguous()
-            snd = (b * n + idx[-1]).contiguous()
+            if csr_in:
+                rec = snd = None
+            else:
+                b = _flat_batch_index(idx, batch_dims) if batch_dims else 0
+                rec = (b * nR + idx[-2]).contiguous()
+                snd = (b * n + idx[-1]).contiguous()
             Xf = X.reshape(B * n, d)
             num_rows, out_shape = B * nR, batch_dims + (nR,)
+        if not (graph_mode and csr_in):
+            csr = None
 
         if self.cartesian_mode:
             # float32 calls run on the tuned kernels, under autograd with their own backward; the generic kernel keeps float64
@@ -997,7 +1059,7 @@ class FSW_embedding(nn.Module):
             # rule of the diagonal mode above)
             generic = self.get_dtype() == torch.float64 or (torch.is_grad_enabled() and (
                 (torch.is_tensor(W) and W.requires_grad) or (self.d_edge > 0 and X_edge.requires_grad)))
-            out = self._forward_cartesian(Xf, rec, snd, wvals, num_rows, generic, needs_grad, serialize_num_slices, efvals)
+            out = self._forward_cartesian(Xf, rec, snd, wvals, num_rows, generic, needs_grad, serialize_num_slices, efvals, csr)
             return out.reshape(out_shape + ((self.d_out,) if self.collapse_freqs else (self.nSlices, self.nFreqs)))
         if generic and num_rows > 0 and Xf.shape[0] > 0:
             if self.d_out == 0:
@@ -1005,6 +1067,8 @@ class FSW_embedding(nn.Module):
             if self.nSlices == 0:
                 raise NotImplementedError("fsw_gnn_amd: nSlices == 0 with encode_total_mass is not supported")
             bias = self.bias if self.enable_bias else None
+            if csr is not None:
+                rec, snd = _csr_rec_snd(csr, num_rows)
             return self._forward_generic(Xf.contiguous(), rec, snd, wvals, efvals, num_rows, bias).reshape(out_shape + (self.d_out,))
         if num_rows == 0 or Xf.shape[0] == 0:
             # nothing to embed / empty multisets only: the reference returns an empty tensor, resp. the embedding of the
@@ -1012,7 +1076,9 @@ class FSW_embedding(nn.Module):
             if num_rows == 0:
                 return torch.zeros(out_shape + (self.d_out,), dtype=X.dtype, device=X.device)
             Xf = torch.zeros((1, d), dtype=X.dtype, device=X.device)
-        if self.d_edge > 0:
+        if csr is not None:
+            graph = _import_csr_graph(csr, wvals, efvals, num_rows, Xf.shape[0])
+        elif self.d_edge > 0:
             graph = build_csr_coalesced(rec, snd, wvals.contiguous(), efvals.contiguous(), num_rows, Xf.shape[0])
         else:
             graph = build_csr(rec, snd, wvals, num_rows, Xf.shape[0])
@@ -1033,7 +1099,7 @@ class FSW_embedding(nn.Module):
         P = _GenericEmbedFn.apply(Xf, self.projVecs, self.freqs, bias if plain else None, scale, wvals, efvals, self, csr, 1.0)
         return P if plain else self._homog_epilogue(P, 1.0, bias)
 
-    def _forward_cartesian(self, Xf, rec, snd, wvals, num_rows, generic, train, serialize_num_slices, efvals=None):
+    def _forward_cartesian(self, Xf, rec, snd, wvals, num_rows, generic, train, serialize_num_slices, efvals=None, csr=None):
         """Cartesian mode: [num_rows, has_mass + S F], column has_mass + s F + f = (slice s, frequency f).  generic: the generic
         kernel (float64 modules, gradients of W or X_edge); otherwise the tuned float32 kernels (csrc/embed_cart.hip), under autograd
         (train) with their backward (_CartEmbedFn, csrc/embed_cart_bwd.hip).  efvals [nnz, d_edge]: the edge features of the entries
@@ -1052,8 +1118,12 @@ class FSW_embedding(nn.Module):
             Z = torch.zeros((num_rows, self.d_out), dtype=dt, device=dev)
             return Z + bias if bias is not None else Z
         if generic:
+            if csr is not None:
+                rec, snd = _csr_rec_snd(csr, num_rows)
             return self._forward_generic(Xf.contiguous(), rec, snd, wvals, efvals, num_rows, bias)
-        if self.d_edge > 0:
+        if csr is not None:     # a torch.sparse_csr W: (crow_indices, col_indices), imported without a sort
+            graph = _import_csr_graph(csr, wvals, efvals, num_rows, Xf.shape[0])
+        elif self.d_edge > 0:
             graph = build_csr_coalesced(rec, snd, wvals.detach().contiguous(), efvals.detach().contiguous(), num_rows, Xf.shape[0])
         else:
             graph = build_csr(rec, snd, wvals.detach().contiguous() if wvals is not None else None, num_rows, Xf.shape[0])
@@ -1463,6 +1533,8 @@ class FSW_embedding(nn.Module):
         st = graph.read_stats()
         if fsw_embedding_basic_safety_checks:
             fl = st[_lib.STAT_FLAGS]
+            assert not (fl & _lib.FLAG_CSR_MALFORMED), CSR_MALFORMED_MESSAGE
+            assert not (fl & _lib.FLAG_CSR_COL_ORDER), CSR_COL_ORDER_MESSAGE
             assert not (fl & _lib.FLAG_INDEX_RANGE), "adjacency index out of range"
             assert not (fl & _lib.FLAG_X_NONFINITE), "The entries of X cannot contain NaNs or infs"
             assert not (fl & _lib.FLAG_W_NONFINITE), "All entries of W must be finite"

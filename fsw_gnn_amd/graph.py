@@ -1,4 +1,5 @@
-"""Adjacency handling: edge list -> CSR by recipient + degree bins, on the GPU (csrc/graph_build.hip).
+"""Adjacency handling: edge list -> CSR by recipient + degree bins, on the GPU (csrc/graph_build.hip), and the import of a CSR
+adjacency the caller already holds (csrc/graph_import.hip).
 
 Stands where the reference builds a coalesced torch.sparse_coo adjacency and repeatedly sorts its int64
 COO keys (FSW_conv.edge_index_to_adj, reference fsw_conv.py:384-447; sp.get_slice_info, reference
@@ -159,6 +160,62 @@ def build_csr(recipients, senders, edge_w, num_rows, num_cols, want_invperm=Fals
     _lib.check(rc, "fsw_graph_build")
     return CSRGraph(num_rows, num_cols, E, rowptr, col, w, perm, bin_start if chunk_rows else bin_start.view(-1), stats, invperm,
                     chunk_rows=chunk_rows, meta=meta, hint=hint)
+
+
+def import_csr(rowptr, col, w, num_rows, num_cols, self_loop_weight=0.0, gcn=False, strict_cols=False, want_invperm=False,
+               want_slots=False, chunk_rows=0):
+    """A CSR adjacency the caller already holds (row i lists the senders to recipient i) -> CSRGraph, without a sort
+    (fsw_graph_import_csr, csrc/graph_import.hip).  The result equals, entry for entry, what build_csr / build_csr_coalesced give for
+    the edge list (recipient = row of e, sender = col[e]) in CSR order.
+
+    rowptr [num_rows + 1], col [nnz]: int32 or int64 CUDA tensors of one dtype, contiguous; col None = the identity col[e] = e
+    (segments of consecutive vertices: a readout's ptr; nnz = num_cols then).  w float32 [nnz] or None (unit weights).
+    self_loop_weight > 0: one loop per row, appended as the row's last entry (strict_cols False) or merged into / inserted at the
+    diagonal entry of a row with strictly increasing columns (strict_cols True: the coalesced adjacency that goes with edge
+    features).  gcn: w / sqrt(deg[row]) / sqrt(deg[col]).  want_slots: graph.slot_of_edge[e] = output position of input entry e.
+    A malformed rowptr, a column out of range or (strict_cols) unsorted columns give the EMPTY graph and a flag in graph.stats()
+    (FSW_embedding._checked_stats raises for them); nothing is read out of bounds.  No host wait."""
+    L = _lib.lib()
+    assert torch.is_tensor(rowptr) and rowptr.dtype in (torch.int32, torch.int64), \
+        "rowptr must be an int32 or int64 tensor (got %s)" % (getattr(rowptr, "dtype", type(rowptr)),)
+    assert col is None or (torch.is_tensor(col) and col.dtype == rowptr.dtype), "col must have the dtype of rowptr (int32 or int64)"
+    dev = rowptr.device
+    assert rowptr.dim() == 1 and rowptr.numel() == num_rows + 1, "rowptr must hold num_rows + 1 entries"
+    assert col is None or (col.dim() == 1 and col.device == dev), "col must be a 1-D tensor on the device of rowptr"
+    nnz = int(col.numel()) if col is not None else int(num_cols)
+    loops = float(self_loop_weight) != 0.0
+    assert not (loops or gcn) or num_rows == num_cols, "self loops and 'gcn' weights need a square adjacency"
+    assert float(self_loop_weight) >= 0.0, "self_loop_weight must be >= 0"
+    if dev.type != "cuda":
+        raise RuntimeError("fsw_gnn_amd.import_csr: tensors must live on a HIP device (no CPU path)")
+    rowptr = rowptr.contiguous()
+    col = col.contiguous() if col is not None else None
+    if w is not None:
+        assert w.dtype == torch.float32 and w.dim() == 1 and w.numel() == nnz and w.device == dev, "w must be float32 [nnz] on the device"
+        w = w.contiguous()
+    cap = max(nnz + (num_rows if loops else 0), 1)
+    weighted = w is not None or loops or bool(gcn)
+    rowptr_out = torch.empty(num_rows + 1, dtype=torch.int32, device=dev)
+    col_out = torch.empty(cap, dtype=torch.int32, device=dev)
+    w_out = torch.empty(cap, dtype=torch.float32, device=dev) if weighted else None
+    # zeroed: an input that fails the device-side check leaves the slots unwritten, and the host scatters feature rows with them
+    slot = torch.zeros(max(nnz, 1), dtype=torch.int32, device=dev) if want_slots else None
+    perm = torch.empty(num_rows, dtype=torch.int32, device=dev)
+    invperm = torch.empty(num_rows, dtype=torch.int32, device=dev) if want_invperm else None
+    num_chunks = -(-num_rows // chunk_rows) if chunk_rows else 1
+    assert num_chunks <= _lib.MAX_ROW_CHUNKS and chunk_rows % _lib.BIN_BLOCK_ROWS == 0, "bad chunk_rows"
+    meta = torch.empty(_lib.NUM_STATS + num_chunks * (_lib.NUM_BINS + 1), dtype=torch.int32, device=dev)
+    stats, bin_start = meta[:_lib.NUM_STATS], meta[_lib.NUM_STATS:].view(num_chunks, _lib.NUM_BINS + 1)
+    ws_bytes = int(L.fsw_graph_import_workspace_bytes(num_rows, nnz))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = L.fsw_graph_import_csr(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(w), rowptr.element_size(), nnz, num_rows, num_cols, chunk_rows,
+                                float(self_loop_weight), int(bool(gcn)), int(bool(strict_cols)), _lib.ptr(rowptr_out), _lib.ptr(col_out),
+                                _lib.ptr(w_out), _lib.ptr(slot), _lib.ptr(perm), _lib.ptr(invperm), _lib.ptr(bin_start), _lib.ptr(stats),
+                                _lib.ptr(ws), ws_bytes, stream)
+    _lib.check(rc, "fsw_graph_import_csr")
+    return CSRGraph(num_rows, num_cols, cap if (nnz or loops) else 0, rowptr_out, col_out, w_out, perm,
+                    bin_start if chunk_rows else bin_start.view(-1), stats, invperm, slot_of_edge=slot, chunk_rows=chunk_rows, meta=meta)
 
 
 def build_csr_coalesced(recipients, senders, edge_w, edge_feat, num_rows, num_cols, want_slots=False):

@@ -146,6 +146,48 @@ int fsw_graph_build_coalesced(const int64_t* recipients, const int64_t* senders,
                               int32_t* invperm, int32_t* bin_start, int32_t* stats, void* workspace, size_t workspace_bytes,
                               fsw_stream_t stream);
 
+/* ---- adjacency: CSR in, the same CSR + degree bins out (no sort) ---------------------------------
+ * For callers that hold the adjacency by recipient already (torch.sparse_csr, PyG's adj_t.csr(), batch.ptr).  Row i of the
+ * input lists the senders to recipient i.  The outputs are those of fsw_graph_build (rowptr / col / w as int32 / int32 / float,
+ * perm, optional invperm, bin_start, stats, chunk_rows with the same meaning) and equal, entry for entry, what the builds above
+ * produce from the edge list (recipient = row of e, sender = col_in[e]) in CSR order.
+ *   rowptr_in [num_rows + 1], col_in [nnz] : int32 (index_bytes 4) or int64 (index_bytes 8); col_in NULL = the identity
+ *                col[e] = e (segments of consecutive vertices: a readout's ptr), which needs num_cols >= nnz
+ *   w_in float[nnz] or NULL for unit weights
+ *   col / w / slot_of_entry : sized for nnz entries, and for nnz + num_rows when self_loop_weight != 0; w may be NULL when the
+ *                result is unit (w_in NULL, no self loops, no gcn); slot_of_entry int32[nnz] (nullable) receives the output
+ *                position of every input entry
+ *   self_loop_weight : 0 = none (finite, >= 0; needs num_rows == num_cols).  strict_cols 0: one entry (r, r, self_loop_weight) is
+ *                appended as the LAST entry of every row, whether or not the row has a diagonal entry (what appending the loops
+ *                to the edge list and the stable build give); a unit input becomes weighted with w = 1 on its entries.
+ *                strict_cols 1 (the coalesced adjacency, used with edge features): the columns of every row must be strictly
+ *                increasing; the loop's weight is ADDED to the diagonal entry where there is one (float64 sum rounded to
+ *                float), otherwise a new entry is inserted at its sorted place -- fsw_graph_build_coalesced of the edge list
+ *                with the loops appended.  The caller scatters its feature rows with slot_of_entry; new entries carry zeros.
+ *   gcn 1      : deg[r] = sum of row r's final weights (float64 partial sums in a fixed order: reproducible), then
+ *                w = w / sqrt(deg[row]) / sqrt(deg[col]) in float32; needs num_rows == num_cols.
+ * Entries keep their order inside a row; repeated columns stay separate elements (strict_cols 0).
+ * stats: FSW_FLAG_W_NONFINITE / FSW_FLAG_W_NEGATIVE describe the FINAL weights; FSW_FLAG_INDEX_RANGE a column outside
+ * [0, num_cols); and
+ *   FSW_FLAG_CSR_MALFORMED  rowptr_in[0] != 0, a negative or decreasing pair, or rowptr_in[num_rows] != nnz
+ *   FSW_FLAG_CSR_COL_ORDER  strict_cols only: two neighbouring columns of a row are not strictly increasing
+ *   FSW_FLAG_W_NONUNIT      informational: some input weight is not exactly 1
+ * Safety: given only that the arrays have the stated lengths, every device access of the import is in bounds for ANY contents
+ * (col_in / w_in are indexed by e < nnz; a value of rowptr_in becomes an index only after the whole array passed the check).
+ * With MALFORMED, INDEX_RANGE or COL_ORDER set the imported graph is EMPTY -- rowptr all 0, stats[FSW_STAT_NNZ] 0, every row in the
+ * zero-degree bin (the kernels of the import read the flag word on the device) -- so no later kernel can index out of range before
+ * the host has seen the flag.  Stream-ordered: no host wait, no allocation.  Sizes with nnz + num_rows >= 2^31, index_bytes other
+ * than 4 or 8 and a workspace below fsw_graph_import_workspace_bytes (per-row scratch only, about 12 bytes a row) are refused
+ * with a status before any launch.                                                                                          */
+#define FSW_FLAG_CSR_MALFORMED 16
+#define FSW_FLAG_CSR_COL_ORDER 32
+#define FSW_FLAG_W_NONUNIT 64
+size_t fsw_graph_import_workspace_bytes(int64_t num_rows, int64_t nnz);
+int fsw_graph_import_csr(const void* rowptr_in, const void* col_in, const float* w_in, int index_bytes, int64_t nnz,
+                         int64_t num_rows, int64_t num_cols, int64_t chunk_rows, float self_loop_weight, int gcn, int strict_cols,
+                         int32_t* rowptr, int32_t* col, float* w, int32_t* slot_of_entry, int32_t* perm, int32_t* invperm,
+                         int32_t* bin_start, int32_t* stats, void* workspace, size_t workspace_bytes, fsw_stream_t stream);
+
 /* ---- projection: Xp[n, ldp] = X[n, ldx] . V[S, ldv]^T on the matrix cores -------------------------
  * Default: every operand split into three bf16 planes (x = x1 + x2 + x3 carries fp32's 24 significand bits), six
  * v_mfma_f32_32x32x16_bf16 per k-step with fp32 accumulation: < 5e-7 against float64, 2.7x fewer matrix cycles than the exact
