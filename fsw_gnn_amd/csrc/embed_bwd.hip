@@ -181,17 +181,19 @@ __device__ __forceinline__ void weighted_bwd_rows(int p, int pe, const int32_t* 
     const double taud = (double)tau;
     const double inv = 1.0 / fmax(m, taud);
     key[DEG] = 0.f;                               // the reference's pad element (fsw_embedding.py:787-821)
-    wr[DEG] = (float)fmax(taud - m, 0.0);
+    const double padd = fmax(taud - m, 0.0);      // the pad weight enters the cumulative weights in float64 (fsw_common.h: pad_residual)
+    wr[DEG] = (float)padd;
+    auto wd = [&](int t) { return t == DEG ? padd : (double)wr[t]; };
     double cum[DEG + 1];
 #pragma unroll
-    for (int t = 0; t <= DEG; ++t) cum[t] = (double)wr[t];
+    for (int t = 0; t <= DEG; ++t) cum[t] = wd(t);
 #pragma unroll
     for (int u = 0; u <= DEG; ++u)
 #pragma unroll
       for (int t = u + 1; t <= DEG; ++t) {
         const bool before = key[t] < key[u];      // ties keep element order, like a stable sort
-        cum[u] += before ? (double)wr[t] : 0.0;
-        cum[t] += before ? 0.0 : (double)wr[u];
+        cum[u] += before ? wd(t) : 0.0;
+        cum[t] += before ? 0.0 : wd(u);
       }
 #pragma unroll
     for (int t = 0; t < DEG; ++t) {

@@ -122,6 +122,7 @@ __device__ __forceinline__ void cart_reg_weighted(const CartTuned& a, int p, int
     }
     net.k[D] = 0.f;                                   // the reference's pad element at x = 0
     net.w[D] = (float)fmax(tau - m, 0.0);
+    const double rho = pad_residual(tau - m, net.w[D]);   // what the float lane lost of the pad weight (fsw_common.h)
     const double inv = 1.0 / fmax(m, tau);
     sort_network<D + 1>(net);
     double cn[D + 1];
@@ -129,7 +130,7 @@ __device__ __forceinline__ void cart_reg_weighted(const CartTuned& a, int p, int
 #pragma unroll
     for (int t = 0; t <= D; ++t) {
       cum += (double)net.w[t];
-      cn[t] = cum * inv;
+      cn[t] = (cum + pad_residual_at(rho, net.k[t])) * inv;
     }
     float* orow = a.out + (int64_t)node * a.ldo;
     const int64_t c0 = (int64_t)a.has_mass + (int64_t)s * a.F;
@@ -209,12 +210,14 @@ __global__ void __launch_bounds__(64) k_cart_wave(const CartTuned a, int p0) {
   const double m = mpart;
   const double tau = (double)a.tau;
   const double inv = 1.0 / fmax(m, tau);
+  const float padw = (float)fmax(tau - m, 0.0);
+  const double rho = pad_residual(tau - m, padw);    // what the float line loses of the pad weight (fsw_common.h)
   if constexpr (WEIGHTED) {
 #pragma unroll
     for (int j = 0; j < M; ++j)
       if (lane * M + j == D) {
         ln.k[j] = 0.f;
-        ln.w[j] = (float)fmax(tau - m, 0.0);
+        ln.w[j] = padw;
       }
   }
   ln.sort();
@@ -235,7 +238,7 @@ __global__ void __launch_bounds__(64) k_cart_wave(const CartTuned a, int p0) {
 #pragma unroll
     for (int j = 0; j < M; ++j) {
       c += (double)ln.w[j];
-      lc[lane * M + j] = c * inv;
+      lc[lane * M + j] = (c + pad_residual_at(rho, ln.k[j])) * inv;   // telescoped readout: a zero key's term has dp == 0 unless the pad lies before it
     }
   }
   __syncthreads();

@@ -198,7 +198,7 @@ __device__ __forceinline__ void cart_bwd_reg_weighted(const CartBwd& a, int p, i
     }
     net.k[D] = 0.f;                                   // the reference's pad element at x = 0, last among equal keys
     net.w[D] = __int_as_float(D);
-    const float padw = (float)fmax(tau - m, 0.0);
+    const double padw = fmax(tau - m, 0.0);           // float64: it enters the float64 cumulative weight (fsw_common.h: pad_residual)
     const double inv = 1.0 / fmax(m, tau);
     sort_network<D + 1>(net);
     double cn[D + 1];
@@ -206,7 +206,7 @@ __device__ __forceinline__ void cart_bwd_reg_weighted(const CartBwd& a, int p, i
 #pragma unroll
     for (int t = 0; t <= D; ++t) {
       const int id = __float_as_int(net.w[t]);
-      cum += (double)(id < D ? (a.w ? a.w[start + id] : 1.f) : padw);
+      cum += id < D ? (double)(a.w ? a.w[start + id] : 1.f) : padw;
       cn[t] = cum * inv;
     }
     float G[D + 1];
@@ -302,6 +302,7 @@ __global__ void __launch_bounds__(64) k_cart_bwd_wave(const CartBwd a, int p0) {
   const double tau = (double)a.tau;
   const double inv = 1.0 / fmax(m, tau);
   const float padw = (float)fmax(tau - m, 0.0);
+  const double rho = pad_residual(tau - m, padw);  // what the float wt[] loses of the pad weight: added where the walk passes the pad (fsw_common.h)
   ln.sort();
   float key[M];
   int idx[M];
@@ -319,7 +320,7 @@ __global__ void __launch_bounds__(64) k_cart_bwd_wave(const CartBwd a, int p0) {
     for (int j = 0; j < M; ++j) {
       const int id = idx[j];
       wt[j] = id < D ? (a.w ? a.w[start + id] : 1.f) : (id == D ? padw : 0.f);
-      pre += (double)wt[j];
+      pre += (double)wt[j] + (id == D ? rho : 0.0);
     }
     cbase = wave_exclusive_scan_f64(pre);
   }
@@ -338,7 +339,7 @@ __global__ void __launch_bounds__(64) k_cart_bwd_wave(const CartBwd a, int p0) {
       const int t = lane * M + j;
       double cn;
       if constexpr (WEIGHTED) {
-        c += (double)wt[j];
+        c += (double)wt[j] + (idx[j] == D ? rho : 0.0);
         cn = c * inv;
       } else {
         cn = (double)min(t + 1, D) * invD;

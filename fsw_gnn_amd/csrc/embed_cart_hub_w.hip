@@ -92,8 +92,9 @@ __global__ void __launch_bounds__(NW* kWave, 2) k_cart_hub_w(const CartHubW a, i
     for (int q = 0; q < NW; ++q) m += redd[q];
     __syncthreads();
     const double inv = 1.0 / fmax(m, taud);
+    const float padw = (float)fmax(taud - m, 0.0);             // zero weight unless the row is deficient
+    const double rho = pad_residual(taud - m, padw);           // what the float line loses of it (fsw_common.h)
     {
-      const float padw = (float)fmax(taud - m, 0.0);           // zero weight unless the row is deficient
 #pragma unroll
       for (int j = 0; j < M; ++j)
         if (t0 + j * kWave + lane == D) {
@@ -141,11 +142,12 @@ __global__ void __launch_bounds__(NW* kWave, 2) k_cart_hub_w(const CartHubW a, i
         } else {
           const double xi = (double)xif;
           double cw = cw0;
-          float sprev = sin2pi_rev(xi * (cw * inv));
+          // the element before a key >= 0 is the pad element, or lies behind it, or multiplies a zero key: same residual
+          float sprev = sin2pi_rev(xi * ((cw + pad_residual_at(rho, ln.k[0])) * inv));
 #pragma unroll
           for (int j = 0; j < M; ++j) {
             cw += (double)ln.w[j];
-            const float sn = sin2pi_rev(xi * (cw * inv));
+            const float sn = sin2pi_rev(xi * ((cw + pad_residual_at(rho, ln.k[j])) * inv));
             acc = fmaf(sn - sprev, ln.k[j], acc);
             sprev = sn;
           }

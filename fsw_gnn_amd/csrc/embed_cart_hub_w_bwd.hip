@@ -95,6 +95,7 @@ __global__ void __launch_bounds__(256) k_cart_bwd_long_w(const CartBwdLongW a, i
     const double m = wave_sum(mpart);
     const double inv = 1.0 / fmax(m, taud);
     const float padw = (float)fmax(taud - m, 0.0);
+    const double rho = pad_residual(taud - m, padw);             // what the float wt[] loses of the pad weight: added where the walk passes the pad (fsw_common.h)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     // B. merge levels above one chunk
     for (int size = 2 * CAP; size <= Dp; size <<= 1) {
@@ -132,7 +133,7 @@ __global__ void __launch_bounds__(256) k_cart_bwd_long_w(const CartBwdLongW a, i
 #pragma unroll
         for (int j = 0; j < M; ++j) {
           wt[j] = idx[j] < D ? (wrow ? wrow[idx[j]] : 1.f) : (idx[j] == D ? padw : 0.f);
-          pre += (double)wt[j];
+          pre += (double)wt[j] + (idx[j] == D ? rho : 0.0);
         }
         const double cbase = carry + wave_exclusive_scan_f64(pre);
         carry += wave_sum(pre);
@@ -143,7 +144,7 @@ __global__ void __launch_bounds__(256) k_cart_bwd_long_w(const CartBwdLongW a, i
           float ds = 0.f;
 #pragma unroll
           for (int j = 0; j < M; ++j) {
-            c += (double)wt[j];
+            c += (double)wt[j] + (idx[j] == D ? rho : 0.0);
             double Fv, dFv;
             F_dF(fc, c * inv, Fv, dFv);
             if (j == 0) {

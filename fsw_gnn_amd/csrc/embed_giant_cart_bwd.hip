@@ -130,6 +130,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_cart_giant_bwd(const CartGiantBw
     }
     double inv = 1.0 / (double)D;
     float padw = 0.f;
+    double rho = 0.0;                                        // what the float wt[] loses of the pad weight: added where the walk passes the pad (fsw_common.h)
     if constexpr (WEIGHTED) {
       mpart = wave_sum(mpart);
       if (lane == 0) redm[w] = mpart;
@@ -142,6 +143,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_cart_giant_bwd(const CartGiantBw
       for (int q = 0; q < NW; ++q) m += redm[q];             // rewritten after the barriers of the next line's phase C at the earliest
       inv = 1.0 / fmax(m, taud);
       padw = (float)fmax(taud - m, 0.0);
+      rho = pad_residual(taud - m, padw);
     }
     // B. merge-path levels between ping and pong
     const mp64_t* se = merge_path64_levels(ping, pong, total, tk, part);
@@ -169,7 +171,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_cart_giant_bwd(const CartGiantBw
 #pragma unroll
           for (int j = 0; j < VT; ++j) {
             wt[j] = idx[j] < D ? (wrow ? wrow[idx[j]] : 1.f) : (idx[j] == D ? padw : 0.f);
-            pre += (double)wt[j];
+            pre += (double)wt[j] + (idx[j] == D ? rho : 0.0);
           }
           double cw0 = wave_exclusive_scan_f64(pre);
           const double wtot = __shfl(cw0 + pre, kWave - 1);  // this wavefront's total
@@ -193,7 +195,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_cart_giant_bwd(const CartGiantBw
               float ds = 0.f;
 #pragma unroll
               for (int j = 0; j < VT; ++j) {
-                c += (double)wt[j];
+                c += (double)wt[j] + (idx[j] == D ? rho : 0.0);
                 double Fv, dFv;
                 F_dF(fc, c * inv, Fv, dFv);
                 G[j] = fmaf(gi, (float)(Fv - Fp), G[j]);

@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_cart_mergepath_w(const CartGiantW 
 #pragma unroll
         for (int q = 0; q < NW; ++q) m += redd[q];
         __syncthreads();
-        const float padw = (float)fmax(taud - m, 0.0);     // zero weight unless the row is deficient
+        const float padw = (float)fmax(taud - m, 0.0);     // zero weight unless the row is deficient (its residual: below)
 #pragma unroll
         for (int j = 0; j < M; ++j)
           if (t0 + j * kWave + lane == D) {
@@ -135,6 +135,8 @@ __global__ void __launch_bounds__(kMpNT, 2) k_cart_mergepath_w(const CartGiantW 
       }
     }
     const double inv = 1.0 / fmax(m, taud);
+    // must be the float that phase A stored as the pad element's weight (padw above: the same expression of the same m)
+    const double rho = pad_residual(taud - m, (float)fmax(taud - m, 0.0));   // what the float line loses of the pad weight (fsw_common.h)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
     // B. merge-path levels; level i reads the line that level i - 1 wrote, so the last of `levels` writes the pong line when levels is odd
@@ -200,11 +202,12 @@ __global__ void __launch_bounds__(kMpNT, 2) k_cart_mergepath_w(const CartGiantW 
             } else {
               const double xi = (double)xif;
               double cw = cw0;
-              float sprev = sin2pi_rev(xi * (cw * inv));
+              // the element before a key >= 0 is the pad element, or lies behind it, or multiplies a zero key: same residual
+              float sprev = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[0])) * inv));
 #pragma unroll
               for (int j = 0; j < kMpVT; ++j) {
                 cw += (double)ww[j];
-                const float sn = sin2pi_rev(xi * (cw * inv));
+                const float sn = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[j])) * inv));
                 acc[q] = fmaf(sn - sprev, kk[j], acc[q]);
                 sprev = sn;
               }

@@ -699,8 +699,9 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k
     }
     const double taud = (double)tau;
     const double inv = 1.0 / fmax(m, taud);
+    const float padw = (float)fmax(taud - m, 0.0);           // zero weight unless the row is deficient
+    const double rho = pad_residual(taud - m, padw);         // what the float line loses of it (fsw_common.h)
     {
-      const float padw = (float)fmax(taud - m, 0.0);         // zero weight unless the row is deficient
 #pragma unroll
       for (int j = 0; j < M; ++j)
         if (t0 + j * kWave + lane == D) {
@@ -735,7 +736,8 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k
       __syncthreads();
     }
     float acc = 0.f;
-    float sprev = lin ? 0.f : sin2pi_rev(xi * (cw * inv));
+    // the element before a key >= 0 is the pad element, or lies behind it, or multiplies a zero key: same residual
+    float sprev = lin ? 0.f : sin2pi_rev(xi * ((cw + pad_residual_at(rho, ln.k[0])) * inv));
     const int r0 = w * CAP + lane * M;
 #pragma unroll
     for (int j = 0; j < M; ++j) {
@@ -744,7 +746,7 @@ __global__ void __launch_bounds__(NW == 1 ? 256 : NW * kWave, M >= 24 ? 2 : 3) k
       if (lin) {
         acc += valid ? ln.w[j] * ln.k[j] : 0.f;
       } else {
-        const float sn = sin2pi_rev(xi * (cw * inv));
+        const float sn = sin2pi_rev(xi * ((cw + pad_residual_at(rho, ln.k[j])) * inv));
         acc += valid ? (sn - sprev) * ln.k[j] : 0.f;
         sprev = sn;
       }
@@ -798,10 +800,11 @@ __device__ unsigned long long g_mp_stamps[512][4][16];   // [workgroup][wavefron
 // 28 bitonic sweeps of a 150 000-neighbour line by ONE wavefront became 5 passes by a workgroup.
 //
 // readout of N consecutive ranks per thread, threads in rank order (wavefront w, lane, j): returns the thread's partial sum and
-// advances `carry` (the cumulative weight before the workgroup's first element) by the workgroup's total
+// advances `carry` (the cumulative weight before the workgroup's first element) by the workgroup's total.  rho: pad_residual of the row
 template <int N>
 __device__ __forceinline__ float weighted_readout(const float* __restrict__ kk, const float* __restrict__ ww, int r0, int Dtot, double xi,
-                                                  double inv, bool lin, double& carry, double* __restrict__ redd, int w, int lane) {
+                                                  double inv, bool lin, double rho, double& carry, double* __restrict__ redd, int w,
+                                                  int lane) {
   constexpr int NW = kMpNT / kWave;
   double lsum = 0.0;
 #pragma unroll
@@ -820,7 +823,7 @@ __device__ __forceinline__ float weighted_readout(const float* __restrict__ kk, 
   cw += carry;
   carry += tot;
   float acc = 0.f;
-  float sprev = lin ? 0.f : sin2pi_rev(xi * (cw * inv));
+  float sprev = lin ? 0.f : sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[0])) * inv));
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     const bool valid = r0 + j < Dtot;
@@ -828,7 +831,7 @@ __device__ __forceinline__ float weighted_readout(const float* __restrict__ kk, 
     if (lin) {
       acc += valid ? ww[j] * kk[j] : 0.f;
     } else {
-      const float sn = sin2pi_rev(xi * (cw * inv));
+      const float sn = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[j])) * inv));
       acc += valid ? (sn - sprev) * kk[j] : 0.f;
       sprev = sn;
     }
@@ -872,7 +875,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_embed_mergepath_w(
     const int nb = (Dtot + kMpBlk - 1) / kMpBlk;
     // total mass of the row: summed from the weights as the blocks load them (the pad element, whose weight needs it, is element
     // D of the line = in the LAST block: one workgroup reduction there instead of a pass of its own over the row's weights)
-    double pm = 0.0, m = 0.0, inv = 0.0;
+    double pm = 0.0, m = 0.0, inv = 0.0, rho = 0.0;
     float padw = 0.f;
     const double taud = (double)tau;
     const float xif = freqs[k];
@@ -906,6 +909,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_embed_mergepath_w(
         __syncthreads();
         inv = 1.0 / fmax(m, taud);
         padw = (float)fmax(taud - m, 0.0);
+        rho = pad_residual(taud - m, padw);                 // what the float line loses of the pad weight (fsw_common.h)
 #pragma unroll
         for (int j = 0; j < M; ++j)
           if (t0 + j * kWave + lane == D) {
@@ -933,13 +937,13 @@ __global__ void __launch_bounds__(kMpNT, 2) k_embed_mergepath_w(
     double carry = 0.0;
     FSW_MP_MARK(st, 3);                                    // blocks parked in the scratch line
     if (nb == 1) {
-      acc = weighted_readout<M>(ln.k, ln.w, w * CAP + lane * M, Dtot, xi, inv, lin, carry, redd, w, lane);
+      acc = weighted_readout<M>(ln.k, ln.w, w * CAP + lane * M, Dtot, xi, inv, lin, rho, carry, redd, w, lane);
     } else {
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __syncthreads();
       FSW_MP_MARK(st, 4);                                  // fence + barrier
       merge_path_levels<true>(k0, k1, w0, w1, nb, tk, tw, part, [&](int r0, const float* ok, const float* ow) {
-        acc += weighted_readout<kMpVT>(ok, ow, r0, Dtot, xi, inv, lin, carry, redd, w, lane);
+        acc += weighted_readout<kMpVT>(ok, ow, r0, Dtot, xi, inv, lin, rho, carry, redd, w, lane);
       }, st);
     }
     acc *= lin ? 2.f * (float)inv : (float)((1.0 + xi) / (kPi * xi));

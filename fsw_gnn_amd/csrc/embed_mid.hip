@@ -250,6 +250,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
       }
     }
     const float padw = (float)fmax(taud - m, 0.0);   // zero weight when the row is not deficient
+    const double rho = pad_residual(taud - m, padw); // what the float lane lost of it (fsw_common.h)
 #pragma unroll
     for (int t = FSW_REG_MAX_DEG + 1; t < DP; ++t)
       if (t == D) {
@@ -264,7 +265,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
     for (int t = 0; t < DP; ++t) {
       if (t <= D) {
         c += (double)net.w[t];
-        const float s = sin2pi_rev(xi * (c * inv));
+        const float s = sin2pi_rev(xi * ((c + pad_residual_at(rho, net.k[t])) * inv));
         acc = fmaf(s - sprev, net.k[t], acc);
         acc0 = fmaf(net.w[t], net.k[t], acc0);
         sprev = s;

@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_bwd(const int32_t* __restrict
     }
     sort_network<DP>(net);
     const double inv = 1.0 / (WEIGHTED ? fmax(m, taud) : m);
-    const float padw = WEIGHTED ? (float)fmax(taud - m, 0.0) : 0.f;
+    const double padw = WEIGHTED ? fmax(taud - m, 0.0) : 0.0;   // float64: it enters the float64 cumulative weight (fsw_common.h: pad_residual)
     const float gi = kvalid ? out_scale * g[(int64_t)node * ldg + gcol0 + k] : 0.f;
     double Fp = 0.0, dFp = 0.0;   // F(0) = dF(0) = 0
     if constexpr (!WEIGHTED) {
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_bwd(const int32_t* __restrict
       for (int r = 0; r < DP; ++r) {
         if (r < Dtot) {
           const int id = (int)(unsigned int)net.e[r];
-          c += (double)(id == D ? padw : (w ? w[start + id] : 1.f));
+          c += id == D ? padw : (double)(w ? w[start + id] : 1.f);
           const double ph = xi * (c * inv);
           double s, co, F, dF;
           sincospi(2.0 * (ph - rint(ph)), &s, &co);

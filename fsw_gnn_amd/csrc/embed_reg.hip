@@ -219,6 +219,7 @@ __device__ __forceinline__ void weighted_run(int p, int pe, const int32_t* __res
     const double denom = fmax(m, taud);
     net.k[DEG] = 0.f;                             // the reference's pad element at x = 0
     net.w[DEG] = (float)fmax(taud - m, 0.0);      // zero weight when the row is not deficient
+    const double rho = pad_residual(taud - m, net.w[DEG]);   // what the float lane lost of the pad weight (fsw_common.h)
     const double inv = 1.0 / denom;
     sort_network<DEG + 1>(net);
     double c = 0.0;
@@ -226,7 +227,7 @@ __device__ __forceinline__ void weighted_run(int p, int pe, const int32_t* __res
 #pragma unroll
     for (int t = 0; t <= DEG; ++t) {
       c += (double)net.w[t];
-      const float s = sin2pi_rev(xi * (c * inv));
+      const float s = sin2pi_rev(xi * ((c + pad_residual_at(rho, net.k[t])) * inv));
       acc = fmaf(s - sprev, net.k[t], acc);
       acc0 = fmaf(net.w[t], net.k[t], acc0);
       sprev = s;

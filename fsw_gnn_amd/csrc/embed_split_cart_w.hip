@@ -334,7 +334,10 @@ __global__ void __launch_bounds__(kMpNT, 2) k_splitw_readout(const CartSplitW a)
   const bool odd = splitw_levels(l.nb) & 1;
   const float* fk = a.scratch + line * 4 * a.cap + (odd ? a.cap : 0);
   const float* fw = fk + 2 * a.cap;
-  const double inv = 1.0 / fmax(splitw_mass(a, row, l.nb), (double)a.tau);
+  const double m = splitw_mass(a, row, l.nb);
+  const double inv = 1.0 / fmax(m, (double)a.tau);
+  // must be the float that k_splitw_sort stored as the pad element's weight (padw there: the same expression of the same splitw_mass)
+  const double rho = pad_residual((double)a.tau - m, (float)fmax((double)a.tau - m, 0.0));   // what the float line loses of the pad weight (fsw_common.h)
   const double* ts = a.tsum + line * a.tiles;
   double carry = 0.0;                                         // the cumulative weight before the tile
   for (int q = 0; q < i; ++q) carry += ts[q];
@@ -377,11 +380,12 @@ __global__ void __launch_bounds__(kMpNT, 2) k_splitw_readout(const CartSplitW a)
         } else {
           const double xi = (double)xif;
           double cw = cw0;
-          float sprev = sin2pi_rev(xi * (cw * inv));
+          // the element before a key >= 0 is the pad element, or lies behind it, or multiplies a zero key: same residual
+          float sprev = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[0])) * inv));
 #pragma unroll
           for (int j = 0; j < kMpVT; ++j) {
             cw += (double)ww[j];
-            const float sn = sin2pi_rev(xi * (cw * inv));
+            const float sn = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[j])) * inv));
             acc[q] = fmaf(sn - sprev, kk[j], acc[q]);
             sprev = sn;
           }

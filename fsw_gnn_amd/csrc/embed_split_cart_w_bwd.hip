@@ -104,6 +104,10 @@ __device__ __forceinline__ double swb_mass(const CartSplitWBwd& a, int64_t row, 
 __device__ __forceinline__ float swb_weight(const float* wrow, int idx, int D, float padw) {
   return idx < D ? (wrow ? wrow[idx] : 1.f) : (idx == D ? padw : 0.f);
 }
+// the same in float64 with the pad weight unrounded, for the float64 sums of the cumulative weight (fsw_common.h: pad_residual)
+__device__ __forceinline__ double swb_weight_f64(const float* wrow, int idx, int D, double padw) {
+  return idx < D ? (double)(wrow ? wrow[idx] : 1.f) : (idx == D ? padw : 0.0);
+}
 
 // grid (tiles, rows): piece blockIdx.x of the row
 __global__ void __launch_bounds__(kMp64NT) k_splitw_bwd_mass(const CartSplitWBwd a) {
@@ -199,11 +203,11 @@ __global__ void __launch_bounds__(kMp64NT) k_splitw_bwd_tsum(const CartSplitWBwd
   if (t064 > l.D) return;                                    // the tiles beyond element D hold fill elements only
   const int D = l.D;
   const float* wrow = a.w ? a.w + l.start : nullptr;
-  const float padw = (float)fmax((double)a.tau - swb_mass(a, row, l.total), 0.0);
+  const double padw = fmax((double)a.tau - swb_mass(a, row, l.total), 0.0);
   const mp64_t* se = swb_region(a, line, mp64_num_levels(l.total)) + t064 + (int)threadIdx.x * VT;   // total is a multiple of TILE
   double pre = 0.0;
 #pragma unroll
-  for (int j = 0; j < VT; ++j) pre += (double)swb_weight(wrow, (int)((unsigned int)se[j] & 0x7fffffffu), D, padw);
+  for (int j = 0; j < VT; ++j) pre += swb_weight_f64(wrow, (int)((unsigned int)se[j] & 0x7fffffffu), D, padw);
   pre = wave_sum(pre);
   if (lane_id() == 0) redd[wave_id()] = pre;
   __syncthreads();
@@ -231,6 +235,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_splitw_bwd_walk(const CartSplitW
   const double taud = (double)a.tau, m = swb_mass(a, row, l.total);
   const double inv = 1.0 / fmax(m, taud);
   const float padw = (float)fmax(taud - m, 0.0);
+  const double rho = pad_residual(taud - m, padw);           // what the float wt[] loses of the pad weight: added where the walk passes the pad
   const double* ts = a.tsum + line * a.tiles;
   double carry = 0.0;                                        // the cumulative weight before the tile
   for (int q = 0; q < (int)blockIdx.x; ++q) carry += ts[q];
@@ -249,7 +254,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_splitw_bwd_walk(const CartSplitW
     key[j] = r0 + j < L ? from_orderable_bits((unsigned int)(e >> 32)) : 0.f;   // fill elements: no inf in the frequency sums
     idx[j] = (int)((unsigned int)e & 0x7fffffffu);
     wt[j] = swb_weight(wrow, idx[j], D, padw);
-    pre += (double)wt[j];
+    pre += (double)wt[j] + (idx[j] == D ? rho : 0.0);
   }
   double cw0 = wave_exclusive_scan_f64(pre);
   const double wtot = __shfl(cw0 + pre, kWave - 1);          // this wavefront's total
@@ -274,7 +279,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_splitw_bwd_walk(const CartSplitW
         float ds = 0.f;
 #pragma unroll
         for (int j = 0; j < VT; ++j) {
-          c += (double)wt[j];
+          c += (double)wt[j] + (idx[j] == D ? rho : 0.0);
           double Fv, dFv;
           F_dF(fc, c * inv, Fv, dFv);
           G[j] = fmaf(gi, (float)(Fv - Fp), G[j]);

@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
     const int start = rowptr[node];
     const int D = rowptr[node + 1] - start;
     const int Dtot = WEIGHTED ? D + 1 : D;              // the weighted variant always carries the pad element; Dtot <= CAP
-    double m = (double)D;
+    double m = (double)D, rho = 0.0;
     if constexpr (WEIGHTED) {
       double part = 0.0;
       for (int t = threadIdx.x; t < D; t += blockDim.x) {
@@ -66,7 +66,9 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
       if (lane == 0) msum[wv] = part;
       __syncthreads();
       m = msum[0] + msum[1] + msum[2] + msum[3];
-      if (threadIdx.x == 0) wrow[D + D / M] = (float)fmax((double)tau - m, 0.0);   // pad element: zero weight unless deficient
+      const float padw = (float)fmax((double)tau - m, 0.0);    // pad element: zero weight unless deficient
+      rho = pad_residual((double)tau - m, padw);               // what the float line loses of it (fsw_common.h)
+      if (threadIdx.x == 0) wrow[D + D / M] = padw;
       __syncthreads();
     }
     const double inv = 1.0 / (WEIGHTED ? fmax(m, (double)tau) : m);
@@ -143,7 +145,8 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
 #pragma unroll
           for (int j = 0; j < M; ++j) part += (double)ln.w[j];
           double c = wave_exclusive_scan_f64(part);
-          float sprev = lin ? 0.f : sin2pi_rev(xi * (c * inv));
+          // the element before a key >= 0 is the pad element, or lies behind it, or multiplies a zero key: same residual
+          float sprev = lin ? 0.f : sin2pi_rev(xi * ((c + pad_residual_at(rho, ln.k[0])) * inv));
 #pragma unroll
           for (int j = 0; j < M; ++j) {
             const bool valid = lane * M + j < Dtot;
@@ -151,7 +154,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
             if (lin) {
               acc += valid ? ln.w[j] * ln.k[j] : 0.f;
             } else {
-              const float s = sin2pi_rev(xi * (c * inv));
+              const float s = sin2pi_rev(xi * ((c + pad_residual_at(rho, ln.k[j])) * inv));
               acc += valid ? (s - sprev) * ln.k[j] : 0.f;
               sprev = s;
             }
@@ -264,7 +267,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
     if (D <= dlo) continue;                             // rows another kernel takes (the launcher passes 0: none)
     const int Dtot = WEIGHTED ? D + 1 : D;
     const int Dp = (int)pow2ceil((uint32_t)Dtot);       // >= 2 CAP: D > FSW_LDS_MAX_DEG = CAP; <= wave_bytes / 8 by the bin's bound
-    double m = (double)D;
+    double m = (double)D, rho = 0.0;
     float padw = 0.f;
     if constexpr (WEIGHTED) {
       double part = 0.0;
@@ -273,6 +276,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
       for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
       m = part;
       padw = (float)fmax((double)tau - m, 0.0);
+      rho = pad_residual((double)tau - m, padw);        // what the float line loses of the pad weight (fsw_common.h)
     }
     const double inv = 1.0 / (WEIGHTED ? fmax(m, (double)tau) : m);
     const float xif = freqs[k];
@@ -364,7 +368,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
 #pragma unroll
           for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
           carry += tot;
-          float sprev = lin ? 0.f : sin2pi_rev(xi * (c * inv));
+          float sprev = lin ? 0.f : sin2pi_rev(xi * ((c + pad_residual_at(rho, ln.k[0])) * inv));
 #pragma unroll
           for (int j = 0; j < M; ++j) {
             const bool valid = r0 + j < Dtot;
@@ -372,7 +376,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
             if (lin) {
               acc += valid ? ln.w[j] * ln.k[j] : 0.f;
             } else {
-              const float s = sin2pi_rev(xi * (c * inv));
+              const float s = sin2pi_rev(xi * ((c + pad_residual_at(rho, ln.k[j])) * inv));
               acc += valid ? (s - sprev) * ln.k[j] : 0.f;
               sprev = s;
             }

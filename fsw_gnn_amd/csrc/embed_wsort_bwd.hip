@@ -38,9 +38,11 @@ constexpr int kWbSplitY = 4;
 // WEIGHTED: weight_of(index) returns the element's weight, `cbase` is the cumulative weight before this lane's first
 // element on entry (only used when WEIGHTED).
 template <int M, bool WEIGHTED, class WeightFn, class EmitFn>
-__device__ __forceinline__ float walk_line(const WaveLine64<M>& ln, int r0, int D, int Dtot, double xi, double inv, float gi,
+__device__ __forceinline__ double walk_line(const WaveLine64<M>& ln, int r0, int D, int Dtot, double xi, double inv, float gi,
                                            double cbase, WeightFn weight_of, EmitFn emit) {
-  float gf = 0.f;
+  // float64 lane sum: the terms are as large as the sum, and where xi / D is a small fraction (1/4 on 16384 neighbours) they repeat with a
+  // short period along the ranks, so that the roundings of a float32 sum share a sign and grow like D (3.4e-5 of the terms there)
+  double gf = 0.0;
   double Fp, dFp;
   const FCoef fc(xi);
   if constexpr (!WEIGHTED) {
@@ -59,7 +61,7 @@ __device__ __forceinline__ float walk_line(const WaveLine64<M>& ln, int r0, int 
       F_dF_sc(fc, (double)min(r0 + j + 1, D) * inv, s, c, F, dF);
       if (r0 + j < D) {
         emit(ln.index(j), gi * (float)(F - Fp));
-        gf = fmaf(gi * (float)(dF - dFp), ln.key(j), gf);
+        gf = fma((double)gi * (dF - dFp), (double)ln.key(j), gf);
       }
       Fp = F;
       dFp = dF;
@@ -76,7 +78,7 @@ __device__ __forceinline__ float walk_line(const WaveLine64<M>& ln, int r0, int 
       F_dF(fc, c * inv, F, dF);
       if (valid) {
         if (id < D) emit(id, gi * (float)(F - Fp));   // the pad element (id == D) has no source row
-        gf = fmaf(gi * (float)(dF - dFp), ln.key(j), gf);
+        gf = fma((double)gi * (dF - dFp), (double)ln.key(j), gf);
       }
       Fp = F;
       dFp = dF;
@@ -128,6 +130,9 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
       __syncthreads();
     }
     const double inv = 1.0 / (WEIGHTED ? fmax(m, (double)tau) : m);
+    // the pad element's weight enters the float64 cumulative weights in float64, not as the float of wrow (fsw_common.h: pad_residual)
+    const double padd = WEIGHTED ? fmax((double)tau - m, 0.0) : 0.0;
+    auto weight_of = [&](int id) -> double { return id == D ? padd : (double)wrow[id + id / M]; };
 
     const int ngroups = (S + SC - 1) / SC;
     for (int grp = blockIdx.y; grp < ngroups; grp += gridDim.y) {
@@ -176,15 +181,15 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
 #pragma unroll
           for (int j = 0; j < M; ++j) {
             const int id = ln.index(j);
-            part += (lane * M + j < Dtot) ? (double)wrow[id + id / M] : 0.0;
+            part += (lane * M + j < Dtot) ? weight_of(id) : 0.0;
           }
           cbase = wave_exclusive_scan_f64(part);
         }
-        float gf = (FSW_WSB_ABL & 4) ? 0.f : walk_line<M, WEIGHTED>(
-            ln, lane * M, D, Dtot, xi, inv, gi, cbase, [&](int id) { return wrow[id + id / M]; },
+        double gf = (FSW_WSB_ABL & 4) ? 0.0 : walk_line<M, WEIGHTED>(
+            ln, lane * M, D, Dtot, xi, inv, gi, cbase, weight_of,
             [&](int id, float v) { line[id + id / M] = v; });   // every lane has read its keys: the line is free
         gf = wave_sum(gf);
-        if (lane == 0 && gfreq) atomicAdd(gfreq + k, gf);
+        if (lane == 0 && gfreq) atomicAdd(gfreq + k, (float)gf);
       }
       __syncthreads();
       for (int i = threadIdx.x; i < D * SC; i += blockDim.x) {
@@ -255,10 +260,10 @@ __global__ void __launch_bounds__(256, (M >= 32 ? 2 : (M >= 16 ? 3 : 4))) k_embe
     const double xi = (double)freqs[k];
     const float gi = out_scale * g[(int64_t)node * ldg + gcol0 + k];
     // every lane of THIS wavefront has read the line (the sort needed all keys): its places may take the results
-    float gf = walk_line<M, false>(
+    double gf = walk_line<M, false>(
         ln, lane * M, D, D, xi, 1.0 / (double)D, gi, 0.0, [](int) { return 0.f; }, [&](int id, float v) { xq[w][id] = v; });
     gf = wave_sum(gf);
-    if (lane == 0 && gfreq) atomicAdd(gfreq + k, gf);
+    if (lane == 0 && gfreq) atomicAdd(gfreq + k, (float)gf);
     __syncthreads();
     for (int e = threadIdx.x; e < D; e += blockDim.x)
       *reinterpret_cast<float4*>(gkey + (int64_t)(start + e) * ldk + k0) = make_float4(xq[0][e], xq[1][e], xq[2][e], xq[3][e]);
@@ -306,12 +311,12 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global_bwd(const int32_t* _
     const int Dtot = WEIGHTED ? D + 1 : D;
     const int Dp = (int)pow2ceil((uint32_t)Dtot);
     double m = (double)D;
-    float padw = 0.f;
+    double padw = 0.0;                                   // float64: it enters the float64 cumulative weights (fsw_common.h: pad_residual)
     if constexpr (WEIGHTED) {
       double part = 0.0;
       for (int t = lane; t < D; t += kWave) part += (double)(w ? w[start + t] : 1.f);
       m = wave_sum(part);
-      padw = (float)fmax((double)tau - m, 0.0);
+      padw = fmax((double)tau - m, 0.0);
     }
     const double inv = 1.0 / (WEIGHTED ? fmax(m, (double)tau) : m);
     const double xi = (double)freqs[k];
@@ -339,9 +344,9 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global_bwd(const int32_t* _
       for (int j = 0; j < M; ++j) se[c0 + lane * M + j] = ln.e[j];
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    float gf = 0.f;
+    double gf = 0.0;
     double carry = 0.0;
-    auto weight_of = [&](int id) { return id == D ? padw : (w ? w[start + id] : 1.f); };
+    auto weight_of = [&](int id) -> double { return id == D ? padw : (double)(w ? w[start + id] : 1.f); };
     for (int size = 2 * CAP; size <= Dp; size <<= 1) {
       sweep_pairs_b(se, Dp, size, 0, true);
       for (int st = size >> 2; st >= CAP; st >>= 1) sweep_pairs_b(se, Dp, size, st, false);
@@ -370,7 +375,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global_bwd(const int32_t* _
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
     gf = wave_sum(gf);
-    if (lane == 0 && gfreq) atomicAdd(gfreq + k, gf);
+    if (lane == 0 && gfreq) atomicAdd(gfreq + k, (float)gf);
     for (int t = lane; t < D; t += kWave) {
       const float v = sc[t];
       if (gkey) gkey[(int64_t)(start + t) * ldk + k] = v;

@@ -116,6 +116,16 @@ __device__ __forceinline__ float sin2pi_rev(double x) {
   return sinpif(2.f * (float)r);
 }
 
+// The pad element's weight max(tau - m, 0) lives in a float lane array next to the neighbours' float weights, but the cumulative
+// weight is a float64 sum and the phase 2 pi xi c magnifies what that rounding loses (3e-8 of the denominator) by 2 pi xi:
+// 1e-4 at xi = 511.  pad_residual: the part of the pad weight its float copy padw does not hold, exact in float64 (deficit = tau - m
+// in float64).  It is added to the cumulative weight from the pad element on.
+__device__ __forceinline__ double pad_residual(double deficit, float padw) { return fmax(deficit, 0.0) - (double)padw; }
+// Forward kernels: an element's coefficient is multiplied by its key, and every element with key == 0 contributes nothing, so
+// adding the residual to the cumulative weight of every element with key >= 0 (-0.0 included) is exact wherever the pad element
+// ranks among the zeros.  rho == 0 unless the row is deficient.
+__device__ __forceinline__ double pad_residual_at(double rho, float key) { return key >= 0.f ? rho : 0.0; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);

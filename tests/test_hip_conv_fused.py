@@ -252,7 +252,7 @@ def test_add_bias_act_grid_stride_and_no_rows(dev):
 
 # ---- 5. fsw_conv_fused_f32 --------------------------------------------------------------------------------------------------------
 def run_fused(dev, g, S, hm, Hout, bias=False, mass_fn=0, mass_scale=1.0, out_scale=1.0, yin=None, ldyin_pad=0, lin_bias=False, act=0,
-              slope=0.0, W1=None, yin_node=None, seed=0, mutate=None, reference=True):
+              slope=0.0, W1=None, yin_node=None, seed=0, mutate=None, reference=True, fr=None):
     """One call of fsw_conv_fused_f32 on the ladder graph g (ladder_graph).  yin: None, 'perm' (row p belongs to node perm[p]) or
     'node'.  mutate(args, call): edits the arguments before the call (refusal tests).  Returns a dict: rc, Y [rows, Hout + 3] as
     float32 numpy, and with reference=True E, A, Y_ref, bound.  Checks (vi): Yin, Wq and Xp are bitwise unchanged."""
@@ -263,7 +263,7 @@ def run_fused(dev, g, S, hm, Hout, bias=False, mass_fn=0, mass_scale=1.0, out_sc
     rng = np.random.default_rng(1000 * S + 10 * Hout + seed)
     ldp, ldt, ldy = S + 3, S + 1, Hout + 3
     Xp = R.keys(nc, ldp, seed=11 + S)
-    fr = R.freqs(S, seed=13 + S)
+    fr = R.freqs(S, seed=13 + S) if fr is None else np.asarray(fr, dtype=np.float32)     # fr: the S frequencies, instead of the drawn ones
     bias_h = rng.standard_normal(K).astype(np.float32) if bias else None
     if W1 is None:
         W1 = (rng.standard_normal((Hout, K)) / np.sqrt(K)).astype(np.float32)

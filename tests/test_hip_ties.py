@@ -20,8 +20,9 @@ Measured on an MI355X, largest per-entry error / line maximum over all degree cl
     stored key gradients against the atomic form: identical in every entry, every mode
     per row: forward <= 7.1e-7, gkey <= 8.5e-7, gfreq <= 2.2e-7 (Cartesian 7.1e-7); module level: gX per entry <= 0.05 of its bound
 The control column stays below the bound in every class, so no class has a bound of its own.  The largest figures belong to the rows
-of total mass 0.4: the kernels round the pad element's weight to float32 (6e-8), which shifts the phase 2 pi xi c of every element
-behind the pad by 2 pi xi * 4e-8 -- rounding, the same for tied and distinct keys, not an order effect.
+of total mass 0.4: when this was measured the kernels rounded the pad element's weight to float32 (6e-8), which shifts the phase
+2 pi xi c of every element behind the pad by 2 pi xi * 4e-8 -- rounding, the same for tied and distinct keys, not an order effect
+(since then the pad weight enters the cumulative weight in float64: tests/test_hip_large_freqs.py).
 """
 import ctypes
 import functools
@@ -113,12 +114,12 @@ def key_columns(rowptr, kinds=COLUMNS):
     return K
 
 
-def expected_bin_rows():
-    """Rows per degree bin of include/fsw_hip.h for DEGREES."""
+def expected_bin_rows(degrees=DEGREES):
+    """Rows per degree bin of include/fsw_hip.h for `degrees`."""
     from fsw_gnn_amd import _lib
     uppers = list(range(_lib.REG_MAX_DEG + 1)) + list(_lib.MID_SIZES) + [512, 1024, 2048, 4096, 8192, 16384, 32768, 1 << 62]
     rows = [0] * len(uppers)
-    for d in DEGREES:
+    for d in degrees:
         rows[next(i for i, u in enumerate(uppers) if d <= u)] += 1
     return rows
 
@@ -157,7 +158,7 @@ def check_key_gradients(got, ref, rowptr, columns, what, scale, row_bound=F32_BO
     assert (lm > 0).all(), what
     ratio = np.abs(got - ref) / lm
     ctrl = np.array([c == CONTROL for c in columns])
-    tied_cls = per_row(lambda a, b: ratio[a:b][:, ~ctrl].max(), rowptr)
+    tied_cls = per_row(lambda a, b: ratio[a:b][:, ~ctrl].max(), rowptr) if not ctrl.all() else np.zeros(deg.size)
     ctrl_cls = per_row(lambda a, b: ratio[a:b][:, ctrl].max(), rowptr) if ctrl.any() else np.zeros(deg.size)
     print("%s: row norm-wise max %.2e | per entry tied max %.2e (D = %d), control max %.2e (D = %d)" % (
         what, rows.max(), tied_cls.max(), deg[tied_cls.argmax()], ctrl_cls.max(), deg[ctrl_cls.argmax()]))
@@ -170,44 +171,51 @@ def check_key_gradients(got, ref, rowptr, columns, what, scale, row_bound=F32_BO
 
 # ---- the graph on the device and the oracle's answers, computed once per weight mode ----------------------------------------------
 @functools.lru_cache(maxsize=None)
-def tied_case(weights, kinds=COLUMNS):
+def tied_case(weights, kinds=COLUMNS, ladder=None, tau=None):
+    """ladder (tests/large_freq_cases.py: Ladder): another graph of one recipient per degree, with the ladder's own edge list for the
+    weight mode `weights` and its own len(kinds) key columns for (weights, tau); None: the graph of DEGREES and the columns `kinds`."""
     from fsw_gnn_amd import _lib, build_csr
     dev = torch.device("cuda:0")
-    rec, snd, w = edge_list(weights)
-    graph = build_csr(t(rec, dev, torch.int64), t(snd, dev, torch.int64), None if w is None else t(w, dev), len(DEGREES), NNZ)
+    degrees = DEGREES if ladder is None else ladder.degrees
+    nnz = sum(degrees)
+    rec, snd, w = edge_list(weights) if ladder is None else ladder.edge_list(weights)
+    graph = build_csr(t(rec, dev, torch.int64), t(snd, dev, torch.int64), None if w is None else t(w, dev), len(degrees), nnz)
     st = graph.read_stats()
-    assert st[_lib.STAT_FLAGS] == 0 and st[_lib.STAT_NNZ] == NNZ and st[_lib.STAT_MAX_DEGREE] == max(DEGREES)
+    assert st[_lib.STAT_FLAGS] == 0 and st[_lib.STAT_NNZ] == nnz and st[_lib.STAT_MAX_DEGREE] == max(degrees)
     rowptr = graph.rowptr.cpu().numpy().astype(np.int64)
-    assert tuple(np.diff(rowptr)) == DEGREES
+    assert tuple(np.diff(rowptr)) == degrees
     bins = np.diff(graph.bin_start_host[0]).tolist()
-    assert bins == expected_bin_rows()
-    assert bins[_lib.BIN_MID0:] == [2, 1, 1, 1, 0, 1, 1, 1, 3, 3, 3, 3, 2, 1, 1, 0, 0]   # mid, LDS, hub bins, global
-    col = graph.col[:NNZ].cpu().numpy().astype(np.int64)
-    assert np.array_equal(np.sort(col), np.arange(NNZ))            # every sender exactly once
-    for r in (5, 20, 31):                                          # the rows keep the order of the (shuffled) edge list
+    assert bins == expected_bin_rows(degrees)
+    if ladder is None:
+        assert bins[_lib.BIN_MID0:] == [2, 1, 1, 1, 0, 1, 1, 1, 3, 3, 3, 3, 2, 1, 1, 0, 0]   # mid, LDS, hub bins, global
+    col = graph.col[:nnz].cpu().numpy().astype(np.int64)
+    assert np.array_equal(np.sort(col), np.arange(nnz))            # every sender exactly once
+    for r in (5, 20, 31) if ladder is None else range(len(degrees)):   # the rows keep the order of the (shuffled) edge list
         assert np.array_equal(col[rowptr[r]:rowptr[r + 1]], snd[rec == r])
-    wv = np.ones(NNZ) if w is None else graph.w[:NNZ].cpu().numpy().astype(np.float64)
-    if w is not None:
+    wv = np.ones(nnz) if w is None else graph.w[:nnz].cpu().numpy().astype(np.float64)
+    if w is not None and ladder is None:
         assert (wv == 0).sum() >= 30
         for deg in LOW_MASS_ROWS:
             r = DEGREES.index(deg)
             assert abs(wv[rowptr[r]:rowptr[r + 1]].sum() - 0.4) < 1e-5
-    K = key_columns(rowptr, kinds)
-    Xp = np.zeros((NNZ, 64), dtype=np.float32)
+    if w is not None and ladder is not None:
+        assert np.array_equal(graph.w[:nnz].cpu().numpy(), w[np.argsort(rec, kind="stable")])      # the float32 weights, untouched
+    K = key_columns(rowptr, kinds) if ladder is None else ladder.key_columns(weights, tau, len(kinds))
+    Xp = np.zeros((nnz, 64), dtype=np.float32)
     Xp[col, :K.shape[1]] = K                                       # sender col[e] carries the keys of entry e
-    g = np.random.default_rng(43).standard_normal((len(DEGREES), HAS_MASS + 20)).astype(np.float32)
-    more = np.random.default_rng(44).standard_normal((len(DEGREES), 12)).astype(np.float32)     # columns 21 .. 32: Cartesian 4 x 8
+    g = np.random.default_rng(43).standard_normal((len(degrees), HAS_MASS + 20)).astype(np.float32)
+    more = np.random.default_rng(44).standard_normal((len(degrees), 12)).astype(np.float32)     # columns 21 .. 32: Cartesian 4 x 8
     g = np.concatenate([g, more], axis=1)
-    return {"graph": graph, "st": st, "rowptr": rowptr, "col": col, "w": wv, "K": K, "Xp": Xp, "g": g}
+    return {"graph": graph, "st": st, "rowptr": rowptr, "col": col, "w": wv, "K": K, "Xp": Xp, "g": g, "degrees": degrees, "nnz": nnz}
 
 
 @functools.lru_cache(maxsize=None)
-def diagonal_reference(weights, tau, S, freqs=FREQS, kinds=COLUMNS):
+def diagonal_reference(weights, tau, S, freqs=FREQS, kinds=COLUMNS, ladder=None):
     """Oracle (float64, entry order among equal keys) on the first S key columns (of kind kinds[:S], at freqs[:S]): out [rows, 1 + S],
     gkey [nnz, S], gfreq [S]."""
-    c = tied_case(weights, kinds)
+    c = tied_case(weights, kinds) if ladder is None else tied_case(weights, kinds, ladder, tau)
     K, fr, rowptr = c["K"][:, :S].astype(np.float64), np.array(freqs[:S]), c["rowptr"]
-    ident = np.arange(NNZ)                                         # the oracle's "features" are the keys of every entry
+    ident = np.arange(c["nnz"])                                       # the oracle's "features" are the keys of every entry
     emb, mass = O.fsw_embed_csr(K, rowptr, ident, c["w"], np.eye(S), fr, total_mass_pad_thresh=tau, return_mass=True)
     G = OUT_SCALE * c["g"][:, HAS_MASS:HAS_MASS + S].astype(np.float64)
     _, _, gxi, gkey = O.fsw_embed_csr_backward(K, rowptr, ident, c["w"], np.eye(S), fr, G, total_mass_pad_thresh=tau, return_gkey=True)
@@ -217,11 +225,11 @@ def diagonal_reference(weights, tau, S, freqs=FREQS, kinds=COLUMNS):
 
 
 @functools.lru_cache(maxsize=None)
-def cartesian_reference(weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS):
+def cartesian_reference(weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS, ladder=None):
     """The oracle through the diagonal identity of tests/test_cartesian_cpu.py: key column s repeated F times, freqs[:F] tiled;
     gkey[e, s] is the sum over f, gkey_sf [nnz, S, F] its terms."""
-    c = tied_case(weights, kinds)
-    S, rowptr = len(cols), c["rowptr"]
+    c = tied_case(weights, kinds) if ladder is None else tied_case(weights, kinds, ladder, tau)
+    S, rowptr, NNZ = len(cols), c["rowptr"], c["nnz"]
     K = np.repeat(c["K"][:, list(cols)].astype(np.float64), F, axis=1)        # column s F + f = key column s
     fr = np.tile(np.array(freqs[:F]), S)
     ident = np.arange(NNZ)
@@ -233,12 +241,12 @@ def cartesian_reference(weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS):
             "gkey_sf": gkey.reshape(NNZ, S, F)}
 
 
-def check_forward(got, ref, what):
+def check_forward(got, ref, what, degrees=DEGREES):
     assert np.isfinite(got).all()
-    errs = np.array([relerr(got[r], ref[r]) for r in range(len(DEGREES))])
-    print("%s: forward per row max %.2e (D = %d)" % (what, errs.max(), DEGREES[errs.argmax()]))
-    assert np.abs(got[0, HAS_MASS:]).max() == 0.0                 # the empty row
-    assert errs.max() <= TOL, (what, dict(zip(DEGREES, errs.tolist())))
+    errs = np.array([relerr(got[r], ref[r]) for r in range(len(degrees))])
+    print("%s: forward per row max %.2e (D = %d)" % (what, errs.max(), degrees[errs.argmax()]))
+    assert degrees[0] == 0 and np.abs(got[0, HAS_MASS:]).max() == 0.0      # the empty row
+    assert errs.max() <= TOL, (what, dict(zip(degrees, errs.tolist())))
 
 
 # ---- 2. kernel level ----------------------------------------------------------------------------------------------------------------
@@ -248,7 +256,7 @@ def embed_args(c, S, tau, fr, table, scratch):
     a = _lib.EmbedArgs()
     a.rowptr, a.col, a.perm, a.bin_start = graph.rowptr.data_ptr(), graph.col.data_ptr(), graph.perm.data_ptr(), graph.bin_start.data_ptr()
     a.w = graph.w.data_ptr() if graph.w is not None else None
-    a.num_rows, a.bin_start_host = len(DEGREES), graph.bin_start_host[0].ctypes.data
+    a.num_rows, a.bin_start_host = len(c["degrees"]), graph.bin_start_host[0].ctypes.data
     a.Xp, a.ldp, a.freqs, a.S, a.tau = c["Xp_dev"].data_ptr(), c["Xp_dev"].stride(0), fr.data_ptr(), S, tau
     a.unit_table, a.ldt = (table.data_ptr(), table.stride(0)) if table is not None else (None, 0)
     a.out_scale, a.has_mass, a.mass_fn, a.mass_scale = OUT_SCALE, HAS_MASS, 0, 1.0
@@ -258,13 +266,14 @@ def embed_args(c, S, tau, fr, table, scratch):
     return a
 
 
-def run_tuned_kernels(dev, weights, tau, S, freqs=FREQS, kinds=COLUMNS):
-    """fsw_embed_f32, fsw_embed_backward_f32 and fsw_embed_backward_keys_f32 on the graph of DEGREES, key columns kinds[:S], frequencies
-    freqs[:S]: (out [rows, 1 + S], gkey read back from the atomic form [nnz, S], stored gkey [nnz, S], {name: gfreq [S]}), float64."""
+def run_tuned_kernels(dev, weights, tau, S, freqs=FREQS, kinds=COLUMNS, ladder=None):
+    """fsw_embed_f32, fsw_embed_backward_f32 and fsw_embed_backward_keys_f32 on the graph of DEGREES (or of `ladder`), key columns
+    kinds[:S], frequencies freqs[:S]: (out [rows, 1 + S], gkey read back from the atomic form [nnz, S], stored gkey [nnz, S],
+    {name: gfreq [S]}), float64."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
-    c = dict(tied_case(weights, kinds))
-    col = c["col"]
+    c = dict(tied_case(weights, kinds) if ladder is None else tied_case(weights, kinds, ladder, tau))
+    col, DEGREES, NNZ = c["col"], c["degrees"], c["nnz"]
     stream = torch.cuda.current_stream(dev).cuda_stream
     c["Xp_dev"] = t(c["Xp"], dev)
     fr = t(np.array(freqs[:S]), dev)
@@ -325,14 +334,13 @@ def test_tuned_kernels_on_tied_keys(dev, weights, tau, S):
         assert e <= F32_BOUND, (what, name, e)
 
 
-def run_generic_kernel(dev, weights, tau, storage, freqs=FREQS, kinds=COLUMNS):
-    """fsw_embed_generic, forward and backward, on the plain CSR of the graph of DEGREES, the 8 key columns `kinds` and frequencies
-    `freqs`: (out [rows, 9], gkey [nnz, 8], gfreq [8]) in the storage type."""
+def run_generic_kernel(dev, weights, tau, storage, freqs=FREQS, kinds=COLUMNS, ladder=None, S=8):
+    """fsw_embed_generic, forward and backward, on the plain CSR of the graph of DEGREES (or of `ladder`), the S key columns `kinds`
+    and frequencies `freqs`: (out [rows, 1 + S], gkey [nnz, S], gfreq [S]) in the storage type."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
-    S = 8
-    c = tied_case(weights, kinds)
-    graph = c["graph"]
+    c = tied_case(weights, kinds) if ladder is None else tied_case(weights, kinds, ladder, tau)
+    graph, DEGREES, NNZ = c["graph"], c["degrees"], c["nnz"]
     dt = torch.float64 if storage == "float64" else torch.float32
     stream = torch.cuda.current_stream(dev).cuda_stream
     Xp = t(c["Xp"], dev, dt)
@@ -395,14 +403,15 @@ def test_generic_kernel_on_tied_keys(dev, weights, tau, storage):
 CART_COLUMNS = [(0, 1, 2, 5), (3, 4, 6, 5)]      # indices into COLUMNS: (a, b, c, e) and (d_up, d_down, b, e)
 
 
-def run_cartesian_kernels(dev, weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS):
+def run_cartesian_kernels(dev, weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS, ladder=None, flags=0):
     """fsw_embed_cart_f32 and fsw_embed_cart_backward_keys_f32, S = len(cols) slices (key columns cols of `kinds`) x F frequencies
-    freqs[:F], on the graph of DEGREES: (out [rows, 1 + S F], gkey [nnz, S], gfreq [F])."""
+    freqs[:F], on the graph of DEGREES (or of `ladder`): (out [rows, 1 + S F], gkey [nnz, S], gfreq [F]).  flags: fsw_cart_args.flags
+    of both calls (the split forms of the longest rows); the scratch then also holds what every split query asks for."""
     from fsw_gnn_amd import _lib
     L = _lib.lib()
     S = len(cols)
-    c = tied_case(weights, kinds)
-    graph, st = c["graph"], c["st"]
+    c = tied_case(weights, kinds) if ladder is None else tied_case(weights, kinds, ladder, tau)
+    graph, st, DEGREES, NNZ = c["graph"], c["st"], c["degrees"], c["nnz"]
     stream = torch.cuda.current_stream(dev).cuda_stream
     Xp_host = np.zeros((NNZ, 32), dtype=np.float32)
     Xp_host[:, :S] = c["Xp"][:, list(cols)]
@@ -416,11 +425,11 @@ def run_cartesian_kernels(dev, weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS
         dtable = torch.empty_like(table)
         _lib.check(L.fsw_unit_coeff_table(_lib.ptr(fr), F, _lib.REG_MAX_DEG, _lib.ptr(table), F, stream), "fsw_unit_coeff_table")
         _lib.check(L.fsw_unit_dcoeff_table(_lib.ptr(fr), F, _lib.REG_MAX_DEG, _lib.ptr(dtable), F, stream), "fsw_unit_dcoeff_table")
-    scratch = torch.empty(int(L.fsw_embed_cart_generic_scratch_bytes(max(DEGREES), len(DEGREES))), dtype=torch.uint8, device=dev)
+    scratch = None
 
     def args():
         a = _lib.CartArgs()
-        a.value_dtype, a.S, a.F, a.has_mass = 0, S, F, HAS_MASS
+        a.value_dtype, a.S, a.F, a.has_mass, a.flags = 0, S, F, HAS_MASS, flags
         a.rowptr, a.col, a.w = graph.rowptr.data_ptr(), graph.col.data_ptr(), graph.w.data_ptr() if graph.w is not None else None
         a.perm, a.bin_start, a.bin_start_host = graph.perm.data_ptr(), graph.bin_start.data_ptr(), graph.bin_start_host[0].ctypes.data
         a.num_rows, a.max_degree = len(DEGREES), st[_lib.STAT_MAX_DEGREE]
@@ -428,9 +437,16 @@ def run_cartesian_kernels(dev, weights, tau, cols, F, freqs=FREQS, kinds=COLUMNS
         a.mass_fn, a.mass_scale = 0, 1.0
         if table is not None:
             a.unit_table, a.ldt = table.data_ptr(), F
-        a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        if scratch is not None:
+            a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
         return a
 
+    nbytes = int(L.fsw_embed_cart_generic_scratch_bytes(max(DEGREES), len(DEGREES)))
+    if flags:
+        queries = (L.fsw_embed_cart_split_scratch_bytes, L.fsw_embed_cart_split_backward_scratch_bytes,
+                   L.fsw_embed_cart_split_w_scratch_bytes, L.fsw_embed_cart_split_w_backward_scratch_bytes)
+        nbytes = max([nbytes] + [int(q(ctypes.byref(args()))) for q in queries])
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.full((len(DEGREES), HAS_MASS + S * F), float("nan"), device=dev)
     a = args()
     a.out, a.ldo = out.data_ptr(), out.stride(0)
