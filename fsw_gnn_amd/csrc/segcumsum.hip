@@ -455,16 +455,13 @@ __global__ void k_legacy_add_block_sums(V* __restrict__ output, const V* __restr
 template <class V>
 static int64_t seg_tile_elems() { return (int64_t)kSegThreads * (sizeof(V) == 4 ? 16 : 8); }   // = TILE of k_segscan_chained
 
+// The persistent grid of k_segscan_chained<V, I, REV, .> on the current device: every workgroup must be resident (the look-back
+// spins on predecessors).  4 workgroups of 256 threads per CU need <= 128 registers and no LDS to speak of; the occupancy query
+// guards against surprises.  The grid is a property of (kernel instantiation, DEVICE): one atomic slot per device ordinal, so a
+// process that drives several GPUs -- or several host threads -- never sizes the grid of one device by another's CU count (a
+// benign race: every writer stores the same value).  The launcher and fsw_segcumsum_geometry both come here.
 template <class V, class I, bool REV>
-static int launch_segscan(const void* values, void* out, const void* ids, int64_t n, void* ws, hipStream_t stream) {
-  const int64_t ntiles = ceil_div(n, seg_tile_elems<V>());
-  unsigned long long* desc = reinterpret_cast<unsigned long long*>(ws);
-  FSW_CHECK_HIP(hipMemsetAsync(desc, 0, sizeof(unsigned long long) * DescWords<V>::kWords * (size_t)ntiles, stream));
-  // persistent grid: every workgroup must be resident (the look-back spins on predecessors).  4 workgroups of 256
-  // threads per CU need <= 128 registers and no LDS to speak of; the occupancy query guards against surprises.
-  // The grid is a property of (kernel instantiation, DEVICE): one atomic slot per device ordinal, so a process that drives
-  // several GPUs -- or several host threads -- never sizes the grid of one device by another's CU count (a benign race:
-  // every writer stores the same value).
+static int seg_resident_workgroups(int* resident_out) {
   static std::atomic<int> grid_cache[kMaxDevices];
   int dev = 0;
   FSW_CHECK_HIP(hipGetDevice(&dev));
@@ -476,6 +473,17 @@ static int launch_segscan(const void* values, void* out, const void* ids, int64_
     resident = std::max(1, cus) * std::max(1, std::min(per_cu - 1, kSegMaxWgPerCu));   // one below the query: it can be one high (MI355X guide)
     if (dev >= 0 && dev < kMaxDevices) grid_cache[dev].store(resident, std::memory_order_relaxed);
   }
+  *resident_out = resident;
+  return 0;
+}
+
+template <class V, class I, bool REV>
+static int launch_segscan(const void* values, void* out, const void* ids, int64_t n, void* ws, hipStream_t stream) {
+  const int64_t ntiles = ceil_div(n, seg_tile_elems<V>());
+  unsigned long long* desc = reinterpret_cast<unsigned long long*>(ws);
+  FSW_CHECK_HIP(hipMemsetAsync(desc, 0, sizeof(unsigned long long) * DescWords<V>::kWords * (size_t)ntiles, stream));
+  int resident = 0;
+  if (int rc = seg_resident_workgroups<V, I, REV>(&resident)) return rc;
   const unsigned grid = (unsigned)std::min<int64_t>(ntiles, resident);
   // vector accesses (EPL elements per lane): aligned pointers, and scanning from the end the groups must start on a multiple of EPL
   constexpr int EPL = SegTile<V, I>::EPL;
@@ -491,6 +499,19 @@ static int launch_segscan(const void* values, void* out, const void* ids, int64_
   else
     k_segscan_chained<V, I, REV, false><<<grid, kSegThreads, 0, stream>>>((const V*)values, (V*)out, (const I*)ids, n, desc, ntiles, use_halo);
   FSW_LAUNCH_CHECK();
+  return 0;
+}
+
+template <class V, class I>
+static int seg_geometry(int reverse, int32_t out[4]) {
+  using T = SegTile<V, I>;
+  static_assert(T::TILE == (int)kSegThreads * (sizeof(V) == 4 ? 16 : 8), "seg_tile_elems is the kernel's TILE");
+  int resident = 0;
+  if (int rc = reverse ? seg_resident_workgroups<V, I, true>(&resident) : seg_resident_workgroups<V, I, false>(&resident)) return rc;
+  out[0] = T::EPL;
+  out[1] = T::GRP;
+  out[2] = T::TILE;
+  out[3] = resident;
   return 0;
 }
 
@@ -523,6 +544,16 @@ extern "C" int fsw_segcumsum(int value_dtype, const void* values, void* out, con
   if (value_dtype == 0) return run_segcumsum<float, int64_t>(values, out, segment_ids, n, reverse, workspace, stream);
   if (id_bytes == 4) return run_segcumsum<double, int32_t>(values, out, segment_ids, n, reverse, workspace, stream);
   return run_segcumsum<double, int64_t>(values, out, segment_ids, n, reverse, workspace, stream);
+}
+
+extern "C" int fsw_segcumsum_geometry(int value_dtype, int id_bytes, int reverse, int32_t out[4]) {
+  FSW_REQUIRE(out, "fsw_segcumsum_geometry: null pointer");
+  FSW_REQUIRE((value_dtype == 0 || value_dtype == 1) && (id_bytes == 4 || id_bytes == 8),
+              "fsw_segcumsum_geometry: value_dtype must be 0 (float32) or 1 (float64), id_bytes 4 or 8");
+  if (value_dtype == 0 && id_bytes == 4) return seg_geometry<float, int32_t>(reverse, out);
+  if (value_dtype == 0) return seg_geometry<float, int64_t>(reverse, out);
+  if (id_bytes == 4) return seg_geometry<double, int32_t>(reverse, out);
+  return seg_geometry<double, int64_t>(reverse, out);
 }
 
 // ---- legacy ABI (reference fsw_embedding.cu:194, 212, 231): default stream, synchronous, void -----------

@@ -674,6 +674,11 @@ int fsw_edge_keys_f32(const int32_t* col, int64_t nnz, const float* Xp, int64_t 
 size_t fsw_segcumsum_workspace_bytes(int64_t n);
 int fsw_segcumsum(int value_dtype, const void* values, void* out, const void* segment_ids, int id_bytes,
                   int64_t n, int reverse, void* workspace, size_t workspace_bytes, fsw_stream_t stream);
+/* Shape of the scan for one (value_dtype, id_bytes, reverse), for tests that place segment boundaries where the kernel
+ * branches: out = { elements per lane and load, elements per group of 64 lanes (the halo), elements per tile,
+ * workgroups of the persistent grid on the current device for a large n }.  A wavefront's chunk is a quarter of a tile.
+ * No launch; the last value comes from the occupancy computation that fsw_segcumsum itself uses. */
+int fsw_segcumsum_geometry(int value_dtype, int id_bytes, int reverse, int32_t out[4]);
 
 /* ---- legacy entry points: exact signatures of reference fsw_embedding.cu:194, 212, 231 ------------
  * Same semantics as the reference kernels (block-local segmented scan + carry add), launched on the

@@ -17,7 +17,7 @@ import shutil
 import subprocess
 import sys
 
-UNITS = [(f, "", f) for f in ("api graph_build project embed_reg embed_wsort embed_generic embed_wsort_bwd embed_api conv_fused "
+UNITS = [(f, "", f) for f in ("api graph_build graph_import project embed_reg embed_wsort embed_generic embed_wsort_bwd embed_api conv_fused "
                               "embed_bwd segcumsum gemm_tn embed_cart embed_cart_bwd embed_cart_hub embed_cart_hub_bwd embed_cart_hub_w "
                               "embed_cart_hub_w_bwd embed_giant_cart embed_split_cart embed_giant_cart_w embed_split_cart_w embed_giant_cart_bwd embed_split_cart_bwd embed_split_cart_w_bwd edge_keys").split()]
 UNITS += [("embed_mid", "-DFSW_MID_PART=%d" % p, "embed_mid_%d" % p) for p in range(3)]
