@@ -1,6 +1,7 @@
 // What the forward (embed_cart.hip, embed_cart_hub.hip, embed_cart_hub_w.hip, embed_giant_cart.hip, embed_split_cart.hip, embed_giant_cart_w.hip, embed_split_cart_w.hip) and the tuned backward (embed_cart_bwd.hip,
 // embed_cart_hub_bwd.hip, embed_cart_hub_w_bwd.hip, embed_giant_cart_bwd.hip, embed_split_cart_bwd.hip, embed_split_cart_w_bwd.hip) of Cartesian mode share: the degree classes, the
-// constant-address-space reads of wave-uniform tables and the host helpers of the entry points.  gfx950.
+// constant-address-space reads of wave-uniform tables, the row lookup of the split forms and the host helpers of the entry points and of
+// the 13 launchers (the fill of a kernel's argument struct from fsw_cart_args, the plans of the split forms).  gfx950.
 #pragma once
 #include <algorithm>
 #include "embed_launch.h"
@@ -96,6 +97,30 @@ constexpr CartLongMode kCartLong[2] = {
 };
 constexpr const CartLongMode& cart_long_mode(bool unit_fast) { return kCartLong[unit_fast ? 0 : 1]; }
 inline bool cart_unit_fast(const fsw_cart_args* c) { return c->w == nullptr && c->tau <= 1.0; }
+
+// The fields that every launcher copies from fsw_cart_args into its kernel's argument struct T, by name: the inputs (cart_fill_inputs_w:
+// with w and tau, for the structs of general weights), the forward's outputs, the backward's gradients.  What else T holds (tables,
+// scratch, the class's rows) is the launcher's.
+template <class T>
+void cart_fill_inputs(T& t, const fsw_cart_args* c) {
+  t.rowptr = c->rowptr; t.col = c->col; t.perm = c->perm; t.bin_start = c->bin_start;
+  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F;
+}
+template <class T>
+void cart_fill_inputs_w(T& t, const fsw_cart_args* c) {
+  cart_fill_inputs(t, c);
+  t.w = (const float*)c->w; t.tau = (float)c->tau;
+}
+template <class T>
+void cart_fill_outputs(T& t, const fsw_cart_args* c) {
+  t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
+  t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
+}
+template <class T>
+void cart_fill_grads(T& t, const fsw_cart_args* c) {
+  t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
+  t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
+}
 
 constexpr bool cart_long_table_ok(const CartLongMode& m, int max_line) {
   if (m.cls[0].dlo + m.pad != kCartMaxLine || m.last().dhi + m.pad != max_line) return false;   // from the wavefront path to max_line
@@ -198,6 +223,37 @@ inline int cart_giant_plan(const fsw_cart_args* c, const CartLongMode& m, int64_
   return 0;
 }
 
+// ---- what the four split plans below start with (host values only: bin_start_host, max_degree, w, tau, S, F).  lines == 0, no split
+// form for this call: no arguments, the other weight mode, no row of the giant class, or regions above 2 GiB (kCartSplitCap: as
+// fsw_embed_cart_forward_scratch_bytes and fsw_embed_cart_backward_keys_scratch_bytes) ----------------------------------------------
+constexpr size_t kCartSplitCap = (size_t)2 << 30;
+constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+struct CartSplitBase {
+  int64_t rows, lines;                                        // rows from the giant class's first bin on; x S
+  size_t line_bytes;                                          // of one line's regions: line_bytes_of(mode, max_degree)
+};
+inline CartSplitBase cart_split_base(const fsw_cart_args* c, bool unit, size_t (*line_bytes_of)(const CartLongMode&, int64_t)) {
+  CartSplitBase b = {};
+  if (!c || !c->bin_start_host || cart_unit_fast(c) != unit || c->S < 1 || c->F < 1) return b;
+  const CartLongMode& m = cart_long_mode(unit);
+  const int64_t rows = cart_giant_rows(c, m);
+  if (rows <= 0) return b;
+  const size_t line_bytes = line_bytes_of(m, c->max_degree);
+  const int64_t lines = rows * c->S;
+  if (line_bytes > kCartSplitCap || (size_t)lines > kCartSplitCap / line_bytes) return b;
+  b.rows = rows; b.lines = lines; b.line_bytes = line_bytes;
+  return b;
+}
+
+// The row at position p of perm as the kernels of the four split forms look it up: l.node, l.start, l.D.  What a form needs on top (the
+// slice, the line's blocks or runs, the skip rule against ITS line size) is its own
+template <class A, class L>
+__device__ __forceinline__ void cart_row_at(const A& a, int p, L& l) {
+  l.node = a.perm[p];
+  l.start = a.rowptr[l.node];
+  l.D = a.rowptr[l.node + 1] - l.start;
+}
+
 // ---- split form of the giant class's forward, unit weights (embed_split_cart.hip; args->flags & FSW_CART_SPLIT_LINES): every phase of
 // k_cart_giant is a launch of its own over (line, block), so one long line keeps many workgroups busy.  Every line owns a scratch
 // region of line_bytes; the per-block partial sums [lines][nbmax][F] follow the regions -------------------------------------------------
@@ -209,22 +265,15 @@ struct CartSplitPlan {
   size_t partial_offset;                                      // bytes: where the partial sums begin (16-byte aligned)
   size_t bytes;                                               // fsw_embed_cart_split_scratch_bytes
 };
-// host values only (bin_start_host, max_degree, w, tau, S, F).  No split form: general weights, no row of the class, or above 2 GiB
 inline CartSplitPlan cart_split_plan(const fsw_cart_args* c) {
   CartSplitPlan p = {};
-  if (!c || !c->bin_start_host || !cart_unit_fast(c) || c->S < 1 || c->F < 1) return p;
-  const CartLongMode& m = kCartLong[0];
-  const int64_t rows = cart_giant_rows(c, m);
-  if (rows <= 0) return p;
-  const size_t cap = (size_t)2 << 30;                          // as fsw_embed_cart_forward_scratch_bytes
-  const size_t line_bytes = cart_giant_line_bytes(m, c->max_degree);
-  const int64_t lines = rows * c->S;
-  if (line_bytes > cap || (size_t)lines > cap / line_bytes) return p;
-  const int64_t nbmax = (int64_t)(line_bytes / (kCartGiantBlk * sizeof(float)));
-  const size_t offset = ((size_t)lines * line_bytes + 15) & ~(size_t)15;
-  const size_t partial = (size_t)lines * (size_t)nbmax * (size_t)c->F * sizeof(float);   // lines * nbmax <= 2^14, F < 2^31
-  if (offset + partial > cap) return p;
-  p.lines = lines; p.line_bytes = line_bytes; p.nbmax = (int)nbmax; p.partial_offset = offset; p.bytes = offset + partial;
+  const CartSplitBase b = cart_split_base(c, true, cart_giant_line_bytes);
+  if (b.lines <= 0) return p;
+  const int64_t nbmax = (int64_t)(b.line_bytes / (kCartGiantBlk * sizeof(float)));
+  const size_t offset = up16((size_t)b.lines * b.line_bytes);
+  const size_t partial = (size_t)b.lines * (size_t)nbmax * (size_t)c->F * sizeof(float);   // lines * nbmax <= 2^14, F < 2^31
+  if (offset + partial > kCartSplitCap) return p;
+  p.lines = b.lines; p.line_bytes = b.line_bytes; p.nbmax = (int)nbmax; p.partial_offset = offset; p.bytes = offset + partial;
   return p;
 }
 // embed_split_cart.hip: the giant class of kCartLong[0] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)
@@ -246,27 +295,20 @@ struct CartSplitWPlan {
   size_t tsum_offset, partial_offset, mass_offset;            // bytes: where the tile sums, the partial sums and the mass pieces begin
   size_t bytes;                                               // fsw_embed_cart_split_w_scratch_bytes
 };
-// host values only (bin_start_host, max_degree, w, tau, S, F).  No split form: unit weights with tau <= 1, no row of the class, or above 2 GiB
 inline CartSplitWPlan cart_split_w_plan(const fsw_cart_args* c) {
   CartSplitWPlan p = {};
-  if (!c || !c->bin_start_host || cart_unit_fast(c) || c->S < 1 || c->F < 1) return p;
-  const CartLongMode& m = kCartLong[1];
-  const int64_t rows = cart_giant_rows(c, m);
-  if (rows <= 0) return p;
-  const size_t cap = (size_t)2 << 30;                          // as fsw_embed_cart_forward_scratch_bytes
-  const size_t line_bytes = cart_giant_line_bytes(m, c->max_degree);
-  const int64_t lines = rows * c->S;
-  if (line_bytes > cap || (size_t)lines > cap / line_bytes) return p;
-  const int64_t elems = (int64_t)(line_bytes / (4 * sizeof(float)));
+  const CartSplitBase b = cart_split_base(c, false, cart_giant_line_bytes);
+  if (b.lines <= 0) return p;
+  const size_t cap = kCartSplitCap, lines = (size_t)b.lines;
+  const int64_t elems = (int64_t)(b.line_bytes / (4 * sizeof(float)));
   const int64_t nbmax = elems / kCartGiantWBlk, tiles = elems / kCartSplitWTile;
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t regions = (size_t)lines * line_bytes;           // a multiple of 16
-  const size_t tsum = up16((size_t)lines * (size_t)tiles * sizeof(double));             // lines * tiles <= 2^15
-  if ((size_t)c->F > cap / ((size_t)lines * (size_t)tiles * sizeof(float))) return p;
-  const size_t partial = up16((size_t)lines * (size_t)tiles * (size_t)c->F * sizeof(float));
-  const size_t mass = up16((size_t)rows * (size_t)nbmax * sizeof(double));
+  const size_t regions = lines * b.line_bytes;                 // a multiple of 16
+  const size_t tsum = up16(lines * (size_t)tiles * sizeof(double));                      // lines * tiles <= 2^15
+  if ((size_t)c->F > cap / (lines * (size_t)tiles * sizeof(float))) return p;
+  const size_t partial = up16(lines * (size_t)tiles * (size_t)c->F * sizeof(float));
+  const size_t mass = up16((size_t)b.rows * (size_t)nbmax * sizeof(double));
   if (regions + tsum + partial + mass > cap) return p;
-  p.lines = lines; p.rows = rows; p.cap = elems; p.nbmax = (int)nbmax; p.tiles = (int)tiles;
+  p.lines = b.lines; p.rows = b.rows; p.cap = elems; p.nbmax = (int)nbmax; p.tiles = (int)tiles;
   p.tsum_offset = regions; p.partial_offset = regions + tsum; p.mass_offset = regions + tsum + partial;
   p.bytes = regions + tsum + partial + mass;
   return p;
@@ -321,23 +363,16 @@ struct CartSplitBwdPlan {
   size_t partial_offset;                                      // bytes: where the partial sums begin (16-byte aligned)
   size_t bytes;                                               // fsw_embed_cart_split_backward_scratch_bytes: the rows of the other classes included
 };
-// host values only (bin_start_host, max_degree, w, tau, S, F).  No split form: general weights, no row of the class, or above 2 GiB
 inline CartSplitBwdPlan cart_split_bwd_plan(const fsw_cart_args* c) {
   CartSplitBwdPlan p = {};
-  if (!c || !c->bin_start_host || !cart_unit_fast(c) || c->S < 1 || c->F < 1) return p;
-  const CartLongMode& m = kCartLong[0];
-  const int64_t rows = cart_giant_rows(c, m);
-  if (rows <= 0) return p;
-  const size_t cap = (size_t)2 << 30;                          // as fsw_embed_cart_backward_keys_scratch_bytes
-  const size_t line_bytes = cart_giant_bwd_line_bytes(m, c->max_degree);
-  const int64_t lines = rows * c->S;
-  if (line_bytes > cap || (size_t)lines > cap / line_bytes) return p;
+  const CartSplitBase b = cart_split_base(c, true, cart_giant_bwd_line_bytes);
+  if (b.lines <= 0) return p;
   const int64_t ntmax = ceil_div(c->max_degree, (int64_t)kCartSplitBwdWalk);
-  const size_t offset = (size_t)lines * line_bytes;            // a multiple of 16
-  const size_t partial = ((size_t)lines * (size_t)ntmax * (size_t)c->F * sizeof(float) + 15) & ~(size_t)15;   // lines * ntmax < 2^16, F < 2^31
-  if (offset + partial > cap) return p;
-  p.lines = lines; p.line_bytes = line_bytes; p.ntmax = (int)ntmax; p.partial_offset = offset;
-  p.bytes = std::max(offset + partial, cart_line_classes_bwd_bytes(c, m));
+  const size_t offset = (size_t)b.lines * b.line_bytes;        // a multiple of 16
+  const size_t partial = up16((size_t)b.lines * (size_t)ntmax * (size_t)c->F * sizeof(float));   // lines * ntmax < 2^16, F < 2^31
+  if (offset + partial > kCartSplitCap) return p;
+  p.lines = b.lines; p.line_bytes = b.line_bytes; p.ntmax = (int)ntmax; p.partial_offset = offset;
+  p.bytes = std::max(offset + partial, cart_line_classes_bwd_bytes(c, kCartLong[0]));
   return p;
 }
 // embed_split_cart_bwd.hip: the giant class of kCartLong[0] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)
@@ -359,28 +394,21 @@ struct CartSplitWBwdPlan {
   size_t mass_offset, tsum_offset, partial_offset;            // bytes: where the mass pieces, the tile sums and the partial sums begin
   size_t bytes;                                               // fsw_embed_cart_split_w_backward_scratch_bytes: the rows of the classes below included
 };
-// host values only (bin_start_host, max_degree, w, tau, S, F).  No split form: unit weights with tau <= 1, no row of the class, or above 2 GiB
 inline CartSplitWBwdPlan cart_split_w_bwd_plan(const fsw_cart_args* c) {
   CartSplitWBwdPlan p = {};
-  if (!c || !c->bin_start_host || cart_unit_fast(c) || c->S < 1 || c->F < 1) return p;
-  const CartLongMode& m = kCartLong[1];
-  const int64_t rows = cart_giant_rows(c, m);
-  if (rows <= 0) return p;
-  const size_t cap = (size_t)2 << 30;                          // as fsw_embed_cart_backward_keys_scratch_bytes
-  const size_t line_bytes = cart_giant_bwd_line_bytes(m, c->max_degree);
-  const int64_t lines = rows * c->S;
-  if (line_bytes > cap || (size_t)lines > cap / line_bytes) return p;
-  const int64_t words = (int64_t)(line_bytes / kCartGiantBwdElemBytes), tiles = words / kCartSplitWBwdWalk;
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t regions = (size_t)lines * line_bytes;           // a multiple of 16
-  const size_t mass = up16((size_t)rows * (size_t)tiles * sizeof(double));               // lines * tiles <= 2^16
-  const size_t tsum = up16((size_t)lines * (size_t)tiles * sizeof(double));
-  if ((size_t)c->F > cap / ((size_t)lines * (size_t)tiles * sizeof(float))) return p;
-  const size_t partial = up16((size_t)lines * (size_t)tiles * (size_t)c->F * sizeof(float));
+  const CartSplitBase b = cart_split_base(c, false, cart_giant_bwd_line_bytes);
+  if (b.lines <= 0) return p;
+  const size_t cap = kCartSplitCap, lines = (size_t)b.lines;
+  const int64_t words = (int64_t)(b.line_bytes / kCartGiantBwdElemBytes), tiles = words / kCartSplitWBwdWalk;
+  const size_t regions = lines * b.line_bytes;                 // a multiple of 16
+  const size_t mass = up16((size_t)b.rows * (size_t)tiles * sizeof(double));             // lines * tiles <= 2^16
+  const size_t tsum = up16(lines * (size_t)tiles * sizeof(double));
+  if ((size_t)c->F > cap / (lines * (size_t)tiles * sizeof(float))) return p;
+  const size_t partial = up16(lines * (size_t)tiles * (size_t)c->F * sizeof(float));
   if (regions + mass + tsum + partial > cap) return p;
-  p.lines = lines; p.rows = rows; p.words = words; p.tiles = (int)tiles;
+  p.lines = b.lines; p.rows = b.rows; p.words = words; p.tiles = (int)tiles;
   p.mass_offset = regions; p.tsum_offset = regions + mass; p.partial_offset = regions + mass + tsum;
-  p.bytes = std::max(regions + mass + tsum + partial, cart_line_classes_bwd_bytes(c, m));
+  p.bytes = std::max(regions + mass + tsum + partial, cart_line_classes_bwd_bytes(c, kCartLong[1]));
   return p;
 }
 // embed_split_cart_w_bwd.hip: the giant class of kCartLong[1] in the split form, out of c->scratch (>= p.bytes, 16-byte aligned: checked by the caller)

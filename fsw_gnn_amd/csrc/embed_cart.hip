@@ -417,10 +417,9 @@ extern "C" int fsw_embed_cart_f32(const fsw_cart_args* c, fsw_stream_t stream_) 
   }
 
   CartTuned t;
-  t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
-  t.table = c->unit_table; t.ldt = c->ldt; t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias;
-  t.out_scale = (float)c->out_scale; t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
+  cart_fill_inputs_w(t, c);
+  cart_fill_outputs(t, c);
+  t.table = c->unit_table; t.ldt = c->ldt;
 
   // rows of in-degree 0: the embedding of the pad element alone is 0 -> out_scale * bias (mass column: f(0) = 0)
   if (bs[1] > bs[0]) {

@@ -416,11 +416,9 @@ extern "C" int fsw_embed_cart_backward_keys_f32(const fsw_cart_args* c, const fl
   }
 
   CartBwd t;
-  t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
+  cart_fill_inputs_w(t, c);
+  cart_fill_grads(t, c);
   t.table = c->unit_table; t.dtable = unit_dtable; t.ldt = c->ldt; t.lddt = lddt;
-  t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
-  t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
 
   // 1 <= D <= 32: one lane per (row, slice); grid = the exact number of tiles of every degree bin
   int64_t tiles = 0;

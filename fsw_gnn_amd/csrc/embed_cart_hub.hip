@@ -96,10 +96,8 @@ int launch_cart_hub_class(const CartHub& t, const CartLongClass& k, int64_t rows
 int launch_cart_hub(const fsw_cart_args* c, hipStream_t stream) {
   const int32_t* bs = c->bin_start_host;
   CartHub t;
-  t.rowptr = c->rowptr; t.col = c->col; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F;
-  t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
-  t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
+  cart_fill_inputs(t, c);
+  cart_fill_outputs(t, c);
   constexpr decltype(&launch_cart_hub_class<2>) launch[] = {launch_cart_hub_class<2>, launch_cart_hub_class<4>, launch_cart_hub_class<8>,
                                                             launch_cart_hub_class<16>};   // class i: 2 << i wavefronts
   const CartLongMode& m = kCartLong[0];

@@ -63,21 +63,11 @@ __global__ void __launch_bounds__(256) k_cart_bwd_long(const CartBwdLong a, int 
     const float* xs = a.Xp + s;
     // A. chunks: gather (striped: lane-contiguous col reads; the entry index travels with the key), sort, park
     for (int c0 = 0; c0 < Dp; c0 += CAP) {
-      WaveLine64<M> ln;
-      int c[M];
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        const int t = c0 + j * kWave + lane;
-        c[j] = t < D ? colrow[t] : -1;
+      {
+        constexpr bool RUN_PAD = false;
+        unsigned long long* const run_line = se;
+#include "sorted_run.inc"
       }
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        const int t = c0 + j * kWave + lane;
-        ln.e[j] = pack_key_index(c[j] >= 0 ? xs[(int64_t)c[j] * a.ldp] : __builtin_inff(), t);   // fill elements sort behind the line
-      }
-      ln.sort();
-#pragma unroll
-      for (int j = 0; j < M; ++j) se[c0 + lane * M + j] = ln.e[j];
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     // B. merge levels above one chunk
@@ -157,10 +147,8 @@ __global__ void __launch_bounds__(256) k_cart_bwd_long(const CartBwdLong a, int 
 // unit weights with tau <= 1: the classes of kCartLong[0], one launch per populated hub bin (embed_cart.h: for_each_cart_line_bin)
 int launch_cart_hub_bwd(const fsw_cart_args* c, hipStream_t stream) {
   CartBwdLong t;
-  t.rowptr = c->rowptr; t.col = c->col; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F;
-  t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
-  t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
+  cart_fill_inputs(t, c);
+  cart_fill_grads(t, c);
   return for_each_cart_line_bin(c, kCartLong[0], [&](int bin, int64_t line_elems, int nwaves) {
     k_cart_bwd_long<<<(unsigned)ceil_div(nwaves, 4), 256, 0, stream>>>(t, bin, reinterpret_cast<char*>(c->scratch), line_elems, nwaves);
   });

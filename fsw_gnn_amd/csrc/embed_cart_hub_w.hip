@@ -189,10 +189,8 @@ int launch_cart_hub_w_class(const CartHubW& t, const CartLongClass& k, int64_t r
 int launch_cart_hub_w(const fsw_cart_args* c, hipStream_t stream) {
   const int32_t* bs = c->bin_start_host;
   CartHubW t;
-  t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
-  t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
-  t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
+  cart_fill_inputs_w(t, c);
+  cart_fill_outputs(t, c);
   constexpr decltype(&launch_cart_hub_w_class<2>) launch[] = {launch_cart_hub_w_class<2>, launch_cart_hub_w_class<4>,
                                                               launch_cart_hub_w_class<8>};   // class i: 2 << i wavefronts
   const CartLongMode& m = kCartLong[1];

@@ -193,10 +193,8 @@ __global__ void __launch_bounds__(256) k_cart_bwd_long_w(const CartBwdLongW a, i
 // general weights: the classes of kCartLong[1], one launch per populated bin they touch (embed_cart.h: for_each_cart_line_bin)
 int launch_cart_hub_w_bwd(const fsw_cart_args* c, hipStream_t stream) {
   CartBwdLongW t;
-  t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
-  t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
-  t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
+  cart_fill_inputs_w(t, c);
+  cart_fill_grads(t, c);
   return for_each_cart_line_bin(c, kCartLong[1], [&](int bin, int64_t line_elems, int nwaves) {
     k_cart_bwd_long_w<<<(unsigned)ceil_div(nwaves, 4), 256, 0, stream>>>(t, bin, reinterpret_cast<char*>(c->scratch), line_elems, nwaves);
   });

@@ -53,8 +53,7 @@ __global__ void __launch_bounds__(kCartGiantNW* kWave, 4) k_cart_giant(const Car
   const int pbeg = a.bin_start[a.bin], nrows = a.bin_start[FSW_NUM_BINS] - pbeg;
   const int lane = lane_id(), w = wave_id();
   const int S = a.S, F = a.F;
-  // the workgroups of one XCD take consecutive lines (slices of the same row) when the grid is a multiple of 8
-  const int blk = (gridDim.x & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+  const int blk = xcd_first_line();
   float* sl = a.scratch + (int64_t)blk * a.line_floats;
   const int64_t nlines = (int64_t)nrows * S;
   // every wavefront's scratch stores performed, then a barrier.  Workgroup scope is enough: the wavefronts of a workgroup share their
@@ -73,26 +72,13 @@ __global__ void __launch_bounds__(kCartGiantNW* kWave, 4) k_cart_giant(const Car
     const int nbp = (int)pow2ceil((uint32_t)nb);
     float* mine = sl + w * CAP + lane * M;                // the lane's M keys of block 0; block b: + b * BLK
     WaveLine<M, false> ln;
-    auto park = [&](int b) {
-      float* dst = mine + (int64_t)b * BLK;
-#pragma unroll
-      for (int j = 0; j < M; j += 4) *reinterpret_cast<float4*>(dst + j) = make_float4(ln.k[j], ln.k[j + 1], ln.k[j + 2], ln.k[j + 3]);
-    };
-    auto fetch = [&](int b) {
-      const float* src = mine + (int64_t)b * BLK;
-#pragma unroll
-      for (int j = 0; j < M; j += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(src + j);
-        ln.k[j] = v.x; ln.k[j + 1] = v.y; ln.k[j + 2] = v.z; ln.k[j + 3] = v.w;
-      }
-    };
     // A. blocks: gather, sort in the workgroup's registers, park in the scratch line
 #pragma unroll 1
     for (int b = 0; b < nb; ++b) {
       gather_chunk<M>(ln, a.col + start, b * BLK + w * CAP, D, a.Xp, a.ldp, s, lane);
       ln.sort();
       workgroup_merge_levels<NW, M>(ln, xbuf, w, lane);
-      park(b);
+      park_keys<M>(ln, mine + (int64_t)b * BLK);
     }
     sync_scratch();
     // B. merge levels above one block
@@ -107,21 +93,7 @@ __global__ void __launch_bounds__(kCartGiantNW* kWave, 4) k_cart_giant(const Car
           float* lo = sl + (int64_t)b * BLK;
           float* hi = sl + (int64_t)b2 * BLK;
 #pragma unroll 2
-          for (int e = threadIdx.x * 4; e < BLK; e += NT * 4) {
-            const float4 x = *reinterpret_cast<const float4*>(lo + e);
-            float4 y;
-            if (flip) {                                    // lo[e] against hi[BLK - 1 - e]
-              const float4 t = *reinterpret_cast<const float4*>(hi + (BLK - 4 - e));
-              y = make_float4(t.w, t.z, t.y, t.x);
-            } else {
-              y = *reinterpret_cast<const float4*>(hi + e);
-            }
-            const float4 mn = make_float4(fminf(x.x, y.x), fminf(x.y, y.y), fminf(x.z, y.z), fminf(x.w, y.w));
-            const float4 mx = make_float4(fmaxf(x.x, y.x), fmaxf(x.y, y.y), fmaxf(x.z, y.z), fmaxf(x.w, y.w));
-            *reinterpret_cast<float4*>(lo + e) = mn;
-            if (flip) *reinterpret_cast<float4*>(hi + (BLK - 4 - e)) = make_float4(mx.w, mx.z, mx.y, mx.x);
-            else *reinterpret_cast<float4*>(hi + e) = mx;
-          }
+          for (int e = threadIdx.x * 4; e < BLK; e += NT * 4) sweep_block_pair<BLK>(lo, hi, e, flip);
         }
         sync_scratch();
       };
@@ -129,9 +101,9 @@ __global__ void __launch_bounds__(kCartGiantNW* kWave, 4) k_cart_giant(const Car
       for (int st = size >> 2; st >= 1; st >>= 1) sweep(false, st);
 #pragma unroll 1
       for (int b = 0; b < nb; ++b) {
-        fetch(b);
+        fetch_keys<M>(ln, mine + (int64_t)b * BLK);
         workgroup_merge_block<NW, M>(ln, xbuf, w, lane);
-        park(b);
+        park_keys<M>(ln, mine + (int64_t)b * BLK);
       }
       sync_scratch();
     }
@@ -148,7 +120,7 @@ __global__ void __launch_bounds__(kCartGiantNW* kWave, 4) k_cart_giant(const Car
       for (int b = 0; b < nb; ++b) {
         const int r0 = b * BLK + w * CAP + lane * M;
         if (b * BLK + w * CAP >= D) break;                  // the wavefront's keys of this and the later blocks: all +inf
-        fetch(b);
+        fetch_keys<M>(ln, mine + (int64_t)b * BLK);
 #pragma unroll
         for (int q = 0; q < kFB; ++q)
           if (q < nf) acc[q] += unit_readout<M>(ln, r0, D, a.freqs[f0 + q]);
@@ -186,10 +158,8 @@ int launch_cart_giant(const fsw_cart_args* c, hipStream_t stream) {
   if (const int rc = cart_giant_plan(c, m, &nwg, &line_bytes)) return rc;
   if (nwg == 0) return 0;
   CartGiant t;
-  t.rowptr = c->rowptr; t.col = c->col; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F;
-  t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
-  t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
+  cart_fill_inputs(t, c);
+  cart_fill_outputs(t, c);
   t.scratch = (float*)c->scratch; t.line_floats = (int64_t)(line_bytes / sizeof(float));
   t.bin = m.giant_bin; t.min_degree = m.giant_min_degree;
   k_cart_giant<<<(unsigned)nwg, kCartGiantNW * kWave, 0, stream>>>(t);

@@ -6,19 +6,16 @@
 // k_cart_giant_bwd<WEIGHTED>: one workgroup of four wavefronts takes ONE (recipient row, slice) line at a time (the forward's
 // persistent, XCD-aware line loop) in its own scratch line: two lines of packed (key, entry index) words (ping, pong), the line
 // rounded up to whole runs of kCartMaxLine words.
-//   A. every wavefront does what phase A of k_cart_bwd_long / k_cart_bwd_long_w does for the chunks w, w + 4, ..: gather striped,
-//      pack the key with the entry index, sort in registers (WaveLine64), park the sorted run in the ping line.  General weights: the
-//      reference's pad element (key 0, weight max(tau - m, 0)) is element D and carries index D, fill elements have key +inf; the row
-//      mass m is summed in float64 as the chunks load and reduced over the workgroup;
+//   A. every wavefront sorts the runs w, w + 4, .. into the ping line (sorted_run.inc).  General weights: the reference's pad element
+//      has weight max(tau - m, 0); the row mass m is summed in float64 as the chunks load and reduced over the workgroup;
 //   B. the levels above one run are merge-path passes between ping and pong (merge_path64.h: one unsigned 64-bit compare, no ties:
 //      equal keys keep entry order, the pad element sorts last among the zeros -- the project's rule and the generic kernel's);
 //   C. the workgroup walks the sorted line in tiles of 256 threads x kGbVT (16 | 8) consecutive ranks; every tile is read out at all F
 //      frequencies (g_f and xi_f wave-uniform) with the arithmetic of the long-row kernels:
-//        unit weights     c_t = t / D, the float64 rotation of k_cart_bwd_long, restarted from exact values at every thread's first rank;
+//        unit weights     walk_unit.inc;
 //        general weights  the weights re-read by entry index (w[start + idx], the pad weight for idx == D, 0 for fill), the float64
 //                         cumulative weight by wave scan + wavefront offsets + a carry from tile to tile (as k_cart_mergepath_w's
-//                         readout), ONE F_dF per (element, frequency) + one per thread at the cumulative weight before its first
-//                         element (its lower bound);
+//                         readout), then walk_weighted.inc;
 //        gkey[e, s]  = sum_f out_scale g[r, s F + f] (F_f(c_rank) - F_f(c_{rank-1}))          stored for every entry
 //        gfreq[f]   += out_scale g[r, s F + f] sum_t (dF_f(c_t) - dF_f(c_{t-1})) p_(t)         one float atomic per (wavefront, line, frequency)
 //      The key gradients accumulate in registers over the frequencies and pass through the line that the last level left free, in
@@ -31,6 +28,7 @@
 #include "embed_cart.h"
 #include "embed_launch.h"
 #include "fourier_coef.h"
+#include "hub_line.h"
 #include "merge_path64.h"
 #include "sortnet.h"
 #include "wave_sort.h"
@@ -77,8 +75,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_cart_giant_bwd(const CartGiantBw
   const int pbeg = a.bin_start[a.bin], nrows = a.bin_start[FSW_NUM_BINS] - pbeg;
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
   const int S = a.S, F = a.F;
-  // the workgroups of one XCD take consecutive lines (slices of the same row) when the grid is a multiple of 8
-  const int blk = (gridDim.x & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+  const int blk = xcd_first_line();
   mp64_t* ping = reinterpret_cast<mp64_t*>(a.scratch + (int64_t)blk * a.line_cap * kCartGiantBwdElemBytes);
   mp64_t* pong = ping + a.line_cap;
   const int64_t nlines = (int64_t)nrows * S;
@@ -110,23 +107,11 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_cart_giant_bwd(const CartGiantBw
           mpart += (double)max(0, min(D - c0 - lane + kWave - 1, M * kWave) / kWave);   // entries t = c0 + j * 64 + lane < D, j < M
         }
       }
-      WaveLine64<M> ln;
-      int c[M];
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        const int t = c0 + j * kWave + lane;
-        c[j] = t < D ? colrow[t] : -1;
+      {
+        constexpr bool RUN_PAD = WEIGHTED;
+        unsigned long long* const run_line = ping;
+#include "sorted_run.inc"
       }
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        const int t = c0 + j * kWave + lane;
-        // general weights: the pad element at x = 0 with index D, last among equal keys; fill elements sort behind the line
-        const float fill = (WEIGHTED && t == D) ? 0.f : __builtin_inff();
-        ln.e[j] = pack_key_index(c[j] >= 0 ? xs[(int64_t)c[j] * a.ldp] : fill, t);
-      }
-      ln.sort();
-#pragma unroll
-      for (int j = 0; j < M; ++j) ping[c0 + lane * M + j] = ln.e[j];
     }
     double inv = 1.0 / (double)D;
     float padw = 0.f;
@@ -188,54 +173,13 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_cart_giant_bwd(const CartGiantBw
           carry += tot;
           if (live) {
             for (int q = 0; q < nf; ++q) {
-              const FCoef fc((double)a.freqs[fb + q]);
-              const float gi = a.out_scale * grow[fb + q];
-              double c = cw0, Fp, dFp;
-              F_dF(fc, c * inv, Fp, dFp);                    // the lower bound of the thread's first element
-              float ds = 0.f;
-#pragma unroll
-              for (int j = 0; j < VT; ++j) {
-                c += (double)wt[j] + (idx[j] == D ? rho : 0.0);
-                double Fv, dFv;
-                F_dF(fc, c * inv, Fv, dFv);
-                G[j] = fmaf(gi, (float)(Fv - Fp), G[j]);
-                ds = fmaf((float)(dFv - dFp), key[j], ds);
-                Fp = Fv;
-                dFp = dFv;
-              }
-              const float tot = wave_sum(gi * ds);
-              if (lane == q) gfl += tot;
+#include "walk_weighted.inc"
             }
           }
         } else {
           if (live) {
             for (int q = 0; q < nf; ++q) {
-              const double xi = (double)a.freqs[fb + q];
-              const float gi = a.out_scale * grow[fb + q];
-              const FCoef fc(xi);
-              const double step = xi * inv;                  // revolutions per rank
-              double sd, cd, sn, cs, Fp, dFp;
-              sincospi(2.0 * (step - rint(step)), &sd, &cd);
-              const double x0 = step * (double)r0;
-              sincospi(2.0 * (x0 - rint(x0)), &sn, &cs);
-              F_dF_sc(fc, (double)min(r0, D) * inv, sn, cs, Fp, dFp);
-              float ds = 0.f;
-#pragma unroll
-              for (int j = 0; j < VT; ++j) {
-                const double s1 = fma(sn, cd, cs * sd), c1 = fma(cs, cd, -(sn * sd));
-                sn = s1;
-                cs = c1;
-                double Fv, dFv;
-                F_dF_sc(fc, (double)min(r0 + j + 1, D) * inv, sn, cs, Fv, dFv);
-                if (r0 + j < D) {
-                  G[j] = fmaf(gi, (float)(Fv - Fp), G[j]);
-                  ds = fmaf((float)(dFv - dFp), key[j], ds);
-                }
-                Fp = Fv;
-                dFp = dFv;
-              }
-              const float tot = wave_sum(gi * ds);
-              if (lane == q) gfl += tot;
+#include "walk_unit.inc"
             }
           }
         }
@@ -270,10 +214,8 @@ int launch_cart_giant_bwd(const fsw_cart_args* c, hipStream_t stream) {
   FSW_REQUIRE(nwg >= 1, "fsw_embed_cart_backward_keys_f32: scratch buffer too small for one line of the longest class "
                         "(need fsw_embed_cart_backward_keys_scratch_bytes)");
   CartGiantBwd t;
-  t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
-  t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
-  t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
+  cart_fill_inputs_w(t, c);
+  cart_fill_grads(t, c);
   t.scratch = reinterpret_cast<char*>(c->scratch); t.line_cap = (int64_t)(line_bytes / kCartGiantBwdElemBytes);
   t.bin = m.giant_bin; t.min_degree = m.giant_min_degree;
   if (unit_fast) k_cart_giant_bwd<false><<<(unsigned)nwg, kMp64NT, 0, stream>>>(t);

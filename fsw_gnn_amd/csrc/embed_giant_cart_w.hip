@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_cart_mergepath_w(const CartGiantW 
   const int pbeg = a.bin_start[a.bin], nrows = a.bin_start[FSW_NUM_BINS] - pbeg;
   const int lane = lane_id(), w = wave_id();
   const int S = a.S, F = a.F;
-  const int blk = (gridDim.x & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+  const int blk = xcd_first_line();
   float* k0 = a.scratch + (int64_t)blk * 4 * a.line_cap;
   float* k1 = k0 + a.line_cap;
   float* w0 = k1 + a.line_cap;
@@ -195,23 +195,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_cart_mergepath_w(const CartGiantW 
 #pragma unroll
         for (int q = 0; q < kFB; ++q) {
           if (q < nf) {
-            const float xif = a.freqs[f0 + q];
-            if (fabsf(xif) < 1e-30f) {                      // xi == 0: Delta_t = 2 w_t / max(m, tau)
-#pragma unroll
-              for (int j = 0; j < kMpVT; ++j) acc[q] = fmaf(ww[j], kk[j], acc[q]);
-            } else {
-              const double xi = (double)xif;
-              double cw = cw0;
-              // the element before a key >= 0 is the pad element, or lies behind it, or multiplies a zero key: same residual
-              float sprev = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[0])) * inv));
-#pragma unroll
-              for (int j = 0; j < kMpVT; ++j) {
-                cw += (double)ww[j];
-                const float sn = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[j])) * inv));
-                acc[q] = fmaf(sn - sprev, kk[j], acc[q]);
-                sprev = sn;
-              }
-            }
+#include "readout_weighted.inc"
           }
         }
       }
@@ -251,10 +235,8 @@ int launch_cart_giant_w(const fsw_cart_args* c, hipStream_t stream) {
   if (const int rc = cart_giant_plan(c, m, &nwg, &line_bytes)) return rc;
   if (nwg == 0) return 0;
   CartGiantW t;
-  t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
-  t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
-  t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
+  cart_fill_inputs_w(t, c);
+  cart_fill_outputs(t, c);
   t.scratch = (float*)c->scratch; t.line_cap = (int64_t)(line_bytes / (4 * sizeof(float)));
   t.bin = m.giant_bin; t.min_degree = m.giant_min_degree;
   const size_t lds = sizeof(float) * 2 * 4 * kCartLongM * kWave;   // phase A's (key, weight) exchange buffers; the tiles + boundaries fit inside

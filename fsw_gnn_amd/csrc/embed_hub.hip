@@ -321,8 +321,7 @@ __global__ void __launch_bounds__(kGiantNW* kWave, 4) k_embed_giant(const int32_
   __shared__ float red[NW];
   const int pbeg = bin_start[FSW_BIN_GLOBAL], nrows = bin_start[FSW_BIN_GLOBAL + 1] - pbeg;
   const int lane = lane_id(), w = wave_id();
-  // the workgroups of one XCD take consecutive lines (slices of the same row) when the grid is a multiple of 8
-  const int blk = (gridDim.x & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+  const int blk = xcd_first_line();
   float* sl = scratch + (int64_t)blk * line_floats;
   const int64_t nlines = (int64_t)nrows * S;
   // order within the workgroup: every wavefront's scratch stores performed, then a barrier.  Workgroup scope is enough: the
@@ -365,21 +364,7 @@ __global__ void __launch_bounds__(kGiantNW* kWave, 4) k_embed_giant(const int32_
           float* lo = sl + (int64_t)b * BLK;
           float* hi = sl + (int64_t)b2 * BLK;
 #pragma unroll 2
-          for (int e = threadIdx.x * 4; e < BLK; e += NT * 4) {
-            const float4 x = *reinterpret_cast<const float4*>(lo + e);
-            float4 y;
-            if (flip) {                                    // lo[e] against hi[BLK - 1 - e]
-              const float4 t = *reinterpret_cast<const float4*>(hi + (BLK - 4 - e));
-              y = make_float4(t.w, t.z, t.y, t.x);
-            } else {
-              y = *reinterpret_cast<const float4*>(hi + e);
-            }
-            const float4 mn = make_float4(fminf(x.x, y.x), fminf(x.y, y.y), fminf(x.z, y.z), fminf(x.w, y.w));
-            const float4 mx = make_float4(fmaxf(x.x, y.x), fmaxf(x.y, y.y), fmaxf(x.z, y.z), fmaxf(x.w, y.w));
-            *reinterpret_cast<float4*>(lo + e) = mn;
-            if (flip) *reinterpret_cast<float4*>(hi + (BLK - 4 - e)) = make_float4(mx.w, mx.z, mx.y, mx.x);
-            else *reinterpret_cast<float4*>(hi + e) = mx;
-          }
+          for (int e = threadIdx.x * 4; e < BLK; e += NT * 4) sweep_block_pair<BLK>(lo, hi, e, flip);
         }
         sync_scratch();
       };
@@ -856,7 +841,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_embed_mergepath_w(
   int* part = reinterpret_cast<int*>(xsm + 2 * kMpTileLds);
   const int pbeg = bin_start[bin_lo], nrows = bin_start[bin_hi + 1] - pbeg;
   const int lane = lane_id(), w = wave_id();
-  const int blk = (gridDim.x & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+  const int blk = xcd_first_line();
   float* k0 = scratch + (int64_t)blk * 4 * line_cap;
   float* k1 = k0 + line_cap;
   float* w0 = k1 + line_cap;

@@ -4,11 +4,10 @@
 // k_cart_giant gives a line to one workgroup, which walks the line's blocks of kCartGiantBlk keys one after the other through eleven
 // (150 000 keys) to twenty-two (1 000 000 keys) fence-separated passes: one point cloud at S = 16 keeps 16 CUs busy.  Here every pass is
 // a launch of its own whose grid covers (line, block), from the same building blocks (hub_line.h, wave_sort.h):
-//   k_split_sort    (line, block): gather the block from Xp, sort it in the workgroup's registers, park it in the line's scratch region
-//                   at rank order b * BLK + w * CAP + lane * M + j                                      -- phase A of k_cart_giant
-//   k_split_sweep   one launch per exchange of a merge level size = 2, 4, .., pow2ceil(nb): the flip (block b against b ^ (size - 1),
-//                   mirrored), then the strides size / 4 .. 1; element-wise min / max over a pair of blocks, in place, 16 bytes per
-//                   access, every pair cut into kSplitCut workgroups.  Pairs whose upper block holds only +inf are skipped
+//   k_split_sort    (line, block): phase A of k_cart_giant for one block, parked at rank order b * BLK + w * CAP + lane * M + j
+//   k_split_sweep   one launch per exchange of a merge level size = 2, 4, .., pow2ceil(nb): the flip, then the strides size / 4 .. 1
+//                   (hub_line.h: sweep_block_pair), every pair cut into kSplitCut workgroups.  Pairs whose upper block holds only
+//                   +inf are skipped
 //   k_split_tail    (line, block): fetch, workgroup_merge_block; below the line's last level: park.  At the line's LAST level the block
 //                   stays in registers and is read out at all F frequencies in batches of kFB (unit_readout) -- lane, wavefront,
 //                   workgroup -- into partial[line][b][f]
@@ -59,29 +58,13 @@ struct CartSplit {
 };
 
 struct SplitLine { int node, s, start, D, nb; };
-// the line's row; false for a row that k_cart_giant skips too: another class in this bin, or longer than the host's max_degree
+// the line's row (embed_cart.h: cart_row_at) with its slice and its blocks; false for a row that k_cart_giant skips too
 __device__ __forceinline__ bool split_line(const CartSplit& a, int64_t line, SplitLine& l) {
   const int pbeg = a.bin_start[a.bin];
-  l.node = a.perm[pbeg + (int)(line / a.S)];
+  cart_row_at(a, pbeg + (int)(line / a.S), l);
   l.s = (int)(line % a.S);
-  l.start = a.rowptr[l.node];
-  l.D = a.rowptr[l.node + 1] - l.start;
   l.nb = (l.D + kCartGiantBlk - 1) / kCartGiantBlk;
   return l.D >= a.min_degree && (int64_t)l.nb * kCartGiantBlk <= a.line_floats;
-}
-
-template <int M>
-__device__ __forceinline__ void park(const WaveLine<M, false>& ln, float* dst) {
-#pragma unroll
-  for (int j = 0; j < M; j += 4) *reinterpret_cast<float4*>(dst + j) = make_float4(ln.k[j], ln.k[j + 1], ln.k[j + 2], ln.k[j + 3]);
-}
-template <int M>
-__device__ __forceinline__ void fetch(WaveLine<M, false>& ln, const float* src) {
-#pragma unroll
-  for (int j = 0; j < M; j += 4) {
-    const float4 v = *reinterpret_cast<const float4*>(src + j);
-    ln.k[j] = v.x; ln.k[j + 1] = v.y; ln.k[j + 2] = v.z; ln.k[j + 3] = v.w;
-  }
 }
 
 // grid (nbmax, nlines)
@@ -98,7 +81,7 @@ __global__ void __launch_bounds__(kCartGiantNW* kWave, 4) k_split_sort(const Car
   gather_chunk<M>(ln, a.col + l.start, b * BLK + w * CAP, l.D, a.Xp, a.ldp, l.s, lane);
   ln.sort();
   workgroup_merge_levels<NW, M>(ln, xbuf, w, lane);
-  park<M>(ln, a.scratch + line * a.line_floats + (int64_t)b * BLK + w * CAP + lane * M);
+  park_keys<M>(ln, a.scratch + line * a.line_floats + (int64_t)b * BLK + w * CAP + lane * M);
 }
 
 // grid (pow2ceil(nbmax) / 2 * kSplitCut, nlines): pair p of the exchange (flip: st == 0) of level `size`, part blockIdx.x % kSplitCut
@@ -116,20 +99,7 @@ __global__ void __launch_bounds__(kSplitSweepNT) k_split_sweep(const CartSplit a
   float* hi = a.scratch + line * a.line_floats + (int64_t)b2 * BLK;
 #pragma unroll
   for (int i = 0; i < PART / (kSplitSweepNT * 4); ++i) {
-    const int e = part * PART + (i * kSplitSweepNT + (int)threadIdx.x) * 4;
-    const float4 x = *reinterpret_cast<const float4*>(lo + e);
-    float4 y;
-    if (flip) {                                              // lo[e] against hi[BLK - 1 - e]
-      const float4 t = *reinterpret_cast<const float4*>(hi + (BLK - 4 - e));
-      y = make_float4(t.w, t.z, t.y, t.x);
-    } else {
-      y = *reinterpret_cast<const float4*>(hi + e);
-    }
-    const float4 mn = make_float4(fminf(x.x, y.x), fminf(x.y, y.y), fminf(x.z, y.z), fminf(x.w, y.w));
-    const float4 mx = make_float4(fmaxf(x.x, y.x), fmaxf(x.y, y.y), fmaxf(x.z, y.z), fmaxf(x.w, y.w));
-    *reinterpret_cast<float4*>(lo + e) = mn;
-    if (flip) *reinterpret_cast<float4*>(hi + (BLK - 4 - e)) = make_float4(mx.w, mx.z, mx.y, mx.x);
-    else *reinterpret_cast<float4*>(hi + e) = mx;
+    sweep_block_pair<BLK>(lo, hi, part * PART + (i * kSplitSweepNT + (int)threadIdx.x) * 4, flip);
   }
 }
 
@@ -148,10 +118,10 @@ __global__ void __launch_bounds__(kCartGiantNW* kWave, 4) k_split_tail(const Car
   const int lane = lane_id(), w = wave_id();
   float* mine = a.scratch + line * a.line_floats + (int64_t)b * BLK + w * CAP + lane * M;
   WaveLine<M, false> ln;
-  fetch<M>(ln, mine);
+  fetch_keys<M>(ln, mine);
   workgroup_merge_block<NW, M>(ln, xbuf, w, lane);
   if (size < nbp) {
-    park<M>(ln, mine);
+    park_keys<M>(ln, mine);
     return;
   }
   // the line is sorted: the lane's keys have ranks r0 .. r0 + M - 1
@@ -212,10 +182,8 @@ int launch_cart_split(const fsw_cart_args* c, const CartSplitPlan& p, hipStream_
   const CartLongMode& m = kCartLong[0];
   if (p.lines <= 0) return 0;
   CartSplit t;
-  t.rowptr = c->rowptr; t.col = c->col; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F;
-  t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
-  t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
+  cart_fill_inputs(t, c);
+  cart_fill_outputs(t, c);
   t.scratch = (float*)c->scratch; t.line_floats = (int64_t)(p.line_bytes / sizeof(float));
   t.partial = (float*)((char*)c->scratch + p.partial_offset); t.nbmax = p.nbmax; t.nlines = p.lines;
   t.bin = m.giant_bin; t.min_degree = m.giant_min_degree;

@@ -4,14 +4,14 @@
 // k_cart_giant_bwd gives a line to one workgroup of four wavefronts, which sorts its runs, merges them level by level and walks the
 // sorted line tile by tile: one point cloud at S = 16 keeps 16 CUs busy, and the time is the latency of that chain.  Here every phase
 // is a launch of its own whose grid covers (line, piece), from the same building blocks (wave_sort.h, merge_path64.h, fourier_coef.h):
-//   k_split_bwd_runs    (group of four runs, line): gather the keys striped from Xp, pack them with the entry index, sort a run per
-//                       wavefront in registers (WaveLine64), park it in the line's ping region          -- phase A of k_cart_giant_bwd
+//   k_split_bwd_runs    (group of four runs, line): a run per wavefront into the line's ping region (sorted_run.inc) -- phase A of
+//                       k_cart_giant_bwd
 //   k_split_bwd_level   one launch per level R = 2048, 4096, ..: (span of tile slots, line): the span's boundaries by binary search in
 //                       the level's source region, its tiles merged into the other region, its share of the run without a partner
 //                       copied (merge_path64_span.h).  After k levels the line lies in ping (k even) or pong (k odd)     -- phase B
-//   k_split_bwd_walk    (tile of 256 threads x 16 consecutive ranks, line): phase C with its arithmetic and its order of accumulation
-//                       unchanged -- a unit line needs no carry between tiles, c_t = t / D --, so gkey is bit-identical to
-//                       k_cart_giant_bwd<false>.  gkey is stored straight from the walk by entry index; the frequency gradients of a
+//   k_split_bwd_walk    (tile of 256 threads x 16 consecutive ranks, line): phase C with the text k_cart_giant_bwd<false> runs
+//                       (walk_unit.inc) and its order of accumulation -- a unit line needs no carry between tiles, c_t = t / D --,
+//                       so gkey is bit-identical to it.  gkey is stored straight from the walk by entry index; the frequency gradients of a
 //                       tile go to partial[line][tile][f] (no float atomic per tile)
 //   k_split_bwd_finish  (frequency): the partial sums of all lines and tiles in a fixed order, one atomic per frequency into gfreq
 // Consecutive launches in the caller's stream are the only synchronisation between workgroups: no spin barrier, no cooperative launch,
@@ -62,13 +62,11 @@ struct CartSplitBwd {
 };
 
 struct SbLine { int node, s, start, D, total; };
-// the line's row; false for a row that k_cart_giant_bwd skips too: another class in this bin, or longer than the host's max_degree
+// the line's row (embed_cart.h: cart_row_at) with its slice and its whole runs; false for a row that k_cart_giant_bwd skips too
 __device__ __forceinline__ bool sb_line(const CartSplitBwd& a, int64_t line, SbLine& l) {
   const int pbeg = a.bin_start[a.bin];
-  l.node = a.perm[pbeg + (int)(line / a.S)];
+  cart_row_at(a, pbeg + (int)(line / a.S), l);
   l.s = (int)(line % a.S);
-  l.start = a.rowptr[l.node];
-  l.D = a.rowptr[l.node + 1] - l.start;
   const int64_t total64 = ((int64_t)l.D + kCartMaxLine - 1) / kCartMaxLine * kCartMaxLine;
   l.total = (int)total64;
   return l.D >= a.min_degree && total64 <= a.line_cap;
@@ -88,22 +86,11 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_split_bwd_runs(const CartSplitBw
   const int c0 = (int)c64, D = l.D;
   const int32_t* colrow = a.col + l.start;
   const float* xs = a.Xp + l.s;
-  mp64_t* ping = sb_region(a, line, 0);
-  WaveLine64<M> ln;
-  int c[M];
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    const int t = c0 + j * kWave + lane;
-    c[j] = t < D ? colrow[t] : -1;
+  {
+    constexpr bool RUN_PAD = false;
+    unsigned long long* const run_line = sb_region(a, line, 0);
+#include "sorted_run.inc"
   }
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    const int t = c0 + j * kWave + lane;
-    ln.e[j] = pack_key_index(c[j] >= 0 ? xs[(int64_t)c[j] * a.ldp] : __builtin_inff(), t);   // fill elements sort behind the line
-  }
-  ln.sort();
-#pragma unroll
-  for (int j = 0; j < M; ++j) ping[c0 + lane * M + j] = ln.e[j];
 }
 
 // grid (ceil(tile slots of the longest row / span), nlines): span blockIdx.x of level k, runs of kMp64Run << k words
@@ -158,32 +145,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_split_bwd_walk(const CartSplitBw
     for (int j = 0; j < VT; ++j) G[j] = 0.f;
     if (live) {
       for (int q = 0; q < nf; ++q) {
-        const double xi = (double)a.freqs[fb + q];
-        const float gi = a.out_scale * grow[fb + q];
-        const FCoef fc(xi);
-        const double step = xi * inv;                        // revolutions per rank
-        double sd, cd, sn, cs, Fp, dFp;
-        sincospi(2.0 * (step - rint(step)), &sd, &cd);
-        const double x0 = step * (double)r0;
-        sincospi(2.0 * (x0 - rint(x0)), &sn, &cs);
-        F_dF_sc(fc, (double)min(r0, D) * inv, sn, cs, Fp, dFp);
-        float ds = 0.f;
-#pragma unroll
-        for (int j = 0; j < VT; ++j) {
-          const double s1 = fma(sn, cd, cs * sd), c1 = fma(cs, cd, -(sn * sd));
-          sn = s1;
-          cs = c1;
-          double Fv, dFv;
-          F_dF_sc(fc, (double)min(r0 + j + 1, D) * inv, sn, cs, Fv, dFv);
-          if (r0 + j < D) {
-            G[j] = fmaf(gi, (float)(Fv - Fp), G[j]);
-            ds = fmaf((float)(dFv - dFp), key[j], ds);
-          }
-          Fp = Fv;
-          dFp = dFv;
-        }
-        const float tot = wave_sum(gi * ds);
-        if (lane == q) gfl += tot;
+#include "walk_unit.inc"
       }
     }
     // blocks of 64 frequencies add up in block order, as in k_cart_giant_bwd: the same thread wrote the entry in the block before
@@ -233,10 +195,8 @@ int launch_cart_split_bwd(const fsw_cart_args* c, const CartSplitBwdPlan& p, hip
   const CartLongMode& m = kCartLong[0];
   if (p.lines <= 0) return 0;
   CartSplitBwd t;
-  t.rowptr = c->rowptr; t.col = c->col; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F;
-  t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
-  t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
+  cart_fill_inputs(t, c);
+  cart_fill_grads(t, c);
   t.scratch = (mp64_t*)c->scratch; t.line_cap = (int64_t)(p.line_bytes / kCartGiantBwdElemBytes);
   t.partial = (float*)((char*)c->scratch + p.partial_offset); t.ntmax = p.ntmax; t.nlines = p.lines;
   t.bin = m.giant_bin; t.min_degree = m.giant_min_degree;

@@ -77,12 +77,10 @@ struct CartSplitW {
 };
 
 struct SplitWRow { int node, start, D, nb; };
-// row `row` of the class's bins; false for a row that k_cart_mergepath_w skips too: the class below, or longer than the host's max_degree
+// the row (embed_cart.h: cart_row_at) with the blocks of its line of D + 1 elements; false for a row that k_cart_mergepath_w skips too
 __device__ __forceinline__ bool splitw_row(const CartSplitW& a, int64_t row, SplitWRow& l) {
-  l.node = a.perm[a.bin_start[a.bin] + (int)row];
-  l.start = a.rowptr[l.node];
-  l.D = a.rowptr[l.node + 1] - l.start;
-  l.nb = (l.D + 1 + kMpBlk - 1) / kMpBlk;                    // blocks of the line of D + 1 elements
+  cart_row_at(a, a.bin_start[a.bin] + (int)row, l);
+  l.nb = (l.D + 1 + kMpBlk - 1) / kMpBlk;
   return l.D >= a.min_degree && (int64_t)l.nb * kMpBlk <= a.cap;
 }
 // the row's mass: its pieces in block order
@@ -373,23 +371,7 @@ __global__ void __launch_bounds__(kMpNT, 2) k_splitw_readout(const CartSplitW a)
     for (int q = 0; q < kFB; ++q) {
       acc[q] = 0.f;
       if (q < nf) {
-        const float xif = a.freqs[f0 + q];
-        if (fabsf(xif) < 1e-30f) {                            // xi == 0: Delta_t = 2 w_t / max(m, tau)
-#pragma unroll
-          for (int j = 0; j < kMpVT; ++j) acc[q] = fmaf(ww[j], kk[j], acc[q]);
-        } else {
-          const double xi = (double)xif;
-          double cw = cw0;
-          // the element before a key >= 0 is the pad element, or lies behind it, or multiplies a zero key: same residual
-          float sprev = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[0])) * inv));
-#pragma unroll
-          for (int j = 0; j < kMpVT; ++j) {
-            cw += (double)ww[j];
-            const float sn = sin2pi_rev(xi * ((cw + pad_residual_at(rho, kk[j])) * inv));
-            acc[q] = fmaf(sn - sprev, kk[j], acc[q]);
-            sprev = sn;
-          }
-        }
+#include "readout_weighted.inc"
       }
     }
 #pragma unroll
@@ -442,10 +424,8 @@ int launch_cart_split_w(const fsw_cart_args* c, const CartSplitWPlan& p, hipStre
   const CartLongMode& m = kCartLong[1];
   if (p.lines <= 0) return 0;
   CartSplitW t;
-  t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
-  t.out = (float*)c->out; t.ldo = c->ldo; t.bias = (const float*)c->bias; t.out_scale = (float)c->out_scale;
-  t.has_mass = c->has_mass; t.mass_fn = c->mass_fn; t.mass_scale = (float)c->mass_scale;
+  cart_fill_inputs_w(t, c);
+  cart_fill_outputs(t, c);
   t.scratch = (float*)c->scratch; t.cap = p.cap;
   t.tsum = (double*)((char*)c->scratch + p.tsum_offset);
   t.partial = (float*)((char*)c->scratch + p.partial_offset);

@@ -8,16 +8,15 @@
 //   k_splitw_bwd_mass    (run, row): the float64 sum of the weights of the entries [2048 p, 2048 p + 2048) into mass[row][p]; the row's
 //                        mass m is the sum of its pieces in piece order (w == NULL: every weight is 1).  m does not depend on the slice;
 //                        the walk needs it for the pad element's weight max(tau - m, 0) and for 1 / max(m, tau)
-//   k_splitw_bwd_runs    (group of four runs, line): phase A -- gather the keys striped from Xp, pack them with the entry index, sort a
-//                        run per wavefront in registers (WaveLine64), park it in the line's ping region.  The pad element is element D
-//                        with key 0 and index D (last among equal keys), fill elements have key +inf
+//   k_splitw_bwd_runs    (group of four runs, line): phase A -- a run per wavefront into the line's ping region (sorted_run.inc, with
+//                        the pad element)
 //   k_splitw_bwd_level   one launch per level R = 2048, 4096, ..: (span of tile slots, line), as k_split_bwd_level of the unit form:
 //                        mp64_span, mp64_merge_tiles, mp64_copy_run.  After k levels the line lies in ping (k even) or pong (k odd)
 //   k_splitw_bwd_tsum    (walk tile, line): the float64 sum of the weights of the tile's 2048 ranks into tsum[line][tile]; the weights are
 //                        re-read by entry index (w[start + idx], the pad weight for idx == D, 0 for fill)
 //   k_splitw_bwd_walk    (tile of 256 threads x 8 consecutive ranks, line): the cumulative weight before the tile is the sum of the
 //                        earlier tiles' tsum in tile order (float64); inside the tile phase C of k_cart_giant_bwd<true>: wave scan +
-//                        wavefront offsets in float64, ONE F_dF per (element, frequency) + one per thread at its lower bound.  gkey is
+//                        wavefront offsets in float64, then the text that kernel runs per frequency (walk_weighted.inc).  gkey is
 //                        stored straight from the walk by entry index (pad and fill elements store nothing); the frequency gradients of
 //                        a tile go to partial[line][tile][f], the four wavefronts' sums added in wavefront order (no float atomic per tile).
 //                        More than 64 frequencies: blocks of 64, the sums of a gkey entry added in block order by the thread that owns it
@@ -81,12 +80,9 @@ struct CartSplitWBwd {
 };
 
 struct SwbRow { int node, start, D, total; };
-// row `row` of the class's bins with its line of D + 1 elements in whole runs; false for a row that k_cart_giant_bwd<true> skips too:
-// the class below in this bin, or longer than the host's max_degree
+// the row (embed_cart.h: cart_row_at) with its line of D + 1 elements in whole runs; false for a row that k_cart_giant_bwd<true> skips too
 __device__ __forceinline__ bool swb_row(const CartSplitWBwd& a, int64_t row, SwbRow& l) {
-  l.node = a.perm[a.bin_start[a.bin] + (int)row];
-  l.start = a.rowptr[l.node];
-  l.D = a.rowptr[l.node + 1] - l.start;
+  cart_row_at(a, a.bin_start[a.bin] + (int)row, l);
   const int64_t total64 = ((int64_t)l.D + 1 + kCartMaxLine - 1) / kCartMaxLine * kCartMaxLine;
   l.total = (int)total64;
   return l.D >= a.min_degree && total64 <= a.line_cap;
@@ -154,24 +150,11 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_splitw_bwd_runs(const CartSplitW
   const int c0 = (int)c64, D = l.D;
   const int32_t* colrow = a.col + l.start;
   const float* xs = a.Xp + s;
-  mp64_t* ping = swb_region(a, line, 0);
-  WaveLine64<M> ln;
-  int c[M];
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    const int t = c0 + j * kWave + lane;
-    c[j] = t < D ? colrow[t] : -1;
+  {
+    constexpr bool RUN_PAD = true;
+    unsigned long long* const run_line = swb_region(a, line, 0);
+#include "sorted_run.inc"
   }
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    const int t = c0 + j * kWave + lane;
-    // the pad element at x = 0 with index D, last among equal keys; fill elements sort behind the line
-    const float fill = t == D ? 0.f : __builtin_inff();
-    ln.e[j] = pack_key_index(c[j] >= 0 ? xs[(int64_t)c[j] * a.ldp] : fill, t);
-  }
-  ln.sort();
-#pragma unroll
-  for (int j = 0; j < M; ++j) ping[c0 + lane * M + j] = ln.e[j];
 }
 
 // grid (ceil(tiles / span), nlines): span blockIdx.x of level k, runs of kMp64Run << k words
@@ -272,23 +255,7 @@ __global__ void __launch_bounds__(kMp64NT, 2) k_splitw_bwd_walk(const CartSplitW
     for (int j = 0; j < VT; ++j) G[j] = 0.f;
     if (live) {
       for (int q = 0; q < nf; ++q) {
-        const FCoef fc((double)a.freqs[fb + q]);
-        const float gi = a.out_scale * grow[fb + q];
-        double c = cw0, Fp, dFp;
-        F_dF(fc, c * inv, Fp, dFp);                          // the lower bound of the thread's first element
-        float ds = 0.f;
-#pragma unroll
-        for (int j = 0; j < VT; ++j) {
-          c += (double)wt[j] + (idx[j] == D ? rho : 0.0);
-          double Fv, dFv;
-          F_dF(fc, c * inv, Fv, dFv);
-          G[j] = fmaf(gi, (float)(Fv - Fp), G[j]);
-          ds = fmaf((float)(dFv - dFp), key[j], ds);
-          Fp = Fv;
-          dFp = dFv;
-        }
-        const float tot = wave_sum(gi * ds);
-        if (lane == q) gfl += tot;
+#include "walk_weighted.inc"
       }
     }
     // blocks of 64 frequencies add up in block order, as in k_cart_giant_bwd: the same thread wrote the entry in the block before
@@ -338,10 +305,8 @@ int launch_cart_split_w_bwd(const fsw_cart_args* c, const CartSplitWBwdPlan& p, 
   const CartLongMode& m = kCartLong[1];
   if (p.lines <= 0) return 0;
   CartSplitWBwd t;
-  t.rowptr = c->rowptr; t.col = c->col; t.w = (const float*)c->w; t.perm = c->perm; t.bin_start = c->bin_start;
-  t.Xp = (const float*)c->Xp; t.ldp = c->ldp; t.freqs = (const float*)c->freqs; t.S = c->S; t.F = c->F; t.tau = (float)c->tau;
-  t.g = (const float*)c->g; t.ldg = c->ldg; t.gcol0 = c->has_mass; t.out_scale = (float)c->out_scale;
-  t.gkey = (float*)c->gkey; t.ldk = c->ldk; t.gfreq = (float*)c->gfreq;
+  cart_fill_inputs_w(t, c);
+  cart_fill_grads(t, c);
   t.scratch = (mp64_t*)c->scratch; t.line_cap = p.words;
   t.mass = (double*)((char*)c->scratch + p.mass_offset);
   t.tsum = (double*)((char*)c->scratch + p.tsum_offset);

@@ -18,6 +18,7 @@
 //                (fsw_embedding.py:787-821) is element D.
 #include <algorithm>
 #include "embed_launch.h"
+#include "hub_line.h"
 #include "sortnet.h"
 #include "wave_sort.h"
 
@@ -253,7 +254,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
   // lines are numbered (row, slice) with the slice fastest; the workgroups of one XCD (blockIdx.x % 8 under round-robin
   // dispatch) take consecutive lines when the grid is a multiple of 8, so that the slices sharing a sector of an Xp row
   // are read through the same L2
-  const int blk = (gridDim.x & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+  const int blk = xcd_first_line();
   const int gw = blk * 4 + wave_id(), nwaves = gridDim.x * 4;
   float* sk = reinterpret_cast<float*>(scratch + (int64_t)gw * wave_bytes);
   float* sw = sk + (wave_bytes >> 3);                   // second half of the wave's region (weighted only)

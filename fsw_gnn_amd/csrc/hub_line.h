@@ -1,9 +1,11 @@
 // Building blocks of the kernels that keep ONE (row, slice) line of a hub row (FSW_LDS_MAX_DEG < in-degree) in the registers of the
 // NW wavefronts of a workgroup: the striped gather of a wavefront's chunk, the register exchange between wavefronts through LDS, the
-// bitonic merge levels above one chunk and the unit-weight readout of a lane's keys.  Shared by the diagonal kernels of
-// embed_hub.hip (k_embed_hub, k_embed_hub_q4, k_embed_giant; general weights: k_embed_hub_w, k_embed_mergepath_w) and the Cartesian
-// ones of embed_cart_hub.hip (k_cart_hub), embed_cart_hub_w.hip (k_cart_hub_w), embed_giant_cart.hip (k_cart_giant) and
-// embed_giant_cart_w.hip (k_cart_mergepath_w).  gfx950.
+// bitonic merge levels above one chunk and the unit-weight readout of a lane's keys; for lines longer than the registers, the parked
+// blocks of a scratch line and the line loop per XCD.  Shared by the diagonal kernels of embed_hub.hip (k_embed_hub, k_embed_hub_q4,
+// k_embed_giant; general weights: k_embed_hub_w, k_embed_mergepath_w) and embed_wsort.hip (k_embed_wsort_global) and the Cartesian ones
+// of embed_cart_hub.hip (k_cart_hub), embed_cart_hub_w.hip (k_cart_hub_w), embed_giant_cart.hip (k_cart_giant), embed_split_cart.hip
+// (k_split_sort, k_split_sweep, k_split_tail), embed_giant_cart_w.hip (k_cart_mergepath_w), embed_split_cart_w.hip (k_splitw_sort) and
+// embed_giant_cart_bwd.hip (k_cart_giant_bwd).  gfx950.
 #pragma once
 #include "fsw_common.h"
 #include "wave_sort.h"
@@ -144,6 +146,49 @@ __device__ __forceinline__ HubLineId hub_virtual_line(int64_t vb, int xcd, int l
   const int64_t rl = i / S;
   const int s = (int)(i - rl * S);
   return {rl * 8 + xcd, s};
+}
+
+// ---- steps of the kernels that keep a line LONGER than the workgroup's registers in a scratch line (k_embed_giant and the giant and
+// split forms of Cartesian mode).  Loops, unroll pragmas, readfirstlane and barriers stay with the callers: they are each kernel's tuning.
+
+// First line of a persistent workgroup that strides by gridDim.x: the workgroups of one XCD take consecutive lines (slices of the same
+// row) when the grid is a multiple of 8
+__device__ __forceinline__ int xcd_first_line() {
+  return (gridDim.x & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
+}
+
+// park / fetch the lane's M keys at 16 bytes per access
+template <int M>
+__device__ __forceinline__ void park_keys(const WaveLine<M, false>& ln, float* dst) {
+#pragma unroll
+  for (int j = 0; j < M; j += 4) *reinterpret_cast<float4*>(dst + j) = make_float4(ln.k[j], ln.k[j + 1], ln.k[j + 2], ln.k[j + 3]);
+}
+template <int M>
+__device__ __forceinline__ void fetch_keys(WaveLine<M, false>& ln, const float* src) {
+#pragma unroll
+  for (int j = 0; j < M; j += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(src + j);
+    ln.k[j] = v.x; ln.k[j + 1] = v.y; ln.k[j + 2] = v.z; ln.k[j + 3] = v.w;
+  }
+}
+
+// one 16-byte access of an element-wise exchange between two parked blocks of BLK keys: lo[e .. e + 3] against hi[e .. e + 3], or, the
+// flip, against hi[BLK - 1 - e ..] mirrored; the smaller keys stay in lo
+template <int BLK>
+__device__ __forceinline__ void sweep_block_pair(float* lo, float* hi, int e, bool flip) {
+  const float4 x = *reinterpret_cast<const float4*>(lo + e);
+  float4 y;
+  if (flip) {
+    const float4 t = *reinterpret_cast<const float4*>(hi + (BLK - 4 - e));
+    y = make_float4(t.w, t.z, t.y, t.x);
+  } else {
+    y = *reinterpret_cast<const float4*>(hi + e);
+  }
+  const float4 mn = make_float4(fminf(x.x, y.x), fminf(x.y, y.y), fminf(x.z, y.z), fminf(x.w, y.w));
+  const float4 mx = make_float4(fmaxf(x.x, y.x), fmaxf(x.y, y.y), fmaxf(x.z, y.z), fmaxf(x.w, y.w));
+  *reinterpret_cast<float4*>(lo + e) = mn;
+  if (flip) *reinterpret_cast<float4*>(hi + (BLK - 4 - e)) = make_float4(mx.w, mx.z, mx.y, mx.x);
+  else *reinterpret_cast<float4*>(hi + e) = mx;
 }
 
 }  // namespace fsw

@@ -1188,70 +1188,50 @@ class FSW_embedding(nn.Module):
         a.bin_start_host = graph.bin_start_host[0].ctypes.data
         return int(_lib.lib().fsw_embed_cart_backward_keys_scratch_bytes(ctypes.byref(a)))
 
-    def _cart_split(self, graph, st):
-        """The policy of the split form of the longest unit-weight rows (csrc/embed_split_cart.hip), decided ONCE per forward on the
-        module's nSlices, so that every serialize_num_slices chunk takes the same form: bytes of scratch the split form needs, or 0 for the
-        one-workgroup-per-line kernel -- no such row, general weights, or more than fsw_embed_cart_split_max_lines() lines, which fill
-        the chip by themselves.  Host values only."""
+    # form -> (unit weights?, the library's queries of the form's lines, its largest measured line count and its scratch bytes)
+    _CART_SPLIT_FORMS = {
+        "forward": (True, "fsw_embed_cart_split_lines", "fsw_embed_cart_split_max_lines", "fsw_embed_cart_split_scratch_bytes"),
+        "forward_w": (False, "fsw_embed_cart_split_w_lines", "fsw_embed_cart_split_w_max_lines", "fsw_embed_cart_split_w_scratch_bytes"),
+        "backward": (True, "fsw_embed_cart_split_backward_lines", "fsw_embed_cart_split_backward_max_lines",
+                     "fsw_embed_cart_split_backward_scratch_bytes"),
+        "backward_w": (False, "fsw_embed_cart_split_w_backward_lines", "fsw_embed_cart_split_w_backward_max_lines",
+                       "fsw_embed_cart_split_w_backward_scratch_bytes"),
+    }
+
+    def _cart_split_bytes(self, graph, st, form):
+        """The policy of the split forms of the longest rows (csrc/embed_split_cart*.hip), decided ONCE per forward or backward on the
+        module's nSlices, so that every serialize_num_slices chunk takes the same form: bytes of scratch the split form needs, or 0 for
+        the one-workgroup-per-line kernel -- the other weight mode (a weight tensor, W='uniform' or total_mass_pad_thresh > 1 are general
+        weights; it leaves before the query), no such row, or more lines than the form's largest measured count, which fill the chip by
+        themselves.  Host values only.  Called through the class by the four methods below, which tests run on stand-in modules."""
+        unit, lines_fn, max_lines_fn, bytes_fn = FSW_embedding._CART_SPLIT_FORMS[form]
+        if (graph.w is None and self.total_mass_pad_thresh <= 1.0) != unit:
+            return 0
         a = _lib.CartArgs()
         a.S, a.F, a.tau, a.max_degree = self.nSlices, self.nFreqs, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
         a.w = graph.w.data_ptr() if graph.w is not None else None
         a.bin_start_host = graph.bin_start_host[0].ctypes.data
         L = _lib.lib()
-        lines = int(L.fsw_embed_cart_split_lines(ctypes.byref(a)))
-        if not (0 < lines <= int(L.fsw_embed_cart_split_max_lines())):
+        lines = int(getattr(L, lines_fn)(ctypes.byref(a)))
+        if not (0 < lines <= int(getattr(L, max_lines_fn)())):
             return 0
-        return int(L.fsw_embed_cart_split_scratch_bytes(ctypes.byref(a)))
+        return int(getattr(L, bytes_fn)(ctypes.byref(a)))
+
+    def _cart_split(self, graph, st):
+        """_cart_split_bytes of the forward with unit weights (csrc/embed_split_cart.hip)."""
+        return FSW_embedding._cart_split_bytes(self, graph, st, "forward")
 
     def _cart_split_w(self, graph, st):
-        """The policy of the split form of the longest general-weight rows (csrc/embed_split_cart_w.hip: a weight tensor, W='uniform',
-        total_mass_pad_thresh > 1), decided ONCE per forward on the module's nSlices like _cart_split: bytes of scratch the split form
-        needs, or 0 for the one-workgroup-per-line kernel -- unit weights, no such row, or more than fsw_embed_cart_split_w_max_lines()
-        lines.  Host values only; unit weights leave before the query."""
-        if graph.w is None and self.total_mass_pad_thresh <= 1:
-            return 0
-        a = _lib.CartArgs()
-        a.S, a.F, a.tau, a.max_degree = self.nSlices, self.nFreqs, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
-        a.w = graph.w.data_ptr() if graph.w is not None else None
-        a.bin_start_host = graph.bin_start_host[0].ctypes.data
-        L = _lib.lib()
-        lines = int(L.fsw_embed_cart_split_w_lines(ctypes.byref(a)))
-        if not (0 < lines <= int(L.fsw_embed_cart_split_w_max_lines())):
-            return 0
-        return int(L.fsw_embed_cart_split_w_scratch_bytes(ctypes.byref(a)))
+        """_cart_split_bytes of the forward with general weights (csrc/embed_split_cart_w.hip)."""
+        return FSW_embedding._cart_split_bytes(self, graph, st, "forward_w")
 
     def _cart_split_backward(self, graph, st):
-        """The policy of the split form of the longest unit-weight rows' backward (csrc/embed_split_cart_bwd.hip), decided ONCE per
-        backward: bytes of scratch the split form needs, or 0 for the one-workgroup-per-line kernel -- no such row, general weights, or
-        more than fsw_embed_cart_split_backward_max_lines() lines.  Host values only; mirrors _cart_split (general weights leave before
-        the query: their training step is short enough to show the host's microseconds)."""
-        if not self._unit_fast(graph):
-            return 0
-        a = _lib.CartArgs()
-        a.S, a.F, a.tau, a.max_degree = self.nSlices, self.nFreqs, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
-        a.bin_start_host = graph.bin_start_host[0].ctypes.data       # a.w stays NULL: unit weights
-        L = _lib.lib()
-        lines = int(L.fsw_embed_cart_split_backward_lines(ctypes.byref(a)))
-        if not (0 < lines <= int(L.fsw_embed_cart_split_backward_max_lines())):
-            return 0
-        return int(L.fsw_embed_cart_split_backward_scratch_bytes(ctypes.byref(a)))
+        """_cart_split_bytes of the backward with unit weights (csrc/embed_split_cart_bwd.hip)."""
+        return FSW_embedding._cart_split_bytes(self, graph, st, "backward")
 
     def _cart_split_w_backward(self, graph, st):
-        """The policy of the split form of the longest general-weight rows' backward (csrc/embed_split_cart_w_bwd.hip), decided ONCE per
-        backward: bytes of scratch the split form needs, or 0 for the one-workgroup-per-line kernel -- unit weights, no such row, or more
-        than fsw_embed_cart_split_w_backward_max_lines() lines.  Host values only; mirrors _cart_split_w (unit weights leave before the
-        query)."""
-        if graph.w is None and self.total_mass_pad_thresh <= 1:
-            return 0
-        a = _lib.CartArgs()
-        a.S, a.F, a.tau, a.max_degree = self.nSlices, self.nFreqs, self.total_mass_pad_thresh, st[_lib.STAT_MAX_DEGREE]
-        a.w = graph.w.data_ptr() if graph.w is not None else None
-        a.bin_start_host = graph.bin_start_host[0].ctypes.data
-        L = _lib.lib()
-        lines = int(L.fsw_embed_cart_split_w_backward_lines(ctypes.byref(a)))
-        if not (0 < lines <= int(L.fsw_embed_cart_split_w_backward_max_lines())):
-            return 0
-        return int(L.fsw_embed_cart_split_w_backward_scratch_bytes(ctypes.byref(a)))
+        """_cart_split_bytes of the backward with general weights (csrc/embed_split_cart_w_bwd.hip)."""
+        return FSW_embedding._cart_split_bytes(self, graph, st, "backward_w")
 
     def _cart_scratch(self, graph, st, backward=False, reuse=None, split_bytes=0):
         """The scratch buffer of the forward (_cart_forward_scratch_bytes) or of the backward (_cart_backward_scratch_bytes), or of
