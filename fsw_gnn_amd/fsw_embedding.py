@@ -1086,7 +1086,9 @@ class FSW_embedding(nn.Module):
             out = self.embed_autograd(Xf.contiguous(), graph)
         else:
             out = torch.empty((num_rows, self.d_out), dtype=X.dtype, device=X.device)
-            self.embed_into(Xf, graph, out, out_scale=1.0, serialize_num_slices=serialize_num_slices)
+            # a view (a column slice, every other row, a transpose) is copied here, as on the three sibling paths; embed_into and
+            # prepare keep their contiguity contract
+            self.embed_into(Xf.contiguous(), graph, out, out_scale=1.0, serialize_num_slices=serialize_num_slices)
         return out.reshape(out_shape + (self.d_out,))
 
     def _forward_generic(self, Xf, rec, snd, wvals, efvals, num_rows, bias):
