@@ -15,6 +15,7 @@
 // on this part (atomics execute at the memory side, ~1.3 TB/s of added bytes chip-wide; this kernel is bound by that).
 // gX = gXp . V and gV = gXp^T . X are two plain GEMMs left to the BLAS.
 #include "embed_launch.h"
+#include "weighted_coef.h"
 
 namespace fsw {
 
@@ -134,21 +135,6 @@ __global__ void __launch_bounds__(256) k_embed_reg_unit_bwd(const int32_t* __res
 // normalised weight up to and including the element: the coefficient of neighbour t needs only its own cumulative
 // weight, which D(D+1)/2 compares give without sorting (cum[u] += w[t] when t sorts ahead of u).  Coefficient and
 // xi-derivative in float64 (the two terms of dF/dxi cancel from O(c/xi) to O(1)).
-__device__ __forceinline__ void F_dF(double xi, double c, double& F, double& dF) {
-  const double x = 2.0 * kPi * xi * c;
-  if (fabs(x) < 1e-4) {
-    const double q = 1.0 - x * x * (1.0 / 6.0);
-    F = (1.0 + xi) * 2.0 * c * q;
-    dF = 2.0 * c * q - (1.0 + xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * xi * (1.0 / 3.0);
-    return;
-  }
-  const double ph = xi * c;
-  double s, co;
-  sincospi(2.0 * (ph - rint(ph)), &s, &co);
-  F = (1.0 + xi) * s / (kPi * xi);
-  dF = -s / (kPi * xi * xi) + (1.0 + xi) * 2.0 * c * co / xi;
-}
-
 template <int DEG>
 __device__ __forceinline__ void weighted_bwd_rows(int p, int pe, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                   const float* __restrict__ w, const int32_t* __restrict__ perm,

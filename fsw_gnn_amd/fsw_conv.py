@@ -218,8 +218,11 @@ class FSW_conv(_Base):
                 graph.w = None
         return graph
 
-    def build_graph(self, edge_index, num_vertices, edge_features=None, chunk_rows=0):
+    def build_graph(self, edge_index, num_vertices, edge_features=None, chunk_rows=0, edge_weight=None):
         """edge_index [2, E] int64 (row 0 = sender, row 1 = recipient) -> CSRGraph.
+
+        edge_weight [E] (optional): edge e counts edge_weight[e] times; self loops and 'gcn' weighting apply on top, with weighted
+        degrees.  The graph holds the values as constants (forward() routes gradients); cache_graph is bypassed.
 
         With edge features (edgefeat_dim > 0, fsw_conv.py:419-439) the adjacency is coalesced like the reference's:
         parallel edges become one entry with summed weight and summed feature vector; self loops carry zero features.
@@ -232,10 +235,10 @@ class FSW_conv(_Base):
         """
         if edge_features is not None:
             ef = edge_features.detach().reshape(edge_index.shape[1], -1)
-            src, dst, w, ef = self._weighted_edges(edge_index, num_vertices, ef)
+            src, dst, w, ef = self._weighted_edges(edge_index, num_vertices, ef, edge_w=edge_weight)
             return build_csr_coalesced(dst, src, w, ef.contiguous(), num_vertices, num_vertices, want_slots=True)
-        if not self.cache_graph:
-            return self._build_graph_uncached(edge_index, num_vertices, chunk_rows)
+        if not self.cache_graph or edge_weight is not None:
+            return self._build_graph_uncached(edge_index, num_vertices, chunk_rows, edge_weight)
         # optional CSR reuse across calls / layers.  Off by default: the reference rebuilds its
         # adjacency on every forward (fsw_conv.py:352) and bench.py times the rebuild.  The cache entry keeps the
         # edge_index tensor itself alive, so its address cannot be handed to another batch by the caching allocator;
@@ -250,35 +253,63 @@ class FSW_conv(_Base):
         self._graph_cache = (edge_index, key, graph)
         return graph
 
-    def _build_graph_uncached(self, edge_index, num_vertices, chunk_rows):
+    def _build_graph_uncached(self, edge_index, num_vertices, chunk_rows, edge_weight=None):
         """build_graph without edge features: a fresh CSR."""
-        src, dst, w, _ = self._weighted_edges(edge_index, num_vertices)
+        src, dst, w, _ = self._weighted_edges(edge_index, num_vertices, edge_w=edge_weight)
         return build_csr(dst, src, w, num_vertices, num_vertices, want_invperm=self._fusable() and not self.fsw_embed.cartesian_mode,
                          chunk_rows=chunk_rows,
                          hint=self._build_hint())
 
-    def _weighted_edges(self, edge_index, num_vertices, ef=None):
+    def _weighted_edges(self, edge_index, num_vertices, ef=None, edge_w=None, keep_grad=False, dtype=torch.float32):
         """(src, dst, w, ef) of the edge list with the self loops appended (weight self_loop_weight, zero features) and the 'gcn'
-        weighting applied (build_graph); w stays None for unit weights."""
+        weighting applied (build_graph); w stays None for unit weights.  edge_w [E]: a weight per edge in place of 1 (the 'gcn'
+        degrees are then weighted); detached unless keep_grad, in which case every op on it is differentiable.  dtype: of the
+        arithmetic and of w."""
         src, dst = edge_index[0], edge_index[1]
         w = None
+        if edge_w is not None:
+            w = (edge_w if keep_grad else edge_w.detach()).to(dtype)
         if self.self_loop_weight > 0:
             loops = torch.arange(num_vertices, device=edge_index.device, dtype=torch.int64)
-            w = torch.cat([torch.ones(src.numel(), device=src.device, dtype=torch.float32),
-                           torch.full((num_vertices,), float(self.self_loop_weight), device=src.device, dtype=torch.float32)])
+            w = torch.cat([w if w is not None else torch.ones(src.numel(), device=src.device, dtype=dtype),
+                           torch.full((num_vertices,), float(self.self_loop_weight), device=src.device, dtype=dtype)])
             src, dst = torch.cat([src, loops]), torch.cat([dst, loops])
             if ef is not None:
                 ef = torch.cat([ef, torch.zeros((num_vertices, ef.shape[1]), device=ef.device, dtype=ef.dtype)])
         if self.edge_weighting == 'gcn':
             if w is None:
-                w = torch.ones(src.numel(), device=src.device, dtype=torch.float32)
-            deg = torch.zeros(num_vertices, device=src.device, dtype=torch.float32).scatter_add_(0, dst, w)
+                w = torch.ones(src.numel(), device=src.device, dtype=dtype)
+            deg = torch.zeros(num_vertices, device=src.device, dtype=dtype).scatter_add_(0, dst, w)
             ds = torch.sqrt(deg)
             w = w / ds[dst] / ds[src]
         return src, dst, w, ef
 
-    def forward(self, vertex_features, edge_index, edge_features=None):
+    def _check_edge_weight(self, edge_weight, edge_index, csr):
+        """Host-side checks of forward()'s edge_weight (no device is touched); finiteness and sign are checked where the values
+        of a torch.sparse_csr adjacency are: by the graph build's flags (float32) or FSW_embedding.forward (float64)."""
+        emb_mod = self.fsw_embed
+        assert csr is None or not csr[3], \
+            'edge_weight cannot be combined with a torch.sparse_csr adjacency: its values are the weights'
+        num = csr[1].numel() if csr is not None else edge_index.shape[1]
+        assert torch.is_tensor(edge_weight) and edge_weight.dim() == 1 and edge_weight.numel() == num, \
+            'edge_weight must have the shape (num_edges,) = (%d,)' % num
+        assert edge_weight.dtype == emb_mod.get_dtype(), 'edge_weight has incorrect dtype (expected %s, got %s)' % (emb_mod.get_dtype(), edge_weight.dtype)
+        assert edge_weight.device == emb_mod.get_device(), 'edge_weight has incorrect device (expected %s, got %s)' % (emb_mod.get_device(), edge_weight.device)
+        if getattr(self, '_node_parallel', False) or getattr(self, '_slice_parallel', None) is not None:
+            raise NotImplementedError("fsw_gnn_amd: edge_weight under enable_slice_parallel / enable_node_parallel is not implemented")
+
+    def forward(self, vertex_features, edge_index, edge_features=None, edge_weight=None):
         """vertex_features [n, in_channels], edge_index [2, E] long -> [n, out_channels] (fsw_conv.py:331-369).
+
+        edge_weight [E] (optional), in the layer's dtype on its device, finite and non-negative: edge e counts edge_weight[e] times
+        -- the result is the reference layer's on the coalesced adjacency whose values are these weights; self loops
+        (self_loop_weight) and 'gcn' weighting apply on top, with weighted degrees.  Constant weights run wherever general weights
+        run (diagonal and Cartesian mode, with edge features, float64, the tuple CSR form with edge_weight [nnz] aligned with the
+        entries).  Weights that require grad: float32 edge list in diagonal mode without edge features and with the plain degree
+        encoding (FSW_embedding.embed_autograd(edge_weight=), csrc/embed_w_bwd.hip), and float64 layers (the generic kernels);
+        NotImplementedError for float32 Cartesian mode, float32 with edge features, float32 homog_degree_encoding and the tuple CSR
+        form.  Not with a torch.sparse_csr adjacency (its values are the weights), not under enable_slice_parallel /
+        enable_node_parallel; cache_graph is bypassed.
 
         edge_index may also be a CSR adjacency whose row i lists the senders to vertex i (PyG's adj_t), imported without the sort
         of the edge-list path: a tuple (rowptr, col) of int32 / int64 tensors (unit weights; repeated columns are parallel edges;
@@ -288,6 +319,14 @@ class FSW_conv(_Base):
         enable_node_parallel; cache_graph does not apply (the adjacency is imported on every call)."""
         emb_mod = self.fsw_embed
         csr = self._csr_adjacency(edge_index, vertex_features.size(0))
+        if edge_weight is not None:
+            self._check_edge_weight(edge_weight, edge_index, csr)
+        w_grad = edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled()
+        if csr is not None and edge_weight is not None:
+            if w_grad:
+                raise NotImplementedError("fsw_gnn_amd: gradients of edge_weight with a CSR adjacency in tuple form (rowptr, col) are "
+                                          "not implemented; pass the edge list")
+            csr = (csr[0], csr[1], edge_weight.detach(), False)      # the entries' weights, as the values of the tensor form
         if csr is not None:
             if getattr(self, '_node_parallel', False) or getattr(self, '_slice_parallel', None) is not None:
                 raise NotImplementedError("fsw_gnn_amd: a CSR adjacency under enable_slice_parallel / enable_node_parallel is not "
@@ -310,7 +349,7 @@ class FSW_conv(_Base):
         if vertex_features.device.type != 'cuda':
             raise RuntimeError("fsw_gnn_amd: forward needs tensors on a HIP device ('cuda'); there is no CPU path")
         needs_grad = torch.is_grad_enabled() and (vertex_features.requires_grad or any(p.requires_grad for p in self.parameters())
-                                                  or (edge_features is not None and edge_features.requires_grad))
+                                                  or (edge_features is not None and edge_features.requires_grad) or w_grad)
         n = vertex_features.size(0)
         if n == 0:
             return torch.zeros((0, self.out_channels), dtype=vertex_features.dtype, device=vertex_features.device)
@@ -320,9 +359,17 @@ class FSW_conv(_Base):
                                           "the generic kernels on one GPU)")
             # float64 build (the reference's test_conv.py runs the layer this way): the reference's own structure -- coalesced
             # COO adjacency and edge features (fsw_conv.py:384-447), FSW_embedding.forward on the generic kernels, torch tail
-            adj, x_edge = self.adjacency_coo(edge_index, edge_features if self.edgefeat_dim > 0 else None, n, vertex_features.dtype)
+            # (edge_weight: the values before coalescing; autograd passes through coalesce() to a weight that requires grad)
+            adj, x_edge = self.adjacency_coo(edge_index, edge_features if self.edgefeat_dim > 0 else None, n, vertex_features.dtype,
+                                             edge_w=edge_weight if (edge_weight is None or w_grad) else edge_weight.detach())
             emb = emb_mod(vertex_features, W=adj, X_edge=x_edge, graph_mode=True)
             return self._tail(emb, vertex_features)
+        if w_grad:
+            what = ("Cartesian mode" if emb_mod.cartesian_mode else "edge features (edgefeat_dim > 0)" if self.edgefeat_dim > 0
+                    else "homog_degree_encoding" if not emb_mod.plain_mass else None)
+            if what is not None:
+                raise NotImplementedError("fsw_gnn_amd: gradients of edge_weight in a float32 layer with %s are not implemented "
+                                          "(float32: diagonal mode, no edge features, plain degree encoding; or a float64 layer)" % what)
         x = vertex_features.contiguous()
         if getattr(self, '_node_parallel', False):
             if needs_grad:
@@ -332,8 +379,16 @@ class FSW_conv(_Base):
         if sp is not None:
             return self._forward_slice_parallel(sp, x, vertex_features, edge_index, edge_features, needs_grad)
         if emb_mod.cartesian_mode:
-            return self._forward_cartesian(x, vertex_features, edge_index, needs_grad, edge_features)
-        graph = self.build_graph(edge_index, n, edge_features if self.edgefeat_dim > 0 else None)
+            return self._forward_cartesian(x, vertex_features, edge_index, needs_grad, edge_features, edge_weight=edge_weight)
+        if w_grad:
+            # learnable edge weights: the self-loop and 'gcn' arithmetic stays on the autograd tape, the graph (a coalescing build
+            # that yields the CSR entry of every input edge) gets the detached result, _EmbedGraphWFn routes the gradient back
+            # In float64: the weight gradient at frequency xi feels a weight's rounding times 2 pi xi, so the backward gets the
+            # normalised weights beyond the float32 of graph.w (_EmbedGraphWFn: w_lo); the forward runs on graph.w as it is.
+            src, dst, w, _ = self._weighted_edges(edge_index, n, edge_w=edge_weight, keep_grad=True, dtype=torch.float64)
+            graph = build_csr_coalesced(dst, src, w.detach().to(torch.float32), None, n, n, want_slots=True)
+            return self._tail(emb_mod.embed_autograd(x, graph, edge_weight=w), vertex_features)
+        graph = self.build_graph(edge_index, n, edge_features if self.edgefeat_dim > 0 else None, edge_weight=edge_weight)
         ef_in = edge_features.reshape(edge_index.shape[1], -1) if self.edgefeat_dim > 0 else None
         return self._forward_graph(x, vertex_features, graph, needs_grad, ef_in)
 
@@ -432,7 +487,8 @@ class FSW_conv(_Base):
             return self._forward_cartesian(x, vertex_features, None, needs_grad, edge_features, graph=graph, ef_in=ef_in)
         return self._forward_graph(x, vertex_features, graph, needs_grad, ef_in)
 
-    def _forward_cartesian(self, x, vertex_features, edge_index, needs_grad, edge_features=None, graph=None, ef_in=None):
+    def _forward_cartesian(self, x, vertex_features, edge_index, needs_grad, edge_features=None, graph=None, ef_in=None,
+                           edge_weight=None):
         """float32 layer with a Cartesian embedding (embed_slices x embed_freqs): training through _CartEmbedFn and the usual tail;
         inference through ONE kernel for the embedding and the first Linear layer (csrc/conv_fused.hip: k_conv_fused_cart) when the
         configuration is fusable and no row has more than REG_MAX_DEG neighbours, else embed_cartesian_into + the torch tail.
@@ -443,7 +499,7 @@ class FSW_conv(_Base):
         n = x.shape[0]
         has_ef = self.edgefeat_dim > 0
         if graph is None:                            # an edge list; a CSR adjacency comes with its imported graph (_forward_csr)
-            graph = self.build_graph(edge_index, n, edge_features if has_ef else None)
+            graph = self.build_graph(edge_index, n, edge_features if has_ef else None, edge_weight=edge_weight)
             ef_in = edge_features.reshape(edge_index.shape[1], -1) if has_ef else None
         if needs_grad:
             return self._tail(emb_mod.embed_cartesian_autograd(x, graph, edge_feat=ef_in), vertex_features)

@@ -302,6 +302,101 @@ class _EmbedGraphFn(torch.autograd.Function):
         return gX, gV, gfreqs, gbias, gscale, gEf, None, None, None, None, None, None, None
 
 
+class _EmbedGraphWFn(torch.autograd.Function):
+    """out = out_scale * E(X, graph) with gradients for X, projVecs, freqs, bias, the total-mass scale AND the per-edge weights the
+    graph was built from (float32, diagonal mode, no edge features, 'plain' mass encoding).
+
+    graph: a coalescing build with want_slots=True (graph.slot_of_edge: the CSR entry of every input edge; the entry's weight is the
+    sum of its edges' weights, so every edge receives its entry's gradient).  edge_w [num_input_edges]: the weights the graph was
+    built from -- only the gradient is routed to it, the forward kernels read graph.w.  A float64 edge_w (FSW_conv: the self-loop
+    and 'gcn' arithmetic in float64) gives the backward the entries' weights beyond float32: w_lo = sum of the entry's edge_w - graph.w
+    (fsw_embed_backward_w_lo_f32), because d out / d w at frequency xi feels a weight's rounding times 2 pi xi.
+    Forward: the tuned path of _EmbedGraphFn (prepare + embed_into).  Backward: fsw_embed_backward_w_f32 (csrc/embed_w_bwd.hip: rows
+    of up to 24 neighbours on the register kernels, longer rows on the generic kernel) stores the key gradients per entry and
+    accumulates gfreq and gw; gXp is their sum sender by sender (graph.sender_major + fsw_segment_sum_rows_f32).  The total-mass
+    column depends on the weights through m: out_scale scale g[:, 0] f'(m) per recipient is added, as in _GenericEmbedFn.backward.
+    Pad rule: as _GenericEmbedFn.key_grads -- without a deficient row (empty recipients included) the launch gets tau / 2."""
+
+    @staticmethod
+    def forward(ctx, X, projVecs, freqs, bias, mass_scale, edge_w, module, graph, out_scale):
+        assert graph.w is not None and graph.ef is None and graph.slot_of_edge is not None, \
+            'the gradient of the edge weights needs a coalesced graph built with want_slots=True and without edge features'
+        with torch.no_grad():
+            prepared = module.prepare(X, graph)
+            out = torch.empty((graph.num_rows, module.total_mass_encoding_dim + module.nSlices), dtype=X.dtype, device=X.device)
+            module.embed_into(X, graph, out, out_scale=out_scale, prepared=prepared)
+        ctx.module, ctx.graph, ctx.prepared, ctx.out_scale = module, graph, prepared, float(out_scale)
+        ctx.num_edges, ctx.w_dtype = edge_w.shape[0], edge_w.dtype
+        ctx.save_for_backward(X, projVecs, freqs, edge_w if edge_w.dtype == torch.float64 else X.new_zeros(0))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        module, graph, prepared, out_scale = ctx.module, ctx.graph, ctx.prepared, ctx.out_scale
+        X, V, freqs, w64 = ctx.saved_tensors
+        V, fr = V.detach(), freqs.detach().contiguous()
+        L = _lib.lib()
+        dev = X.device
+        S, has_mass = module.nSlices, module.total_mass_encoding_dim
+        need = ctx.needs_input_grad
+        g = g.contiguous()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ldp, Xp, st = prepared["ldp"], prepared["Xp"], prepared["stats"]
+        nnz, max_deg = st[_lib.STAT_NNZ], st[_lib.STAT_MAX_DEGREE]
+        tau = float(module.total_mass_pad_thresh)
+        deg = (graph.rowptr[1:] - graph.rowptr[:-1]).long()
+        rows = torch.repeat_interleave(torch.arange(graph.num_rows, device=dev), deg)
+        slot = graph.slot_of_edge[:ctx.num_edges].long()
+        wd, w_lo = graph.w[:nnz].double(), None
+        if ctx.w_dtype == torch.float64 and nnz:      # the entries' weights in float64 = graph.w + w_lo
+            kept = slot >= 0
+            wd = torch.zeros(nnz, dtype=torch.float64, device=dev).index_add_(0, slot[kept], w64.detach()[kept])
+            w_lo = (wd - graph.w[:nnz].double()).to(torch.float32)
+        m = torch.zeros(graph.num_rows, dtype=torch.float64, device=dev).index_add_(0, rows, wd)
+        gX = gV = gfreqs = gbias = gscale = gWe = None
+        gw = torch.zeros(max(nnz, 1), dtype=torch.float32, device=dev)
+        if nnz and S:
+            a = module.make_args(graph, st, Xp, ldp, fr, S, None, None, 0, None, out_scale, has_mass)
+            if not bool((m < tau).any()):
+                a.tau = 0.5 * tau                      # no row is padded: _GenericEmbedFn.key_grads explains
+            nbytes = int(L.fsw_embed_backward_w_scratch_bytes(max_deg, graph.num_rows))
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+            gkey = torch.empty((nnz, S), dtype=torch.float32, device=dev)
+            gf = torch.zeros(S, dtype=torch.float32, device=dev)
+            _lib.check(L.fsw_embed_backward_w_lo_f32(ctypes.byref(a), _lib.ptr(w_lo), max_deg, _lib.ptr(g), g.stride(0), _lib.ptr(gkey), S,
+                                                     _lib.ptr(gf), _lib.ptr(gw), _lib.ptr(scratch), nbytes, stream),
+                       "fsw_embed_backward_w_lo_f32")
+            if need[0] or need[1]:
+                gXp = torch.zeros((X.shape[0], ldp), dtype=torch.float32, device=dev)
+                cptr, order = graph.sender_major()
+                _lib.check(L.fsw_segment_sum_rows_f32(_lib.ptr(gkey), S, _lib.ptr(cptr), _lib.ptr(order), graph.num_cols, nnz, S,
+                                                      _lib.ptr(gXp), ldp, stream), "fsw_segment_sum_rows_f32")
+                if need[0]:
+                    gX = _grad_x(L, gXp, S, ldp, V[:, :module.d_in], stream)
+                if need[1]:
+                    gV = gemm_tn(gXp[:, :S], X.detach())
+            del gkey
+            gfreqs = gf
+        if need[0] and gX is None:
+            gX = torch.zeros_like(X)
+        if need[1] and gV is None:
+            gV = torch.zeros_like(V)
+        if need[2] and gfreqs is None:
+            gfreqs = torch.zeros_like(freqs)
+        if need[3]:
+            gbias = out_scale * g.sum(dim=0)
+        fn = module.total_mass_encoding_function
+        m32 = m.to(torch.float32)
+        if need[4]:
+            gscale = (out_scale * (g[:, 0] * _mass_f(fn, m32)).sum()).reshape(())
+        if need[5]:
+            if has_mass and nnz:      # the total-mass column depends on the weights through m
+                gw[:nnz] += (out_scale * module._mass_scale_read(st) * g[:, 0] * _mass_df(fn, m32))[rows]
+            gWe = torch.where(slot >= 0, gw[slot.clamp(min=0)], torch.zeros((), dtype=torch.float32, device=dev)).to(ctx.w_dtype)
+        return gX, gV, gfreqs if need[2] else None, gbias, gscale, gWe, None, None, None
+
+
 def _flat_batch_index(idx, batch_dims):
     """Row-major position in the flattened batch of every entry of a COO index matrix idx [len(batch_dims) + ..., nnz]."""
     strides = torch.tensor(list(np.cumprod((batch_dims + (1,))[::-1])[::-1][1:]), device=idx.device, dtype=torch.int64)
@@ -1395,12 +1490,20 @@ class FSW_embedding(nn.Module):
             out = out.add_(out_scale * bias) if in_place else out + out_scale * bias
         return P if in_place else out
 
-    def embed_autograd(self, X, graph, out_scale=1.0, edge_feat=None, slice_range=None, group=None, reduce_grads=False):
+    def embed_autograd(self, X, graph, out_scale=1.0, edge_feat=None, slice_range=None, group=None, reduce_grads=False,
+                       edge_weight=None):
         """Differentiable embedding of a CSR graph (training path): see _EmbedGraphFn.  edge_feat: the per-input-edge
         feature tensor the graph was coalesced from (its gradient is routed back through graph.slot_of_edge).
-        slice_range / group: this rank's block of slices under slice sharding (dist.py)."""
+        slice_range / group: this rank's block of slices under slice sharding (dist.py).
+        edge_weight: the per-input-edge weights [num_input_edges] a coalesced graph (want_slots=True, no edge features) was built
+        from; the embedding is then differentiable in them too (_EmbedGraphWFn; 'plain' mass encoding, no slice sharding)."""
         bias = self.bias if self.enable_bias else None
         scale = self.total_mass_encoding_scale if self.encode_total_mass else None
+        if edge_weight is not None:
+            if not self.plain_mass or edge_feat is not None or slice_range is not None or self.cartesian_mode:
+                raise NotImplementedError("fsw_gnn_amd: gradients of the edge weights need total_mass_encoding_method='plain', diagonal "
+                                          "mode, no edge features and no slice sharding")
+            return _EmbedGraphWFn.apply(X, self.projVecs, self.freqs, bias, scale, edge_weight, self, graph, out_scale)
         if self.plain_mass:
             return _EmbedGraphFn.apply(X, self.projVecs, self.freqs, bias, scale, edge_feat, self, graph, out_scale, slice_range, group,
                                        reduce_grads, True)

@@ -362,6 +362,30 @@ int fsw_graph_transpose(const int32_t* col, int64_t nnz, int64_t num_cols, int32
 int fsw_segment_sum_rows_f32(const float* src, int64_t lds, const int32_t* ptr, const int32_t* order, int64_t num_out, int64_t nnz,
                              int S, float* out, int64_t ldo, fsw_stream_t stream);
 
+/* Backward WITH the gradient of the weights, float32, diagonal mode, no edge features (csrc/embed_w_bwd.hip).  args as for
+ * fsw_embed_backward_keys_f32 with w != NULL and efeat == NULL (an error otherwise); args->tau is used as given.  For the output
+ * gradient g [num_rows, ldg] (column has_mass + k belongs to slice k):
+ *   gkey[e * ldk + k]  = out_scale * g[r, k] * d out[r, k] / d key_e      (stored, every entry)
+ *   gfreq[k]          += out_scale * sum_r g[r, k] * d out[r, k] / d xi_k  (accumulated; nullable)
+ *   gw[e]             += out_scale * sum_k g[r, k] * d out[r, k] / d w_e   (accumulated: zeroed by the caller; the total-mass
+ *                        column's dependence on w is NOT included)
+ * Rows of 1 .. 24 neighbours run on register kernels (float64 coefficients, the 64 slices of a chunk summed in float64, one float32
+ * atomic per entry and chunk); every longer row runs on the generic kernel below (value_dtype 0), launched only when the host-side
+ * row counts of args (bin_start_host, else num_lds_rows / num_global_rows; -1 = unknown) say such rows exist, with
+ * scratch of fsw_embed_backward_w_scratch_bytes(max_degree, num_rows) bytes (0 when max_degree <= 24: scratch may be NULL).
+ * max_degree: host value, an upper bound of the longest row.                                                         */
+size_t fsw_embed_backward_w_scratch_bytes(int64_t max_degree, int64_t num_rows);
+int fsw_embed_backward_w_f32(const fsw_embed_args* args, int64_t max_degree, const float* g, int64_t ldg, float* gkey, int64_t ldk,
+                             float* gfreq, float* gw, void* scratch, size_t scratch_bytes, fsw_stream_t stream);
+/* The same with weights of more than float32 precision: entry e has the weight w[e] + w_lo[e] (w_lo [nnz], NULL = 0), summed in
+ * float64 by the register kernels -- weights that the host computed in float64 ('gcn' normalisation, sums of parallel edges) and
+ * split into a float32 value and its float32 remainder.  d out / d w at frequency xi feels a weight's rounding times 2 pi xi, so the
+ * 2^-25 of a float32 weight shows in the gradient of a short row at xi ~ 100 (DESIGN.md "Per-edge weights").  The rows above 24
+ * neighbours (generic kernel) and the forward read w alone.                                                              */
+int fsw_embed_backward_w_lo_f32(const fsw_embed_args* args, const float* w_lo, int64_t max_degree, const float* g, int64_t ldg,
+                                float* gkey, int64_t ldk, float* gfreq, float* gw, void* scratch, size_t scratch_bytes,
+                                fsw_stream_t stream);
+
 /* ---- generic neighbourhood kernel: any in-degree, float32 or float64 storage, float64 arithmetic -------------------------
  * (csrc/embed_generic.hip; fsw_embed_cart_generic below is the same kernel read out at every frequency)  Two uses:
  *   value_dtype 1 (float64): the float64 build of the path -- FSW_embedding / FSW_conv(dtype=torch.float64), which the
