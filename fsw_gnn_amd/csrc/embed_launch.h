@@ -83,6 +83,15 @@ GenArgs generic_args(const P& p, bool cartesian, int F) {
 // value_dtype 0 float32, 1 float64; rows[0 .. num_rows - 1] (null: all of 0 .. num_rows - 1) of at least min_deg neighbours
 int launch_embed_generic(GenArgs a, int value_dtype, const int32_t* rows, int64_t num_rows, int min_deg, hipStream_t stream);
 
+// backward with the gradient of the weights (fsw_embed_backward_w_f32, embed_w_bwd.hip): register kernels for rows of up to
+// kWRegMaxDeg neighbours, embed_w_sort_bwd.hip (one (row, slice) line per wavefront) up to kWSortMaxDeg, the generic kernel above.
+// 1024, not FSW_LDS_MAX_DEG: the instance of 64 ranks per lane for 1025 .. 2048 neighbours spills (DESIGN.md has the table).
+constexpr int kWRegMaxDeg = 24;
+constexpr int kWSortMaxDeg = 1024;
+constexpr int kWSortLastBin = FSW_BIN_LDS0 + 1;   // 513 .. 1024
+int launch_embed_wsort_w_bwd(const fsw_embed_args& a, const float* w_lo, const float* g, int64_t ldg, float* gkey, int64_t ldk, float* gfreq,
+                             float* gw, hipStream_t stream);
+
 // backward: embed_mid_bwd.hip (33 .. 128) and embed_wsort_bwd.hip (everything above FSW_REG_MAX_DEG; global: rows above FSW_LDS_MAX_DEG)
 int launch_embed_mid_bwd(const fsw_embed_args& a, int64_t rows_upper, const float* g, int64_t ldg, float* gXp, int64_t ldgp,
                          float* gfreq, float* gkey, int64_t ldk, hipStream_t stream);

@@ -25,9 +25,9 @@
 namespace fsw {
 
 constexpr int kWBwdRows = 32;
-// Rows above go to the generic kernel (fsw_embed_backward_w_f32).  24, not FSW_REG_MAX_DEG: the form below for 25 .. 32 neighbours
-// (key, cum / R and q of 32 elements live at once) spills 244 - 324 bytes per lane at 512 registers; DESIGN.md has the table.
-constexpr int kWRegMaxDeg = 24;
+// Rows above kWRegMaxDeg (embed_launch.h) go to the wave-sort kernels of embed_w_sort_bwd.hip.  24, not FSW_REG_MAX_DEG: the form below
+// for 25 .. 32 neighbours (key, cum / R and q of 32 elements live at once) spills 244 - 324 bytes per lane at 512 registers; DESIGN.md
+// has the table.
 static_assert(kWRegMaxDeg <= FSW_REG_MAX_DEG, "the degree bins are exact up to FSW_REG_MAX_DEG only");
 
 constexpr int w_pow2(int d) { int p = 1; while (p < d) p <<= 1; return p; }
@@ -186,9 +186,12 @@ static int launch_w_bwd(const fsw_embed_args& a, const float* w_lo, int64_t nreg
 
 using namespace fsw;
 
+// an upper bound since the rows of 25 .. kWSortMaxDeg neighbours left the generic kernel: what it returned before, for every input
 extern "C" size_t fsw_embed_backward_w_scratch_bytes(int64_t max_degree, int64_t num_rows) {
   return max_degree > kWRegMaxDeg ? fsw_embed_generic_scratch_bytes(max_degree, num_rows) : 0;
 }
+
+extern "C" int fsw_embed_backward_w_tuned_max_degree(void) { return kWSortMaxDeg; }
 
 static int embed_backward_w(const fsw_embed_args* args, const float* w_lo, int64_t max_degree, const float* g, int64_t ldg,
                             float* gkey, int64_t ldk, float* gfreq, float* gw, void* scratch, size_t scratch_bytes,
@@ -209,19 +212,21 @@ static int embed_backward_w(const fsw_embed_args* args, const float* w_lo, int64
     if ((rc = launch_w_bwd<9, 16>(a, w_lo, nreg, g, ldg, gkey, ldk, gfreq, gw, stream))) return rc;
     if ((rc = launch_w_bwd<1, 8>(a, w_lo, nreg, g, ldg, gkey, ldk, gfreq, gw, stream))) return rc;
   }
-  // every longer row: the generic kernel, by row index over the whole graph, skipping the rows of the class above
-  bool longer = max_degree > kWRegMaxDeg;
-  if (longer && a.bin_start_host) longer = a.bin_start_host[FSW_NUM_BINS] > a.bin_start_host[kWRegMaxDeg + 1];
-  else if (longer && kWRegMaxDeg == FSW_REG_MAX_DEG) longer = a.num_lds_rows != 0 || a.num_global_rows != 0;
+  // 25 .. kWSortMaxDeg neighbours: one (row, slice) line per wavefront (embed_w_sort_bwd.hip), every bin that has rows
+  if (max_degree > kWRegMaxDeg && (rc = launch_embed_wsort_w_bwd(a, w_lo, g, ldg, gkey, ldk, gfreq, gw, stream))) return rc;
+  // every longer row: the generic kernel, by row index over the whole graph, skipping the rows of the classes above
+  bool longer = max_degree > kWSortMaxDeg;
+  if (longer && a.bin_start_host) longer = a.bin_start_host[FSW_NUM_BINS] > a.bin_start_host[kWSortLastBin + 1];
+  else if (longer) longer = a.num_lds_rows != 0 || a.num_global_rows != 0;   // -1: unknown
   if (longer) {
     FSW_REQUIRE(scratch, "fsw_embed_backward_w_f32: rows above %d neighbours need scratch (fsw_embed_backward_w_scratch_bytes)",
-                kWRegMaxDeg);
+                kWSortMaxDeg);
     GenArgs ga = {};
     ga.rowptr = a.rowptr; ga.col = a.col; ga.w = a.w; ga.Xp = a.Xp; ga.ldp = a.ldp; ga.freqs = a.freqs; ga.S = a.S; ga.F = 1;
     ga.cartesian = false; ga.tau = (double)a.tau; ga.out_scale = (double)a.out_scale; ga.has_mass = a.has_mass;
     ga.g = g; ga.ldg = ldg; ga.gkey = gkey; ga.ldk = ldk; ga.gfreq = gfreq; ga.gw = gw;
     ga.scratch = (char*)scratch; ga.scratch_bytes = scratch_bytes; ga.max_degree = max_degree;
-    if ((rc = launch_embed_generic(ga, 0, nullptr, a.num_rows, kWRegMaxDeg + 1, stream))) return rc;
+    if ((rc = launch_embed_generic(ga, 0, nullptr, a.num_rows, kWSortMaxDeg + 1, stream))) return rc;
   }
   return 0;
 }

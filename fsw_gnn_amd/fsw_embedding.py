@@ -311,9 +311,10 @@ class _EmbedGraphWFn(torch.autograd.Function):
     built from -- only the gradient is routed to it, the forward kernels read graph.w.  A float64 edge_w (FSW_conv: the self-loop
     and 'gcn' arithmetic in float64) gives the backward the entries' weights beyond float32: w_lo = sum of the entry's edge_w - graph.w
     (fsw_embed_backward_w_lo_f32), because d out / d w at frequency xi feels a weight's rounding times 2 pi xi.
-    Forward: the tuned path of _EmbedGraphFn (prepare + embed_into).  Backward: fsw_embed_backward_w_f32 (csrc/embed_w_bwd.hip: rows
-    of up to 24 neighbours on the register kernels, longer rows on the generic kernel) stores the key gradients per entry and
-    accumulates gfreq and gw; gXp is their sum sender by sender (graph.sender_major + fsw_segment_sum_rows_f32).  The total-mass
+    Forward: the tuned path of _EmbedGraphFn (prepare + embed_into).  Backward: fsw_embed_backward_w_f32 (rows of up to 24
+    neighbours on the register kernels of csrc/embed_w_bwd.hip, rows of 25 .. fsw_embed_backward_w_tuned_max_degree() = 1024 on the
+    wave-sort kernels of csrc/embed_w_sort_bwd.hip, one (row, slice) line per wavefront; only longer rows on the generic kernel,
+    which reads the float32 weights alone) stores the key gradients per entry and accumulates gfreq and gw; gXp is their sum sender by sender (graph.sender_major + fsw_segment_sum_rows_f32).  The total-mass
     column depends on the weights through m: out_scale scale g[:, 0] f'(m) per recipient is added, as in _GenericEmbedFn.backward.
     Pad rule: as _GenericEmbedFn.key_grads -- without a deficient row (empty recipients included) the launch gets tau / 2."""
 
@@ -360,7 +361,8 @@ class _EmbedGraphWFn(torch.autograd.Function):
             a = module.make_args(graph, st, Xp, ldp, fr, S, None, None, 0, None, out_scale, has_mass)
             if not bool((m < tau).any()):
                 a.tau = 0.5 * tau                      # no row is padded: _GenericEmbedFn.key_grads explains
-            nbytes = int(L.fsw_embed_backward_w_scratch_bytes(max_deg, graph.num_rows))
+            # scratch: only the generic kernel's, for rows above the tuned classes (the query is an upper bound)
+            nbytes = int(L.fsw_embed_backward_w_scratch_bytes(max_deg, graph.num_rows)) if max_deg > L.fsw_embed_backward_w_tuned_max_degree() else 0
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
             gkey = torch.empty((nnz, S), dtype=torch.float32, device=dev)
             gf = torch.zeros(S, dtype=torch.float32, device=dev)

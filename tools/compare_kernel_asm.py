@@ -19,7 +19,7 @@ import sys
 
 UNITS = [(f, "", f) for f in ("api graph_build graph_import project embed_reg embed_wsort embed_generic embed_wsort_bwd embed_api conv_fused "
                               "embed_bwd segcumsum gemm_tn embed_cart embed_cart_bwd embed_cart_hub embed_cart_hub_bwd embed_cart_hub_w "
-                              "embed_cart_hub_w_bwd embed_giant_cart embed_split_cart embed_giant_cart_w embed_split_cart_w embed_giant_cart_bwd embed_split_cart_bwd embed_split_cart_w_bwd edge_keys embed_w_bwd").split()]
+                              "embed_cart_hub_w_bwd embed_giant_cart embed_split_cart embed_giant_cart_w embed_split_cart_w embed_giant_cart_bwd embed_split_cart_bwd embed_split_cart_w_bwd edge_keys embed_w_bwd embed_w_sort_bwd").split()]
 UNITS += [("embed_mid", "-DFSW_MID_PART=%d" % p, "embed_mid_%d" % p) for p in range(3)]
 UNITS += [("embed_mid_bwd", "-DFSW_MID_BWD_PART=%d" % p, "embed_mid_bwd_%d" % p) for p in range(2)]
 UNITS += [("embed_hub", "-DFSW_HUB_PART=%d" % p, "embed_hub_%d" % p) for p in range(3)]

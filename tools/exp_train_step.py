@@ -4,8 +4,11 @@
     python tools/exp_train_step.py --rmat 20  RMAT graph with 2^20 vertices and 10M edges (hubs up to 41 300 neighbours)
     python tools/exp_train_step.py --rmat 22 --edges 64000000 --feat 256 --forward-only [--gcn]   BASELINE config 5's shape
     python tools/exp_train_step.py --edge-weights   learnable per-edge weights (FSW_conv.forward(edge_weight=)): the training step, and
-                                                    the embedding's backward on csrc/embed_w_bwd.hip against the generic kernel's
-                                                    (FSW_embedding.forward with a sparse COO W that requires grad), alternating
+                                                    the embedding's backward on the tuned kernels (csrc/embed_w_bwd.hip up to 24
+                                                    neighbours, csrc/embed_w_sort_bwd.hip up to the library's class limit, the
+                                                    generic kernel for the rows above) against the generic kernel's for every row
+                                                    (FSW_embedding.forward with a sparse COO W that requires grad), alternating;
+                                                    also the share of the entries in each of the three classes
 """
 import argparse, os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -53,19 +56,28 @@ if args.edge_weights:
     adj = torch.sparse_coo_tensor(ei.flip(0), w.detach(), (n, n)).coalesce()
     vals = adj.values().clone().requires_grad_(True)
 
-    def generic_route():      # the only route to this gradient without csrc/embed_w_bwd.hip: _GenericEmbedFn
+    def generic_route():      # the only route to this gradient without the tuned kernels: _GenericEmbedFn
         return emb(x, W=torch.sparse_coo_tensor(adj.indices(), vals, (n, n), is_coalesced=True), graph_mode=True)
 
-    times = {"register kernels (embed_w_bwd.hip)": [], "generic kernel": []}
+    from fsw_gnn_amd import _lib
+    limit = int(_lib.lib().fsw_embed_backward_w_tuned_max_degree())
+    deg = torch.bincount(adj.indices()[0], minlength=n)          # entries per recipient of the coalesced adjacency
+    nnz = int(deg.sum())
+    share = [int(deg[sel].sum()) / nnz for sel in (deg <= 24, (deg > 24) & (deg <= limit), deg > limit)]
+    print("entries per class: <= 24 neighbours (register kernels) %.1f %%, 25 .. %d (wave-sort kernels) %.1f %%, above (generic kernel) "
+          "%.1f %% of %d; rows: %d / %d / %d" % (100 * share[0], limit, 100 * share[1], 100 * share[2], nnz, int((deg <= 24).sum()),
+                                                 int(((deg > 24) & (deg <= limit)).sum()), int((deg > limit).sum())), flush=True)
+    tuned = "tuned kernels (embed_w_bwd.hip, embed_w_sort_bwd.hip; generic above %d)" % limit
+    times = {tuned: [], "generic kernel": []}
     for i in range(args.runs + 1):                      # run 0 warms both up
-        for name, fn in (("register kernels (embed_w_bwd.hip)", new_route), ("generic kernel", generic_route)):
+        for name, fn in ((tuned, new_route), ("generic kernel", generic_route)):
             ms = timed_backward(fn)
             if i:
                 times[name].append(ms)
     for name, v in times.items():
         print("embedding backward with dL/dW, %s: %.1f - %.1f ms over %d runs" % (name, min(v), max(v), len(v)), flush=True)
     a, b = times.values()
-    print("ranges %s" % ("do not overlap: the register kernels are faster" if max(a) < min(b) else "overlap or the generic kernel is faster"))
+    print("ranges %s" % ("do not overlap: the tuned kernels are faster" if max(a) < min(b) else "overlap or the generic kernel is faster"))
     print("gkey buffer: %.2f GB" % (int(adj.values().numel()) * 256 * 4 / 1e9))
 
     def step_w():
