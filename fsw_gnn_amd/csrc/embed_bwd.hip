@@ -94,10 +94,6 @@ __device__ __forceinline__ void unit_bwd_rows(int p, int pe, const int32_t* __re
   if (kvalid && gfreq) atomicAdd(gfreq + k, gf);
 }
 
-#define FSW_BWD_CASES(X)                                                                                               \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) \
-  X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-
 template <int DLO, int DHI>
 __global__ void __launch_bounds__(256) k_embed_reg_unit_bwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                             const int32_t* __restrict__ perm, const int32_t* __restrict__ bin_start,
@@ -108,11 +104,7 @@ __global__ void __launch_bounds__(256) k_embed_reg_unit_bwd(const int32_t* __res
                                                             float* __restrict__ gfreq, float* __restrict__ gkey, int64_t ldk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int wv = wave_id();
-  const int chunk = blockIdx.y * 4 + wv;
-  if (chunk * kWave >= S) return;
-  const int k = chunk * kWave + lane_id();
-  const bool kvalid = k < S;
-  const int kc = kvalid ? k : S - 1;
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   int D, p = 0, pe = 0;
   if (!find_degree_tile<kBwdRows>(bin_start, DLO, DHI, (int)blockIdx.x, D, p, pe)) return;   // fsw_common.h
   float* cS = smem + wv * (2 * DHI * kWave);
@@ -123,7 +115,7 @@ __global__ void __launch_bounds__(256) k_embed_reg_unit_bwd(const int32_t* __res
       unit_bwd_rows<d>(p, pe, rowptr, col, perm, Xp, ldp, table, dtable, ldt, g, ldg, gcol0, out_scale, gXp, ldgp,    \
                        gfreq, cS, k, kc, kvalid, gkey, ldk);                                                          \
     break;
-    FSW_BWD_CASES(X)
+    FSW_CASES_1_32(X)
 #undef X
     default:
       break;
@@ -156,7 +148,7 @@ __device__ __forceinline__ void weighted_bwd_rows(int p, int pe, const int32_t* 
     for (int t = 0; t < DEG; ++t) {
       cidx[t] = col[start + t];
       key[t] = Xp[(int64_t)cidx[t] * ldp + kc];
-      if (efeat) {
+      if (efeat) {   // a copy of add_edge_term (fsw_common.h): DESIGN.md, open work of the diagonal-mode steps
         const float* er = efeat + (int64_t)(start + t) * d_edge;
         const float* vr = Ve + (int64_t)kc * ldve;
         for (int q = 0; q < d_edge; ++q) key[t] = fmaf(er[q], vr[q], key[t]);
@@ -204,11 +196,7 @@ __global__ void __launch_bounds__(256) k_embed_reg_weighted_bwd(const int32_t* _
                                                                 float* __restrict__ gXp, int64_t ldgp, float* __restrict__ gfreq,
                                                                 const float* __restrict__ efeat, const float* __restrict__ Ve,
                                                                 int64_t ldve, int d_edge, float* __restrict__ gkey, int64_t ldk) {
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
-  const int k = chunk * kWave + lane_id();
-  const bool kvalid = k < S;
-  const int kc = kvalid ? k : S - 1;
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   int D, p = 0, pe = 0;
   if (!find_degree_tile<kBwdRows>(bin_start, 1, FSW_REG_MAX_DEG, (int)blockIdx.x, D, p, pe)) return;
   switch (D) {
@@ -217,7 +205,7 @@ __global__ void __launch_bounds__(256) k_embed_reg_weighted_bwd(const int32_t* _
     weighted_bwd_rows<d>(p, pe, rowptr, col, w, perm, Xp, ldp, freqs, tau, g, ldg, gcol0, out_scale, gXp, ldgp, gfreq, k, kc, \
                          kvalid, efeat, Ve, ldve, d_edge, gkey, ldk);                                                        \
     break;
-    FSW_BWD_CASES(X)
+    FSW_CASES_1_32(X)
 #undef X
     default:
       break;
@@ -304,11 +292,7 @@ constexpr int kSegLen = 256;
 __global__ void __launch_bounds__(256) k_segment_sum_rows(const float* __restrict__ src, int64_t lds, const int32_t* __restrict__ ptr,
                                                           const int32_t* __restrict__ order, int64_t num_out, int64_t nnz, int S,
                                                           float* __restrict__ out, int64_t ldo) {
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
-  const int k = chunk * kWave + lane_id();
-  const bool kvalid = k < S;
-  const int kc = kvalid ? k : S - 1;
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   // entries past ptr[num_out] belong to no sender (fsw_graph_transpose sorts out-of-range columns there): never walked
   const int64_t q0 = (int64_t)blockIdx.x * kSegLen, q1 = min(q0 + kSegLen, min(nnz, (int64_t)ptr[num_out]));
   if (q0 >= q1) return;

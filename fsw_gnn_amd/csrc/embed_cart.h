@@ -26,10 +26,6 @@ using ConstAS = const T;   // host pass of the same source: no address spaces
 template <class T>
 __device__ __forceinline__ ConstAS<T>* as_const(const T* p) { return (ConstAS<T>*)p; }
 
-#define FSW_CART_CASES_1_32(X)                                                                                         \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) \
-  X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-
 // embed_cart.hip
 int cart_check_common(const fsw_cart_args* c);                // the checks every Cartesian entry point starts with
 

@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(256) k_cart_reg(const CartTuned a) {
     if constexpr (UNIT) cart_reg_unit<d, VEC>(a, p, pe); \
     else cart_reg_weighted<d>(a, p, pe);           \
     break;
-    FSW_CART_CASES_1_32(X)
+    FSW_CASES_1_32(X)
 #undef X
     default:
       break;

@@ -259,7 +259,7 @@ __global__ void __launch_bounds__(256) k_cart_bwd_reg(const CartBwd a) {
     if constexpr (UNIT) cart_bwd_reg_unit<d, VEC>(a, p, pe, sgf, tr);  \
     else cart_bwd_reg_weighted<d>(a, p, pe, sgf, tr);                  \
     break;
-      FSW_CART_CASES_1_32(X)
+      FSW_CASES_1_32(X)
 #undef X
       default:
         break;

@@ -31,9 +31,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_unit(const int32_t* __restric
                                                         const float* __restrict__ freqs, float* __restrict__ out, int64_t ldo,
                                                         const float* __restrict__ bias, float out_scale, int has_mass,
                                                         int mass_fn, float mass_scale) {
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
-  const int kc = min(chunk * kWave + lane_id(), S - 1);   // lanes past the last slice recompute slice S-1 (same value, same address)
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   const int pbeg = bin_start[bin], pend = bin_start[bin + 1];
   const float xif = freqs[kc];
   const double xi = (double)xif;
@@ -109,10 +107,8 @@ __global__ void __launch_bounds__(256, 1) k_embed_mid_unit_pf(const int32_t* __r
                                                            int mass_fn, float mass_scale) {
   static_assert(PF >= 0 && PF <= DP, "prefetched wires");
   constexpr int NCV = (DP + kWave - 1) / kWave;
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   const int lane = lane_id();
-  const int kc = min(chunk * kWave + lane, S - 1);
   const int pbeg = bin_start[bin], pend = bin_start[bin + 1];
   const float xif = freqs[kc];
   const double xi = (double)xif;
@@ -216,9 +212,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
                                                             int has_mass, int mass_fn, float mass_scale,
                                                             const float* __restrict__ efeat, const float* __restrict__ Ve,
                                                             int64_t ldve, int d_edge) {
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
-  const int kc = min(chunk * kWave + lane_id(), S - 1);
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   const int pbeg = bin_start[bin], pend = bin_start[bin + 1];
   const float xif = freqs[kc];
   const double xi = (double)xif;
@@ -239,11 +233,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_weighted(const int32_t* __res
       if (t < D) {
         const float wt = w ? w[start + t] : 1.f;
         float key = Xp[(int64_t)col[start + t] * ldp + kc];
-        if (efeat) {   // edge features: + <e_ij, v_k[d_in:]> (reference fsw_embedding.py:934-968)
-          const float* er = efeat + (int64_t)(start + t) * d_edge;
-          const float* vr = Ve + (int64_t)kc * ldve;
-          for (int q = 0; q < d_edge; ++q) key = fmaf(er[q], vr[q], key);
-        }
+        if (efeat) key = add_edge_term(key, start + t, kc, efeat, Ve, ldve, d_edge);
         net.k[t] = key;
         net.w[t] = wt;
         m += (double)wt;

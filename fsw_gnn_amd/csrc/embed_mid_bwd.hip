@@ -10,31 +10,10 @@
 // F(xi; c) = (1 + xi) sin(2 pi xi c)/(pi xi), see embed_wsort_bwd.hip (which serves the rows above 128).
 #include <algorithm>
 #include "embed_launch.h"
+#include "fourier_coef.h"
 #include "sortnet.h"
 
 namespace fsw {
-
-
-struct FCoefM {
-  double xi, a1, a2, a3;   // a1 = (1 + xi)/(pi xi), a2 = 1/(pi xi^2), a3 = 2 (1 + xi)/xi: no division left per element
-  __device__ __forceinline__ explicit FCoefM(double x) : xi(x) {
-    const double r = x != 0.0 ? 1.0 / x : 0.0;
-    a1 = (1.0 + x) * r * (1.0 / kPi);
-    a2 = r * r * (1.0 / kPi);
-    a3 = 2.0 * (1.0 + x) * r;
-  }
-};
-__device__ __forceinline__ void F_dF_sc_m(const FCoefM& f, double c, double s, double co, double& F, double& dF) {
-  const double x = 2.0 * kPi * f.xi * c;
-  if (fabs(x) < 1e-4) {   // series: the two terms of dF cancel for tiny phases; xi == 0 gives F = dF = 2 c
-    const double q = 1.0 - x * x * (1.0 / 6.0);
-    F = (1.0 + f.xi) * 2.0 * c * q;
-    dF = 2.0 * c * q - (1.0 + f.xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * f.xi * (1.0 / 3.0);
-  } else {
-    F = f.a1 * s;
-    dF = fma(f.a3 * c, co, -(f.a2 * s));
-  }
-}
 
 // DP wires: the bin's padded degree, + 1 for the reference's pad element when WEIGHTED
 template <int DP, bool WEIGHTED>
@@ -48,16 +27,12 @@ __global__ void __launch_bounds__(256) k_embed_mid_bwd(const int32_t* __restrict
                                                        const float* __restrict__ Ve, int64_t ldve, int d_edge,
                                                        float* __restrict__ gkey, int64_t ldk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   const int lane = lane_id();
-  const int k = chunk * kWave + lane;
-  const bool kvalid = k < S;
-  const int kc = kvalid ? k : S - 1;
   float* tile = smem + wave_id() * (DP * kWave) + lane;   // [element][lane] of this wave
   const int pbeg = bin_start[bin], pend = bin_start[bin + 1];
   const double xi = (double)freqs[kc];
-  const FCoefM fc(xi);
+  const FCoef fc(xi);
   const double taud = (double)tau;
   float gf = 0.f;
   for (int p = pbeg + blockIdx.x; p < pend; p += gridDim.x) {
@@ -73,11 +48,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_bwd(const int32_t* __restrict
       float key = __builtin_inff();
       if (t < D) {
         key = Xp[(int64_t)col[start + t] * ldp + kc];
-        if (efeat) {   // edge features: + <e_ij, v_k[d_in:]> (reference fsw_embedding.py:934-968)
-          const float* er = efeat + (int64_t)(start + t) * d_edge;
-          const float* vr = Ve + (int64_t)kc * ldve;
-          for (int q = 0; q < d_edge; ++q) key = fmaf(er[q], vr[q], key);
-        }
+        if (efeat) key = add_edge_term(key, start + t, kc, efeat, Ve, ldve, d_edge);
         if constexpr (WEIGHTED) m += (double)(w ? w[start + t] : 1.f);
       } else if (WEIGHTED && t == D) {
         key = 0.f;   // the reference's pad element at x = 0
@@ -100,7 +71,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_bwd(const int32_t* __restrict
           s = sn;
           c = cn;
           double F, dF;
-          F_dF_sc_m(fc, (double)(r + 1) * inv, s, c, F, dF);
+          F_dF_sc(fc, (double)(r + 1) * inv, s, c, F, dF);
           tile[(int)(unsigned int)net.e[r] * kWave] = gi * (float)(F - Fp);
           gf = fmaf(gi * (float)(dF - dFp), from_orderable_bits((unsigned int)(net.e[r] >> 32)), gf);
           Fp = F;
@@ -117,7 +88,7 @@ __global__ void __launch_bounds__(256) k_embed_mid_bwd(const int32_t* __restrict
           const double ph = xi * (c * inv);
           double s, co, F, dF;
           sincospi(2.0 * (ph - rint(ph)), &s, &co);
-          F_dF_sc_m(fc, c * inv, s, co, F, dF);
+          F_dF_sc(fc, c * inv, s, co, F, dF);
           if (id < D) tile[id * kWave] = gi * (float)(F - Fp);   // the pad element has no source row
           gf = fmaf(gi * (float)(dF - dFp), from_orderable_bits((unsigned int)(net.e[r] >> 32)), gf);
           Fp = F;

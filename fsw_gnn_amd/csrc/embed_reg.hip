@@ -118,21 +118,13 @@ __device__ __forceinline__ void unit_run(int p, int pe, const int32_t* __restric
       });
 }
 
-#define FSW_CASES_1_32(X)                                                                                              \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) \
-  X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
-
 __global__ void __launch_bounds__(256) k_embed_reg_unit(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                         const int32_t* __restrict__ perm, const int32_t* __restrict__ bin_start,
                                                         const float* __restrict__ Xp, int64_t ldp, int S,
                                                         const float* __restrict__ table, int64_t ldt, float* __restrict__ out,
                                                         int64_t ldo, const float* __restrict__ bias, float out_scale,
                                                         int has_mass, int mass_fn, float mass_scale) {
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
-  const int k = chunk * kWave + lane_id();
-  const bool kvalid = k < S;
-  const int kc = kvalid ? k : S - 1;
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   int D, p, pe;
   if (!block_range(bin_start, D, p, pe)) return;
   switch (D) {
@@ -206,11 +198,7 @@ __device__ __forceinline__ void weighted_run(int p, int pe, const int32_t* __res
       const int c = col[start + t];
       const float wt = w ? w[start + t] : 1.f;
       float key = Xp[(int64_t)c * ldp + kc];
-      if (efeat) {   // edge features: + <e_ij, v_k[d_in:]>, the feature row is wave-uniform (reference fsw_embedding.py:934-968)
-        const float* er = efeat + (int64_t)(start + t) * d_edge;
-        const float* vr = Ve + (int64_t)kc * ldve;
-        for (int q = 0; q < d_edge; ++q) key = fmaf(er[q], vr[q], key);
-      }
+      if (efeat) key = add_edge_term(key, start + t, kc, efeat, Ve, ldve, d_edge);   // the feature row is wave-uniform
       net.k[t] = key;
       net.w[t] = wt;
       m += (double)wt;
@@ -247,11 +235,7 @@ __global__ void __launch_bounds__(256) k_embed_reg_weighted(const int32_t* __res
                                                             float out_scale, int has_mass, int mass_fn, float mass_scale,
                                                             const float* __restrict__ efeat, const float* __restrict__ Ve,
                                                             int64_t ldve, int d_edge) {
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
-  const int k = chunk * kWave + lane_id();
-  const bool kvalid = k < S;
-  const int kc = kvalid ? k : S - 1;
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   const bool mass_lane = has_mass && k == 0;
   int D, p, pe;
   if (!block_range(bin_start, D, p, pe)) return;

@@ -131,10 +131,6 @@ __device__ __forceinline__ void w_bwd_rows(int p, int pe, const int32_t* __restr
   if (kvalid && gfreq) atomicAdd(gfreq + k, gf);
 }
 
-#define FSW_W_BWD_CASES(X)                                                                                             \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) \
-  X(22) X(23) X(24)
-
 // one kernel per degree range: the register budget is that of the range's longest row
 template <int DLO, int DHI>
 __global__ void __launch_bounds__(256) k_embed_reg_w_bwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -145,11 +141,7 @@ __global__ void __launch_bounds__(256) k_embed_reg_w_bwd(const int32_t* __restri
                                                          const float* __restrict__ g, int64_t ldg, int gcol0, float out_scale,
                                                          float* __restrict__ gfreq, float* __restrict__ gkey, int64_t ldk,
                                                          float* __restrict__ gw) {
-  const int chunk = blockIdx.y * 4 + wave_id();
-  if (chunk * kWave >= S) return;
-  const int k = chunk * kWave + lane_id();
-  const bool kvalid = k < S;
-  const int kc = kvalid ? k : S - 1;
+#include "slice_chunk.inc"   // chunk, k, kvalid, kc; a wavefront behind the last slice returns
   int D, p = 0, pe = 0;
   if (!find_degree_tile<kWBwdRows>(bin_start, DLO, DHI, (int)blockIdx.x, D, p, pe)) return;
   switch (D) {
@@ -159,7 +151,7 @@ __global__ void __launch_bounds__(256) k_embed_reg_w_bwd(const int32_t* __restri
       w_bwd_rows<d>(p, pe, rowptr, col, w, w_lo, perm, Xp, ldp, freqs, tau, g, ldg, gcol0, out_scale, gfreq, k, kc, kvalid, gkey, ldk, \
                     gw);                                                                                                        \
     break;
-    FSW_W_BWD_CASES(X)
+    FSW_CASES_1_32(X)   // fsw_common.h; the cases above kWRegMaxDeg are empty
 #undef X
     default:
       break;

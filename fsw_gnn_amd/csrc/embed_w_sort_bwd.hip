@@ -22,38 +22,27 @@
 // slice groups the workgroup visits for the row; the workgroup then issues ONE float32 atomic per entry to consecutive addresses
 // of gw (none for an exactly zero sum).  An entry receives min(gridDim.y, ceil(S / SC)) float32 adds.
 // A line whose output gradient is zero writes zeros to its gkey column and adds nothing to gfreq or gw.
+// Shared with k_embed_wsort and k_embed_wsort_bwd: the line length, the slices per group, the workgroups per row and the row mass
+// (wsort_tile.h), the gather of a slice group (wsort_gather.inc) and the float64 wave scans (fsw_common.h).  The packed line load, the
+// lane's weight sum and the forward walk are copies of those of k_embed_wsort_bwd and walk_line<M, true>: DESIGN.md, "Steps that the
+// diagonal-mode kernels share", open work.
 #include <algorithm>
 #include "embed_launch.h"
 #include "sortnet.h"
 #include "wave_sort.h"
 #include "weighted_coef.h"
+#include "wsort_tile.h"
+
+#define FSW_WS_GATHER_EDGE 0   // wsort_gather.inc: no edge features here
 
 namespace fsw {
 
-constexpr int kWsSplitY = 4;
 // as k_embed_wsort_bwd: two workgroups per CU
 template <int M>
 constexpr int ws_lds_bytes() { return 69 * 1024; }
+// slices per group (wsort_tile.h): the float tile next to the two float64 lines (weights, accumulator)
 template <int M>
-constexpr int ws_line() { return M * kWave + kWave + 1; }   // one pad per M elements, odd stride
-// slices per group: the float tile next to the two float64 lines (weights, accumulator)
-template <int M>
-constexpr int ws_slices() {
-  constexpr int lines = (ws_lds_bytes<M>() / 4 - 4 * ws_line<M>()) / ws_line<M>();
-  return lines >= 64 ? 64 : (lines >= 4 ? (lines & ~3) : lines);
-}
-
-// sum of v over the lanes above this one
-__device__ __forceinline__ double wave_reverse_exclusive_scan_f64(double v) {
-  double inc = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const double t = __shfl_down(inc, off);
-    if (lane_id() + off < kWave) inc += t;
-  }
-  const double above = __shfl_down(inc, 1);
-  return lane_id() == kWave - 1 ? 0.0 : above;
-}
+constexpr int wsw_slices() { return ws_slices<M>(ws_lds_bytes<M>(), 2 * 8 * ws_line<M>()); }
 
 template <int M>
 __global__ void __launch_bounds__(256, (M <= 8 ? 2 : 1)) k_embed_wsort_w_bwd(
@@ -63,7 +52,7 @@ __global__ void __launch_bounds__(256, (M <= 8 ? 2 : 1)) k_embed_wsort_w_bwd(
     float out_scale, float* __restrict__ gfreq, float* __restrict__ gkey, int64_t ldk, float* __restrict__ gw) {
   constexpr int CAP = M * kWave;
   constexpr int LINE = ws_line<M>();
-  constexpr int SC = ws_slices<M>();
+  constexpr int SC = wsw_slices<M>();
   static_assert(SC >= 1, "a line must fit the LDS budget");
   static_assert((2 * 8 + 4 * SC) * LINE + 64 <= 160 * 1024, "LDS of one workgroup");
   extern __shared__ __attribute__((aligned(16))) double smem_d[];
@@ -93,29 +82,14 @@ __global__ void __launch_bounds__(256, (M <= 8 ? 2 : 1)) k_embed_wsort_w_bwd(
     part = wave_sum(part);
     if (lane == 0) msum[wv] = part;
     __syncthreads();
-    const double m = msum[0] + msum[1] + msum[2] + msum[3];
+    const double m = ws_row_mass(msum);
     const double inv = 1.0 / fmax(m, taud);
     const double padd = fmax(taud - m, 0.0);              // the pad weight in float64 (fsw_common.h: pad_residual)
     auto weight_of = [&](int id) -> double { return id == D ? padd : wrow[id + id / M]; };
 
     for (int grp = blockIdx.y; grp < ngroups; grp += gridDim.y) {
       const int k0 = grp * SC;
-      constexpr int kGatherDepth = 8;
-      const int total = Dtot * SC;
-      for (int i0 = threadIdx.x; i0 < total; i0 += blockDim.x * kGatherDepth) {
-        float key[kGatherDepth];
-        int pos[kGatherDepth];
-#pragma unroll
-        for (int u = 0; u < kGatherDepth; ++u) {
-          const int i = min(i0 + u * (int)blockDim.x, total - 1);
-          const int kk = i % SC, t = i / SC;
-          pos[u] = kk * LINE + t + t / M;
-          key[u] = 0.f;                                   // t == D: the reference's pad element at x = 0
-          if (t < D) key[u] = Xp[(int64_t)col[start + t] * ldp + min(k0 + kk, S - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < kGatherDepth; ++u) tile[pos[u]] = key[u];
-      }
+#include "wsort_gather.inc"
       __syncthreads();                                    // the tile, and (first group) the row's weights and zeroed sums
       for (int kk = wv; kk < SC; kk += 4) {
         const int k = k0 + kk;
@@ -139,7 +113,7 @@ __global__ void __launch_bounds__(256, (M <= 8 ? 2 : 1)) k_embed_wsort_w_bwd(
         }
         ln.sort();
         const double xi = (double)freqs[k];
-        double lanew = 0.0;
+        double lanew = 0.0;   // (a copy of the loop in k_embed_wsort_bwd)
 #pragma unroll
         for (int j = 0; j < M; ++j) lanew += (lane * M + j < Dtot) ? weight_of(ln.index(j)) : 0.0;
         const double cstart = wave_exclusive_scan_f64(lanew);
@@ -219,10 +193,10 @@ static int launch_wsort_w_bwd(const fsw_embed_args& a, const float* w_lo, int bi
                               int64_t ldk, float* gfreq, float* gw, hipStream_t stream) {
   const int64_t rows = bin_rows_or(a, bin_lo, bin_hi, a.num_rows);
   if (rows <= 0) return 0;
-  constexpr int bytes = (2 * 8 + 4 * ws_slices<M>()) * ws_line<M>();
+  constexpr int bytes = (2 * 8 + 4 * wsw_slices<M>()) * ws_line<M>();
   static_assert(bytes <= ws_lds_bytes<M>(), "the tile and the two float64 lines fit the instance's LDS");
   FSW_SET_MAX_LDS_ONCE((k_embed_wsort_w_bwd<M>), bytes);
-  dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 14), (unsigned)std::min<int64_t>(kWsSplitY, ceil_div(a.S, ws_slices<M>())));
+  dim3 grid((unsigned)std::min<int64_t>(rows, 1 << 14), (unsigned)std::min<int64_t>(kWsSplitY, ceil_div(a.S, wsw_slices<M>())));
   k_embed_wsort_w_bwd<M><<<grid, 256, bytes, stream>>>(a.rowptr, a.col, a.w, w_lo, a.perm, a.bin_start, bin_lo, bin_hi, a.Xp, a.ldp, a.S, a.freqs,
                                                        a.tau, g, ldg, a.has_mass, a.out_scale, gfreq, gkey, ldk, gw);
   FSW_LAUNCH_CHECK();

@@ -21,11 +21,13 @@
 #include "hub_line.h"
 #include "sortnet.h"
 #include "wave_sort.h"
+#include "wsort_tile.h"
+
+#define FSW_WS_GATHER_EDGE 1   // wsort_gather.inc: this kernel has edge features
 
 namespace fsw {
 
 constexpr int kWsLdsBytes = 69 * 1024;   // two workgroups per CU
-constexpr int kWsSplitY = 4;             // workgroups sharing one row (disjoint slice groups)
 
 template <int M, bool WEIGHTED>
 __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -36,15 +38,13 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
                                                      int64_t ldo, const float* __restrict__ bias, float out_scale, int has_mass,
                                                      int mass_fn, float mass_scale, const float* __restrict__ efeat,
                                                      const float* __restrict__ Ve, int64_t ldve, int d_edge) {
-  constexpr int CAP = M * kWave;          // elements a wave can hold
-  constexpr int LINE = CAP + kWave + 1;   // LDS floats per line: one pad per M elements, odd stride
+  constexpr int LINE = ws_line<M>();      // LDS floats per line (wsort_tile.h, as the steps ws_* below)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* res = smem;                                    // [64] results of the current slice group
   float* wrow = smem + 64;                              // [LINE] weights of the row, padded like a line (weighted only)
   float* tile = wrow + (WEIGHTED ? LINE : 0);           // [SC][LINE]
-  constexpr int kTileLines = (kWsLdsBytes / 4 - 64 - (WEIGHTED ? LINE : 0)) / LINE;
-  static_assert(kTileLines >= 1, "a line must fit the LDS budget");
-  constexpr int SC = kTileLines >= 64 ? 64 : (kTileLines >= 4 ? (kTileLines & ~3) : kTileLines);   // lines per group (4 waves)
+  constexpr int SC = ws_slices<M>(kWsLdsBytes, 4 * (64 + (WEIGHTED ? LINE : 0)));   // lines per group (4 waves)
+  static_assert(SC >= 1, "a line must fit the LDS budget");
   __shared__ double msum[4];
   const int pbeg = bin_start[bin_lo], pend = bin_start[bin_hi + 1];
   const int lane = lane_id(), wv = wave_id();
@@ -53,10 +53,10 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
     const int node = perm[p];
     const int start = rowptr[node];
     const int D = rowptr[node + 1] - start;
-    const int Dtot = WEIGHTED ? D + 1 : D;              // the weighted variant always carries the pad element; Dtot <= CAP
+    const int Dtot = WEIGHTED ? D + 1 : D;              // the weighted variant always carries the pad element; Dtot <= 64 M
     double m = (double)D, rho = 0.0;
     if constexpr (WEIGHTED) {
-      double part = 0.0;
+      double part = 0.0;   // (a copy of the staging loop of k_embed_wsort_bwd: DESIGN.md, open work of the diagonal-mode steps)
       for (int t = threadIdx.x; t < D; t += blockDim.x) {
         const float wt = w ? w[start + t] : 1.f;
         wrow[t + t / M] = wt;
@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
       for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
       if (lane == 0) msum[wv] = part;
       __syncthreads();
-      m = msum[0] + msum[1] + msum[2] + msum[3];
+      m = ws_row_mass(msum);
       const float padw = (float)fmax((double)tau - m, 0.0);    // pad element: zero weight unless deficient
       rho = pad_residual((double)tau - m, padw);               // what the float line loses of it (fsw_common.h)
       if (threadIdx.x == 0) wrow[D + D / M] = padw;
@@ -77,32 +77,8 @@ __global__ void __launch_bounds__(256) k_embed_wsort(const int32_t* __restrict__
     const int ngroups = (S + SC - 1) / SC;
     for (int g = blockIdx.y; g < ngroups; g += gridDim.y) {
       const int k0 = g * SC;
-      // 1. gather + transpose: consecutive threads take consecutive slices of one neighbour.  kGatherDepth loads are
-      //    issued before the first LDS store: the loop is otherwise one HBM round trip per iteration.
-      constexpr int kGatherDepth = 8;
-      const int total = Dtot * SC;
-      for (int i0 = threadIdx.x; i0 < total; i0 += blockDim.x * kGatherDepth) {
-        float key[kGatherDepth];
-        int pos[kGatherDepth];
-#pragma unroll
-        for (int u = 0; u < kGatherDepth; ++u) {
-          const int i = min(i0 + u * (int)blockDim.x, total - 1);   // clamped: the tail re-reads the last element
-          const int kk = i % SC, t = i / SC;
-          pos[u] = kk * LINE + t + t / M;
-          key[u] = 0.f;                                  // t == D (weighted): the reference's pad element at x = 0
-          if (t < D) {
-            const int kcl = min(k0 + kk, S - 1);
-            key[u] = Xp[(int64_t)col[start + t] * ldp + kcl];
-            if (efeat) {   // edge features: + <e_ij, v_k[d_in:]> (reference fsw_embedding.py:934-968)
-              const float* er = efeat + (int64_t)(start + t) * d_edge;
-              const float* vr = Ve + (int64_t)kcl * ldve;
-              for (int q = 0; q < d_edge; ++q) key[u] = fmaf(er[q], vr[q], key[u]);
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kGatherDepth; ++u) tile[pos[u]] = key[u];   // clamped duplicates store the same value
-      }
+      // 1. gather + transpose
+#include "wsort_gather.inc"
       __syncthreads();
       // 2 + 3. one wave per line
       for (int kk = wv; kk < SC; kk += 4) {
@@ -292,11 +268,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global(const int32_t* __res
         float key = __builtin_inff(), wt = 0.f;
         if (t < D) {
           key = (FSW_WSG_ABL & 1) ? (float)((t * 2654435761u) >> 8) : Xp[(int64_t)col[start + t] * ldp + k];
-          if (efeat) {   // edge features: + <e_ij, v_k[d_in:]> (reference fsw_embedding.py:934-968)
-            const float* er = efeat + (int64_t)(start + t) * d_edge;
-            const float* vr = Ve + (int64_t)k * ldve;
-            for (int q = 0; q < d_edge; ++q) key = fmaf(er[q], vr[q], key);
-          }
+          if (efeat) key = add_edge_term(key, start + t, k, efeat, Ve, ldve, d_edge);
           if constexpr (WEIGHTED) wt = w ? w[start + t] : 1.f;
         } else if (WEIGHTED && t == D) {
           key = 0.f;                                    // the reference's pad element at x = 0

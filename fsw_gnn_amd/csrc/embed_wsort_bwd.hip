@@ -14,6 +14,8 @@
 // Rows above FSW_LDS_MAX_DEG: one wave per line in a global scratch region, chunks sorted in registers and merged by
 // sweeps as in the forward; the contribution is scattered to element order inside the wave's scratch and then added
 // with one 4-byte atomic per neighbour (these rows are few).
+// The line length, the slices per group, the workgroups per row and the row mass are those of the forward (wsort_tile.h), the gather
+// of a slice group is the forward's text (wsort_gather.inc).
 #include <algorithm>
 #include <stdlib.h>
 #include "embed_launch.h"
@@ -21,6 +23,9 @@
 #include "hub_line.h"
 #include "sortnet.h"
 #include "wave_sort.h"
+#include "wsort_tile.h"
+
+#define FSW_WS_GATHER_EDGE 1   // wsort_gather.inc: this kernel has edge features
 
 namespace fsw {
 
@@ -28,7 +33,6 @@ namespace fsw {
 // workgroup per CU -- those instances take twice the lines per slice group, i.e. twice as long atomic runs per neighbour
 template <int M, bool WEIGHTED>
 constexpr int wb_lds_bytes() { return (WEIGHTED ? M >= 64 : M >= 32) ? 140 * 1024 : 69 * 1024; }
-constexpr int kWbSplitY = 4;
 #ifndef FSW_WSB_ABL
 #define FSW_WSB_ABL 0   // timing experiments on k_embed_wsort_bwd: 1 no atomics, 2 no sort, 4 no coefficient walk
 #endif
@@ -97,14 +101,12 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
                                                          int64_t ldgp, float* __restrict__ gfreq, const float* __restrict__ efeat,
                                                          const float* __restrict__ Ve, int64_t ldve, int d_edge,
                                                          float* __restrict__ gkey, int64_t ldk) {
-  constexpr int CAP = M * kWave;
-  constexpr int LINE = CAP + kWave + 1;   // one pad per M elements, odd stride
+  constexpr int LINE = ws_line<M>();      // wsort_tile.h, as ws_slices and ws_row_mass below
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* wrow = smem;                                   // [LINE] weights of the row, padded like a line (weighted only)
   float* tile = smem + (WEIGHTED ? LINE : 0);           // [SC][LINE]
-  constexpr int kTileLines = (wb_lds_bytes<M, WEIGHTED>() / 4 - (WEIGHTED ? LINE : 0)) / LINE;
-  static_assert(kTileLines >= 1, "a line must fit the LDS budget");
-  constexpr int SC = kTileLines >= 64 ? 64 : (kTileLines >= 4 ? (kTileLines & ~3) : kTileLines);
+  constexpr int SC = ws_slices<M>(wb_lds_bytes<M, WEIGHTED>(), WEIGHTED ? 4 * LINE : 0);
+  static_assert(SC >= 1, "a line must fit the LDS budget");
   __shared__ double msum[4];
   const int pbeg = bin_start[bin_lo], pend = bin_start[bin_hi + 1];
   const int lane = lane_id(), wv = wave_id();
@@ -116,7 +118,7 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
     const int Dtot = WEIGHTED ? D + 1 : D;
     double m = (double)D;
     if constexpr (WEIGHTED) {
-      double part = 0.0;
+      double part = 0.0;   // (a copy of the staging loop of k_embed_wsort: DESIGN.md, open work of the diagonal-mode steps)
       for (int t = threadIdx.x; t < D; t += blockDim.x) {
         const float wt = w ? w[start + t] : 1.f;
         wrow[t + t / M] = wt;
@@ -125,7 +127,7 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
       part = wave_sum(part);
       if (lane == 0) msum[wv] = part;
       __syncthreads();
-      m = msum[0] + msum[1] + msum[2] + msum[3];
+      m = ws_row_mass(msum);
       if (threadIdx.x == 0) wrow[D + D / M] = (float)fmax((double)tau - m, 0.0);
       __syncthreads();
     }
@@ -137,30 +139,7 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
     const int ngroups = (S + SC - 1) / SC;
     for (int grp = blockIdx.y; grp < ngroups; grp += gridDim.y) {
       const int k0 = grp * SC;
-      constexpr int kGatherDepth = 8;
-      const int total = Dtot * SC;
-      for (int i0 = threadIdx.x; i0 < total; i0 += blockDim.x * kGatherDepth) {
-        float key[kGatherDepth];
-        int pos[kGatherDepth];
-#pragma unroll
-        for (int u = 0; u < kGatherDepth; ++u) {
-          const int i = min(i0 + u * (int)blockDim.x, total - 1);
-          const int kk = i % SC, t = i / SC;
-          pos[u] = kk * LINE + t + t / M;
-          key[u] = 0.f;                                  // t == D (weighted): the reference's pad element at x = 0
-          if (t < D) {
-            const int kcl = min(k0 + kk, S - 1);
-            key[u] = Xp[(int64_t)col[start + t] * ldp + kcl];
-            if (efeat) {
-              const float* er = efeat + (int64_t)(start + t) * d_edge;
-              const float* vr = Ve + (int64_t)kcl * ldve;
-              for (int q = 0; q < d_edge; ++q) key[u] = fmaf(er[q], vr[q], key[u]);
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kGatherDepth; ++u) tile[pos[u]] = key[u];
-      }
+#include "wsort_gather.inc"
       __syncthreads();
       for (int kk = wv; kk < SC; kk += 4) {
         const int k = k0 + kk;
@@ -168,7 +147,7 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
         WaveLine64<M> ln;
         float* line = tile + kk * LINE;
 #pragma unroll
-        for (int j = 0; j < M; ++j) {
+        for (int j = 0; j < M; ++j) {   // (k_embed_wsort_w_bwd has a copy: DESIGN.md, open work of the diagonal-mode steps)
           const int t = lane * M + j;
           ln.e[j] = pack_key_index(t < Dtot ? line[lane * (M + 1) + j] : __builtin_inff(), t);
         }
@@ -176,7 +155,7 @@ __global__ void __launch_bounds__(256, (M <= 16 ? 2 : 1)) k_embed_wsort_bwd(cons
         const double xi = (double)freqs[k];
         const float gi = out_scale * g[(int64_t)node * ldg + gcol0 + k];
         double cbase = 0.0;
-        if constexpr (WEIGHTED) {
+        if constexpr (WEIGHTED) {   // the lane's weights (k_embed_wsort_global_bwd, k_embed_wsort_w_bwd have copies: DESIGN.md, open work)
           double part = 0.0;
 #pragma unroll
           for (int j = 0; j < M; ++j) {
@@ -329,11 +308,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global_bwd(const int32_t* _
         float key = __builtin_inff();
         if (t < D) {
           key = Xp[(int64_t)col[start + t] * ldp + k];
-          if (efeat) {
-            const float* er = efeat + (int64_t)(start + t) * d_edge;
-            const float* vr = Ve + (int64_t)k * ldve;
-            for (int q = 0; q < d_edge; ++q) key = fmaf(er[q], vr[q], key);
-          }
+          if (efeat) key = add_edge_term(key, start + t, k, efeat, Ve, ldve, d_edge);
         } else if (WEIGHTED && t == D) {
           key = 0.f;
         }
@@ -364,7 +339,7 @@ __global__ void __launch_bounds__(256) k_embed_wsort_global_bwd(const int32_t* _
         }
         double cbase = 0.0;
         if constexpr (WEIGHTED) {
-          double part = 0.0;
+          double part = 0.0;   // (the lane's weights: a copy of the loop in k_embed_wsort_bwd)
 #pragma unroll
           for (int j = 0; j < M; ++j) part += (c0 + lane * M + j < Dtot) ? (double)weight_of(ln.index(j)) : 0.0;
           cbase = carry + wave_exclusive_scan_f64(part);
@@ -399,7 +374,7 @@ template <int M, bool WEIGHTED>
 static int launch_wsort_bwd(const fsw_embed_args& a, int bin_lo, int bin_hi, int64_t rows_upper, const float* g, int64_t ldg,
                             float* gXp, int64_t ldgp, float* gfreq, float* gkey, int64_t ldk, hipStream_t stream) {
   FSW_SET_MAX_LDS_ONCE((k_embed_wsort_bwd<M, WEIGHTED>), (wb_lds_bytes<M, WEIGHTED>()));
-  dim3 grid((unsigned)std::min<int64_t>(rows_upper, 1 << 14), kWbSplitY);
+  dim3 grid((unsigned)std::min<int64_t>(rows_upper, 1 << 14), kWsSplitY);
   k_embed_wsort_bwd<M, WEIGHTED><<<grid, 256, wb_lds_bytes<M, WEIGHTED>(), stream>>>(a.rowptr, a.col, a.w, a.perm, a.bin_start, bin_lo, bin_hi, a.Xp, a.ldp,
                                                                    a.S, a.freqs, a.tau, g, ldg, a.has_mass, a.out_scale, gXp, ldgp, gfreq,
                                                                    a.efeat, a.Ve, a.ldve, a.d_edge, gkey, ldk);

@@ -56,6 +56,20 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// edge features: key + <e_ij, v_k[d_in:]> of CSR entry `entry` and slice k (reference fsw_embedding.py:934-968)
+__device__ __forceinline__ float add_edge_term(float key, int64_t entry, int k, const float* efeat, const float* Ve, int64_t ldve,
+                                               int d_edge) {
+  const float* er = efeat + entry * d_edge;
+  const float* vr = Ve + (int64_t)k * ldve;
+  for (int q = 0; q < d_edge; ++q) key = fmaf(er[q], vr[q], key);
+  return key;
+}
+
+// the exact degree bins 1 .. FSW_REG_MAX_DEG as switch cases (conv_fused.hip has its own list from 0)
+#define FSW_CASES_1_32(X)                                                                                              \
+  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) \
+  X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
+
 __host__ __device__ inline int degree_bin(int deg) {
   if (deg <= FSW_REG_MAX_DEG) return deg;
   if (deg > FSW_HUB_MAX_DEG) return FSW_BIN_GLOBAL;
@@ -145,6 +159,17 @@ __device__ __forceinline__ double wave_exclusive_scan_f64(double v) {
     if (lane_id() >= off) inc += t;
   }
   return inc - v;
+}
+// sum of v over the lanes above this one
+__device__ __forceinline__ double wave_reverse_exclusive_scan_f64(double v) {
+  double inc = v;
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    const double t = __shfl_down(inc, off);
+    if (lane_id() + off < kWave) inc += t;
+  }
+  const double above = __shfl_down(inc, 1);
+  return lane_id() == kWave - 1 ? 0.0 : above;
 }
 
 // gradient accumulators are float32 or float64 (the generic / Cartesian paths in either precision)

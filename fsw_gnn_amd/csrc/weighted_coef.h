@@ -6,23 +6,8 @@
 
 namespace fsw {
 
-__device__ __forceinline__ void F_dF(double xi, double c, double& F, double& dF) {
-  const double x = 2.0 * kPi * xi * c;
-  if (fabs(x) < 1e-4) {
-    const double q = 1.0 - x * x * (1.0 / 6.0);
-    F = (1.0 + xi) * 2.0 * c * q;
-    dF = 2.0 * c * q - (1.0 + xi) * 2.0 * c * (2.0 * kPi * c) * (2.0 * kPi * c) * xi * (1.0 / 3.0);
-    return;
-  }
-  const double ph = xi * c;
-  double s, co;
-  sincospi(2.0 * (ph - rint(ph)), &s, &co);
-  F = (1.0 + xi) * s / (kPi * xi);
-  dF = -s / (kPi * xi * xi) + (1.0 + xi) * 2.0 * c * co / xi;
-}
-
-// F and dF as above (the same expressions, bit for bit) and h = d F / d c = 2 (1 + xi) cos(2 pi xi c), the factor of the weight
-// gradient (embed_generic.hip: H_t = h(c_t) (p_(t) - p_(t+1))), from the same sine / cosine pair.
+// F, dF / dxi (series for tiny phases: the two terms of dF cancel there) and h = d F / d c = 2 (1 + xi) cos(2 pi xi c), the factor of
+// the weight gradient (embed_generic.hip: H_t = h(c_t) (p_(t) - p_(t+1))), from one sine / cosine pair.
 __device__ __forceinline__ void F_dF_h(double xi, double c, double& F, double& dF, double& h) {
   const double x = 2.0 * kPi * xi * c;
   if (fabs(x) < 1e-4) {
@@ -38,6 +23,11 @@ __device__ __forceinline__ void F_dF_h(double xi, double c, double& F, double& d
   F = (1.0 + xi) * s / (kPi * xi);
   dF = -s / (kPi * xi * xi) + (1.0 + xi) * 2.0 * c * co / xi;
   h = 2.0 * (1.0 + xi) * co;
+}
+// the kernels without a weight gradient: h unused, the same F and dF bit for bit
+__device__ __forceinline__ void F_dF(double xi, double c, double& F, double& dF) {
+  double h;
+  F_dF_h(xi, c, F, dF, h);
 }
 
 }  // namespace fsw

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Compare the device code of two builds kernel by kernel.  Needs hipcc, no GPU.
 
-  tools/compare_kernel_asm.py emit <csrc dir> <out dir> [-j N]   every translation unit of the Makefile -> <out dir>/<unit>.s
-                                                                 (the Makefile's flags + --cuda-device-only -S)
+  tools/compare_kernel_asm.py emit <csrc dir> <out dir> [-j N]   every translation unit of <csrc dir>/Makefile (SRCS and the part
+                                                                 rules) -> <out dir>/<unit>.s (its flags + --cuda-device-only -S)
   tools/compare_kernel_asm.py diff <out dir A> <out dir B>       kernels compared / removed / added / differing
 
 Two kernels are equal when their instruction streams and their .amdhsa_ descriptor (registers, scratch, LDS, ...) are
@@ -17,12 +17,26 @@ import shutil
 import subprocess
 import sys
 
-UNITS = [(f, "", f) for f in ("api graph_build graph_import project embed_reg embed_wsort embed_generic embed_wsort_bwd embed_api conv_fused "
-                              "embed_bwd segcumsum gemm_tn embed_cart embed_cart_bwd embed_cart_hub embed_cart_hub_bwd embed_cart_hub_w "
-                              "embed_cart_hub_w_bwd embed_giant_cart embed_split_cart embed_giant_cart_w embed_split_cart_w embed_giant_cart_bwd embed_split_cart_bwd embed_split_cart_w_bwd edge_keys embed_w_bwd embed_w_sort_bwd").split()]
-UNITS += [("embed_mid", "-DFSW_MID_PART=%d" % p, "embed_mid_%d" % p) for p in range(3)]
-UNITS += [("embed_mid_bwd", "-DFSW_MID_BWD_PART=%d" % p, "embed_mid_bwd_%d" % p) for p in range(2)]
-UNITS += [("embed_hub", "-DFSW_HUB_PART=%d" % p, "embed_hub_%d" % p) for p in range(3)]
+MAKEFILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "fsw_gnn_amd", "csrc", "Makefile")
+
+
+def units_of(makefile_text):
+    """[(source without .hip, define or "", unit name)] from the Makefile's text: one unit per file of SRCS, and for every part rule
+    `$(OBJDIR)/name_%.o: src.hip ...` with `-DMACRO=$*` in its recipe one unit per `$(OBJDIR)/name_<n>.o` listed in OBJS"""
+    text = makefile_text.replace("\\\n", " ")
+    var = lambda name: re.search(r"^%s\s*:?=\s*(.*)$" % name, text, re.M).group(1).split()
+    units = [(f[:-4], "", f[:-4]) for f in var("SRCS") if f.endswith(".hip")]
+    objs = var("OBJS")
+    for m in re.finditer(r"^\$\(OBJDIR\)/(\w+)_%\.o:\s*(\w+)\.hip\b.*\n(?:\t.*\n)*?\t.*-D(\w+)=\$\*", text, re.M):
+        stem, src, macro = m.groups()
+        for o in objs:
+            n = re.fullmatch(r"\$\(OBJDIR\)/%s_(\d+)\.o" % re.escape(stem), o)
+            if n:
+                units.append((src, "-D%s=%s" % (macro, n.group(1)), "%s_%s" % (stem, n.group(1))))
+    return units
+
+
+UNITS = units_of(open(MAKEFILE).read()) if os.path.exists(MAKEFILE) else []
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function --cuda-device-only -S".split()
 
 
@@ -36,8 +50,9 @@ def emit(csrc, out, jobs):
         return name, subprocess.run(cmd, cwd=csrc, capture_output=True, text=True)
 
     failed = 0
+    units = units_of(open(os.path.join(csrc, "Makefile")).read())
     with concurrent.futures.ThreadPoolExecutor(jobs) as pool:
-        for name, r in pool.map(one, UNITS):
+        for name, r in pool.map(one, units):
             print("%-18s %s" % (name, "ok" if r.returncode == 0 else "FAILED\n" + r.stderr))
             failed += r.returncode != 0
     return 1 if failed else 0
