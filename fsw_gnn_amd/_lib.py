@@ -106,6 +106,7 @@ _SIGNATURES = {
     "fsw_embed_backward_keys_f32": (ctypes.c_int, [ctypes.POINTER(EmbedArgs), c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "fsw_embed_backward_w_scratch_bytes": (c_sz, [c_i64, c_i64]),
     "fsw_embed_backward_w_tuned_max_degree": (ctypes.c_int, []),
+    "fsw_embed_backward_w_long_slices": (ctypes.c_int, []),
     "fsw_embed_backward_w_f32": (ctypes.c_int, [ctypes.POINTER(EmbedArgs), c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "fsw_embed_backward_w_lo_f32": (ctypes.c_int, [ctypes.POINTER(EmbedArgs), c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz,
                                                    c_vp]),

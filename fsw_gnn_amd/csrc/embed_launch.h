@@ -84,13 +84,21 @@ GenArgs generic_args(const P& p, bool cartesian, int F) {
 int launch_embed_generic(GenArgs a, int value_dtype, const int32_t* rows, int64_t num_rows, int min_deg, hipStream_t stream);
 
 // backward with the gradient of the weights (fsw_embed_backward_w_f32, embed_w_bwd.hip): register kernels for rows of up to
-// kWRegMaxDeg neighbours, embed_w_sort_bwd.hip (one (row, slice) line per wavefront) up to kWSortMaxDeg, the generic kernel above.
+// kWRegMaxDeg neighbours, embed_w_sort_bwd.hip (one (row, slice) line per wavefront) up to kWSortMaxDeg, embed_w_long_bwd.hip (one
+// wavefront per (row, kWLongSlices slices) on a scratch line in global memory) above.
 // 1024, not FSW_LDS_MAX_DEG: the instance of 64 ranks per lane for 1025 .. 2048 neighbours spills (DESIGN.md has the table).
 constexpr int kWRegMaxDeg = 24;
 constexpr int kWSortMaxDeg = 1024;
 constexpr int kWSortLastBin = FSW_BIN_LDS0 + 1;   // 513 .. 1024
 int launch_embed_wsort_w_bwd(const fsw_embed_args& a, const float* w_lo, const float* g, int64_t ldg, float* gkey, int64_t ldk, float* gfreq,
                              float* gw, hipStream_t stream);
+// embed_w_long_bwd.hip.  kWLongSlices (fsw_embed_backward_w_long_slices): the slices a wavefront sums in float64 before its one
+// float32 add per entry -- DESIGN.md, "Rows above 1024 neighbours", says why 4.  kWLongRanks: ranks per lane of a chunk (chunks of
+// 1024 words; the instance of 32 spills 12 bytes per lane at 512 registers: the table there).
+constexpr int kWLongSlices = 4;
+constexpr int kWLongRanks = 16;
+int launch_embed_w_long_bwd(const fsw_embed_args& a, const float* w_lo, int64_t max_degree, const float* g, int64_t ldg, float* gkey,
+                            int64_t ldk, float* gfreq, float* gw, void* scratch, size_t scratch_bytes, hipStream_t stream);
 
 // backward: embed_mid_bwd.hip (33 .. 128) and embed_wsort_bwd.hip (everything above FSW_REG_MAX_DEG; global: rows above FSW_LDS_MAX_DEG)
 int launch_embed_mid_bwd(const fsw_embed_args& a, int64_t rows_upper, const float* g, int64_t ldg, float* gXp, int64_t ldgp,

@@ -25,7 +25,8 @@
 namespace fsw {
 
 constexpr int kWBwdRows = 32;
-// Rows above kWRegMaxDeg (embed_launch.h) go to the wave-sort kernels of embed_w_sort_bwd.hip.  24, not FSW_REG_MAX_DEG: the form below
+// Rows above kWRegMaxDeg (embed_launch.h) go to the wave-sort kernels of embed_w_sort_bwd.hip, rows above kWSortMaxDeg to the
+// scratch-line kernels of embed_w_long_bwd.hip.  24, not FSW_REG_MAX_DEG: the form below
 // for 25 .. 32 neighbours (key, cum / R and q of 32 elements live at once) spills 244 - 324 bytes per lane at 512 registers; DESIGN.md
 // has the table.
 static_assert(kWRegMaxDeg <= FSW_REG_MAX_DEG, "the degree bins are exact up to FSW_REG_MAX_DEG only");
@@ -179,10 +180,12 @@ static int launch_w_bwd(const fsw_embed_args& a, const float* w_lo, int64_t nreg
 using namespace fsw;
 
 // an upper bound since the rows of 25 .. kWSortMaxDeg neighbours left the generic kernel: what it returned before, for every input
+// (36 bytes per element of the padded line for at least one workgroup: embed_w_long_bwd.hip takes 20 per wavefront)
 extern "C" size_t fsw_embed_backward_w_scratch_bytes(int64_t max_degree, int64_t num_rows) {
   return max_degree > kWRegMaxDeg ? fsw_embed_generic_scratch_bytes(max_degree, num_rows) : 0;
 }
 
+// the largest degree that needs no scratch
 extern "C" int fsw_embed_backward_w_tuned_max_degree(void) { return kWSortMaxDeg; }
 
 static int embed_backward_w(const fsw_embed_args* args, const float* w_lo, int64_t max_degree, const float* g, int64_t ldg,
@@ -198,6 +201,16 @@ static int embed_backward_w(const fsw_embed_args* args, const float* w_lo, int64
   if (a.num_rows <= 0) return 0;
   const int64_t nreg = a.num_reg_rows < 0 ? a.num_rows : a.num_reg_rows;
   int rc;
+  // rows above kWSortMaxDeg neighbours: one wavefront per (row, kWLongSlices slices) on a scratch line (embed_w_long_bwd.hip), every bin
+  // that has rows.  The longest rows first; it is also the only launcher that can refuse the buffer, before anything is launched.
+  bool longer = max_degree > kWSortMaxDeg;
+  if (longer && a.bin_start_host) longer = a.bin_start_host[FSW_NUM_BINS] > a.bin_start_host[kWSortLastBin + 1];
+  else if (longer) longer = a.num_lds_rows != 0 || a.num_global_rows != 0;   // -1: unknown
+  if (longer) {
+    FSW_REQUIRE(scratch, "fsw_embed_backward_w_f32: rows above %d neighbours need scratch (fsw_embed_backward_w_scratch_bytes)",
+                kWSortMaxDeg);
+    if ((rc = launch_embed_w_long_bwd(a, w_lo, max_degree, g, ldg, gkey, ldk, gfreq, gw, scratch, scratch_bytes, stream))) return rc;
+  }
   if (nreg > 0) {
     // long rows first
     if ((rc = launch_w_bwd<17, 24>(a, w_lo, nreg, g, ldg, gkey, ldk, gfreq, gw, stream))) return rc;
@@ -206,22 +219,10 @@ static int embed_backward_w(const fsw_embed_args* args, const float* w_lo, int64
   }
   // 25 .. kWSortMaxDeg neighbours: one (row, slice) line per wavefront (embed_w_sort_bwd.hip), every bin that has rows
   if (max_degree > kWRegMaxDeg && (rc = launch_embed_wsort_w_bwd(a, w_lo, g, ldg, gkey, ldk, gfreq, gw, stream))) return rc;
-  // every longer row: the generic kernel, by row index over the whole graph, skipping the rows of the classes above
-  bool longer = max_degree > kWSortMaxDeg;
-  if (longer && a.bin_start_host) longer = a.bin_start_host[FSW_NUM_BINS] > a.bin_start_host[kWSortLastBin + 1];
-  else if (longer) longer = a.num_lds_rows != 0 || a.num_global_rows != 0;   // -1: unknown
-  if (longer) {
-    FSW_REQUIRE(scratch, "fsw_embed_backward_w_f32: rows above %d neighbours need scratch (fsw_embed_backward_w_scratch_bytes)",
-                kWSortMaxDeg);
-    GenArgs ga = {};
-    ga.rowptr = a.rowptr; ga.col = a.col; ga.w = a.w; ga.Xp = a.Xp; ga.ldp = a.ldp; ga.freqs = a.freqs; ga.S = a.S; ga.F = 1;
-    ga.cartesian = false; ga.tau = (double)a.tau; ga.out_scale = (double)a.out_scale; ga.has_mass = a.has_mass;
-    ga.g = g; ga.ldg = ldg; ga.gkey = gkey; ga.ldk = ldk; ga.gfreq = gfreq; ga.gw = gw;
-    ga.scratch = (char*)scratch; ga.scratch_bytes = scratch_bytes; ga.max_degree = max_degree;
-    if ((rc = launch_embed_generic(ga, 0, nullptr, a.num_rows, kWSortMaxDeg + 1, stream))) return rc;
-  }
   return 0;
 }
+
+extern "C" int fsw_embed_backward_w_long_slices(void) { return kWLongSlices; }
 
 extern "C" int fsw_embed_backward_w_f32(const fsw_embed_args* args, int64_t max_degree, const float* g, int64_t ldg, float* gkey,
                                         int64_t ldk, float* gfreq, float* gw, void* scratch, size_t scratch_bytes,

@@ -307,8 +307,8 @@ class FSW_conv(_Base):
         run (diagonal and Cartesian mode, with edge features, float64, the tuple CSR form with edge_weight [nnz] aligned with the
         entries).  Weights that require grad: float32 edge list in diagonal mode without edge features and with the plain degree
         encoding (FSW_embedding.embed_autograd(edge_weight=): recipients of up to 24 neighbours on the register kernels of
-        csrc/embed_w_bwd.hip, of 25 .. 1024 on the wave-sort kernels of csrc/embed_w_sort_bwd.hip, only longer ones on the generic
-        kernel), and float64 layers (the generic kernels);
+        csrc/embed_w_bwd.hip, of 25 .. 1024 on the wave-sort kernels of csrc/embed_w_sort_bwd.hip, longer ones on the scratch-line
+        kernels of csrc/embed_w_long_bwd.hip), and float64 layers (the generic kernels);
         NotImplementedError for float32 Cartesian mode, float32 with edge features, float32 homog_degree_encoding and the tuple CSR
         form.  Not with a torch.sparse_csr adjacency (its values are the weights), not under enable_slice_parallel /
         enable_node_parallel; cache_graph is bypassed.

@@ -313,8 +313,10 @@ class _EmbedGraphWFn(torch.autograd.Function):
     (fsw_embed_backward_w_lo_f32), because d out / d w at frequency xi feels a weight's rounding times 2 pi xi.
     Forward: the tuned path of _EmbedGraphFn (prepare + embed_into).  Backward: fsw_embed_backward_w_f32 (rows of up to 24
     neighbours on the register kernels of csrc/embed_w_bwd.hip, rows of 25 .. fsw_embed_backward_w_tuned_max_degree() = 1024 on the
-    wave-sort kernels of csrc/embed_w_sort_bwd.hip, one (row, slice) line per wavefront; only longer rows on the generic kernel,
-    which reads the float32 weights alone) stores the key gradients per entry and accumulates gfreq and gw; gXp is their sum sender by sender (graph.sender_major + fsw_segment_sum_rows_f32).  The total-mass
+    wave-sort kernels of csrc/embed_w_sort_bwd.hip, one (row, slice) line per wavefront; longer rows on the scratch-line kernels of
+    csrc/embed_w_long_bwd.hip, one wavefront per (row, fsw_embed_backward_w_long_slices() = 4 slices) on a line in the scratch buffer;
+    every class reads w + w_lo) stores the key gradients per entry and accumulates gfreq and gw; gXp is their sum sender by sender
+    (graph.sender_major + fsw_segment_sum_rows_f32).  The total-mass
     column depends on the weights through m: out_scale scale g[:, 0] f'(m) per recipient is added, as in _GenericEmbedFn.backward.
     Pad rule: as _GenericEmbedFn.key_grads -- without a deficient row (empty recipients included) the launch gets tau / 2."""
 
@@ -361,7 +363,7 @@ class _EmbedGraphWFn(torch.autograd.Function):
             a = module.make_args(graph, st, Xp, ldp, fr, S, None, None, 0, None, out_scale, has_mass)
             if not bool((m < tau).any()):
                 a.tau = 0.5 * tau                      # no row is padded: _GenericEmbedFn.key_grads explains
-            # scratch: only the generic kernel's, for rows above the tuned classes (the query is an upper bound)
+            # scratch: the lines of the rows that need one, above fsw_embed_backward_w_tuned_max_degree() (the query is an upper bound)
             nbytes = int(L.fsw_embed_backward_w_scratch_bytes(max_deg, graph.num_rows)) if max_deg > L.fsw_embed_backward_w_tuned_max_degree() else 0
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
             gkey = torch.empty((nnz, S), dtype=torch.float32, device=dev)
@@ -1498,7 +1500,8 @@ class FSW_embedding(nn.Module):
         feature tensor the graph was coalesced from (its gradient is routed back through graph.slot_of_edge).
         slice_range / group: this rank's block of slices under slice sharding (dist.py).
         edge_weight: the per-input-edge weights [num_input_edges] a coalesced graph (want_slots=True, no edge features) was built
-        from; the embedding is then differentiable in them too (_EmbedGraphWFn; 'plain' mass encoding, no slice sharding)."""
+        from; the embedding is then differentiable in them too (_EmbedGraphWFn; 'plain' mass encoding, no slice sharding): rows of up
+        to 24 neighbours on csrc/embed_w_bwd.hip, 25 .. 1024 on csrc/embed_w_sort_bwd.hip, longer ones on csrc/embed_w_long_bwd.hip."""
         bias = self.bias if self.enable_bias else None
         scale = self.total_mass_encoding_scale if self.encode_total_mass else None
         if edge_weight is not None:

@@ -373,20 +373,27 @@ int fsw_segment_sum_rows_f32(const float* src, int64_t lds, const int32_t* ptr, 
  * atomic per entry and chunk).  Rows of 25 .. fsw_embed_backward_w_tuned_max_degree() = 1024 neighbours run on the wave-sort kernels
  * of csrc/embed_w_sort_bwd.hip: one (row, slice) line of D + 1 packed (key, element index) words per wavefront, float64 cumulative
  * weights and coefficients, the slices a workgroup visits for a row summed in float64 in LDS, at most 4 float32 atomics per entry.
- * Only longer rows run on the generic kernel below (value_dtype 0), launched only when the host-side row counts of args
- * (bin_start_host, else num_lds_rows / num_global_rows; -1 = unknown) say such rows exist; only then is scratch required.
- * fsw_embed_backward_w_scratch_bytes(max_degree, num_rows) is an UPPER BOUND of what a call needs (0 when max_degree <= 24): a call
- * with scratch == NULL, scratch_bytes == 0 succeeds on a graph without rows above fsw_embed_backward_w_tuned_max_degree().
+ * Longer rows run on the scratch-line kernels of csrc/embed_w_long_bwd.hip: one wavefront per (row, group of
+ * fsw_embed_backward_w_long_slices() consecutive slices), the line sorted in chunks of 1024 packed words and merged by sweeps over a
+ * line in `scratch`, the group's slices summed in float64 in that line, ceil(S / fsw_embed_backward_w_long_slices()) float32 atomics
+ * per entry.  They are launched only when the host-side row counts of args (bin_start_host, else num_lds_rows / num_global_rows;
+ * -1 = unknown) say such rows exist; only then is scratch required.  A wavefront's line takes 20 bytes per element of
+ * pow2ceil(longest row of its degree bin + 1); the call uses min(scratch_bytes / that, 2048, tasks) wavefronts per bin and fails,
+ * before anything is launched, when scratch_bytes holds no line of the largest non-empty bin.
+ * fsw_embed_backward_w_scratch_bytes(max_degree, num_rows) is an UPPER BOUND of what a call needs (0 when max_degree <= 24; above,
+ * fsw_embed_generic_scratch_bytes: 36 bytes per element of pow2ceil(max_degree + 1) for up to 2048 lines): a call with
+ * scratch == NULL, scratch_bytes == 0 succeeds on a graph without rows above fsw_embed_backward_w_tuned_max_degree().
  * max_degree: host value, an upper bound of the longest row.                                                         */
 size_t fsw_embed_backward_w_scratch_bytes(int64_t max_degree, int64_t num_rows);
-int fsw_embed_backward_w_tuned_max_degree(void); /* longest row of the register and wave-sort kernels: 1024 */
+int fsw_embed_backward_w_tuned_max_degree(void); /* the largest degree that needs no scratch: 1024 */
+int fsw_embed_backward_w_long_slices(void);      /* slices per wavefront task of the rows above: 4 */
 int fsw_embed_backward_w_f32(const fsw_embed_args* args, int64_t max_degree, const float* g, int64_t ldg, float* gkey, int64_t ldk,
                              float* gfreq, float* gw, void* scratch, size_t scratch_bytes, fsw_stream_t stream);
 /* The same with weights of more than float32 precision: entry e has the weight w[e] + w_lo[e] (w_lo [nnz], NULL = 0), summed in
- * float64 by the register and wave-sort kernels -- weights that the host computed in float64 ('gcn' normalisation, sums of parallel edges) and
+ * float64 by every kernel of this entry -- weights that the host computed in float64 ('gcn' normalisation, sums of parallel edges) and
  * split into a float32 value and its float32 remainder.  d out / d w at frequency xi feels a weight's rounding times 2 pi xi, so the
- * 2^-25 of a float32 weight shows in the gradient of a short row at xi ~ 100 (DESIGN.md "Per-edge weights").  The rows above 1024
- * neighbours (generic kernel) and the forward read w alone.                                                             */
+ * 2^-25 of a float32 weight shows in the gradient of a short row at xi ~ 100 (DESIGN.md "Per-edge weights").  The forward reads
+ * w alone.                                                                                                              */
 int fsw_embed_backward_w_lo_f32(const fsw_embed_args* args, const float* w_lo, int64_t max_degree, const float* g, int64_t ldg,
                                 float* gkey, int64_t ldk, float* gfreq, float* gw, void* scratch, size_t scratch_bytes,
                                 fsw_stream_t stream);

@@ -5,8 +5,8 @@
     python tools/exp_train_step.py --rmat 22 --edges 64000000 --feat 256 --forward-only [--gcn]   BASELINE config 5's shape
     python tools/exp_train_step.py --edge-weights   learnable per-edge weights (FSW_conv.forward(edge_weight=)): the training step, and
                                                     the embedding's backward on the tuned kernels (csrc/embed_w_bwd.hip up to 24
-                                                    neighbours, csrc/embed_w_sort_bwd.hip up to the library's class limit, the
-                                                    generic kernel for the rows above) against the generic kernel's for every row
+                                                    neighbours, csrc/embed_w_sort_bwd.hip up to the library's class limit,
+                                                    csrc/embed_w_long_bwd.hip for the rows above) against the generic kernel's for every row
                                                     (FSW_embedding.forward with a sparse COO W that requires grad), alternating;
                                                     also the share of the entries in each of the three classes
 """
@@ -64,10 +64,10 @@ if args.edge_weights:
     deg = torch.bincount(adj.indices()[0], minlength=n)          # entries per recipient of the coalesced adjacency
     nnz = int(deg.sum())
     share = [int(deg[sel].sum()) / nnz for sel in (deg <= 24, (deg > 24) & (deg <= limit), deg > limit)]
-    print("entries per class: <= 24 neighbours (register kernels) %.1f %%, 25 .. %d (wave-sort kernels) %.1f %%, above (generic kernel) "
+    print("entries per class: <= 24 neighbours (register kernels) %.1f %%, 25 .. %d (wave-sort kernels) %.1f %%, above (scratch-line kernels) "
           "%.1f %% of %d; rows: %d / %d / %d" % (100 * share[0], limit, 100 * share[1], 100 * share[2], nnz, int((deg <= 24).sum()),
                                                  int(((deg > 24) & (deg <= limit)).sum()), int((deg > limit).sum())), flush=True)
-    tuned = "tuned kernels (embed_w_bwd.hip, embed_w_sort_bwd.hip; generic above %d)" % limit
+    tuned = "tuned kernels (embed_w_bwd.hip, embed_w_sort_bwd.hip; embed_w_long_bwd.hip above %d)" % limit
     times = {tuned: [], "generic kernel": []}
     for i in range(args.runs + 1):                      # run 0 warms both up
         for name, fn in ((tuned, new_route), ("generic kernel", generic_route)):
